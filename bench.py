@@ -32,6 +32,9 @@ launch stream, algorithmic bytes over device time), `no_share` (the same step wh
 re-bins instead of reusing the forward's binning: what the plain C entry points give) and, on
 rank 0 at N = 1, `cpu_baseline` (threaded CPU port of the reference algorithm from oracle/, on
 a bounded sample of the same workload).
+
+`--dump-outputs DIR` writes the outputs of the last timed step as .npy files (see dump_outputs);
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -63,6 +66,47 @@ CONFIGS = {
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_COPY_GBS = 6290.0  # measured float4 copy ceiling (same guide)
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: array data of all files (+ .npy headers < 64 MB)
+DUMP_SEED = 0  # --dump-outputs: the element sample of an array too large to write whole
+
+
+def _memory_order_flat(x):
+    """1-D view of a dense tensor in its memory order (no copy for the permuted grid views)."""
+    order = sorted(range(x.ndim), key=lambda d: -x.stride(d))
+    return x.permute(order).reshape(-1)
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write `arrays` (name -> tensor; None is skipped) as `outdir/<name>.npy`, at most `budget`
+    bytes of data in all.  Smallest first, each array gets an equal share of what is left: it
+    is written whole (its own shape) when it fits, else as a 1-D sample of its elements in
+    memory order at sorted indices drawn with DUMP_SEED -- the same indices for the same
+    shape, so that two builds can be compared element for element.  Returns the manifest."""
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    items = sorted(((n, t) for n, t in arrays.items() if t is not None),
+                   key=lambda nt: nt[1].numel() * nt[1].element_size())
+    left, manifest = budget, {}
+    for i, (name, t) in enumerate(items):
+        if t.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"dump_outputs: {name} is {t.dtype}, expected float32 or float64")
+        share = left // (len(items) - i)
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", "")}
+        if t.numel() * t.element_size() <= share:
+            a = t.detach().contiguous().cpu().numpy()  # (keeps a 0-d array 0-d)
+        else:
+            k = share // t.element_size()
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), size=k))
+            flat = _memory_order_flat(t.detach())
+            a = flat.index_select(0, torch.as_tensor(idx, device=t.device)).cpu().numpy()
+            entry["sample"] = {"elements": int(a.size), "seed": DUMP_SEED, "draws": int(k),
+                               "indices": "np.unique(np.random.default_rng(seed).integers(0, numel, draws)) "
+                                          "into the elements in memory order"}
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes
+        manifest[name] = entry
+    return manifest
 
 
 def morton_order(pts, bits=10):
@@ -448,6 +492,7 @@ def run_job(args, cfg, rank, world, device, dist, backend, lean=False):
     fused_alt = torch.empty_like(fused) if overlap else None
     pending = [None, None]
     step_no = [0]
+    last_res = [None]  # the pullback's outputs of the latest step (views of its fused buffer)
 
     def all_reduce(buf, async_op=False):
         if backend == "nccl":
@@ -469,6 +514,7 @@ def run_job(args, cfg, rank, world, device, dist, backend, lean=False):
             all_reduce(out.permute(*reversed(range(out.ndim))))  # the contiguous grid buffer
         if do_bwd:
             res = bwd(buf, share_step)
+            last_res[0] = res
             if pose_exchange:
                 pending[k] = all_reduce(buf, async_op=overlap)
             elif world > 1 and shard == "points":
@@ -528,6 +574,18 @@ def run_job(args, cfg, rank, world, device, dist, backend, lean=False):
     units = (B_global * P) if shard != "points" else P  # (point, pose) pairs per step, whole job
     value = units / (elapsed / args.steps) / 1e6
     untimed_steps = 2 + (0 if lean else args.steps) + n_spin + args.warmup
+
+    # ---- --dump-outputs: what the last timed step handed its caller (rank 0's share), before any
+    # later measurement overwrites the buffers; the barrier after the loop has synchronised
+    dumped = None
+    if args.dump_outputs and not lean and rank == 0:
+        res = last_res[0]
+        arrays = {"out": out if B_local > 0 else None}
+        if res is not None:
+            arrays.update(ds_dpoints=res.points, ds_drotation=res.rotation, ds_dtranslation=res.translation,
+                          ds_dbackground=res.background, ds_dout_weight=res.out_weight,
+                          ds_dpoint_weight=res.point_weight)
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, arrays)}
 
     # ---- per-pass device time with HIP events on the launch stream (torch's current stream);
     # forward and pullback are timed inside fwd+bwd pairs (the pullback consumes -- and, when it
@@ -657,6 +715,8 @@ def run_job(args, cfg, rank, world, device, dist, backend, lean=False):
                if world > 1 else {})},
         "roofline": roof,
     }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     if can_share and not args.no_share_binning and world == 1 and not lean:
         # the drop-in number: plain entry points (no KEEP/REUSE flags), the pullback re-bins
         for _ in range(max(1, args.warmup)):
@@ -894,6 +954,10 @@ def main():
                     help="skip the secondary measurement on Morton-sorted points")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the forward's grid and "
+                         "the pullback's gradients, rank 0) as DIR/<name>.npy, at most 64 MB in all: an "
+                         "array too large for its share is written as a fixed, seeded element sample")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")

@@ -855,6 +855,45 @@ def test_bench_default_line_carries_the_scaling_reference():
     assert isinstance(line["config"]["untimed_steps"], int) and line["config"]["untimed_steps"] >= 3 + 1 + 2
 
 
+def test_bench_dump_outputs_are_the_step_outputs_and_repeat(oracle, dev, tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's forward grid and pullback gradients as .npy
+    files; two runs with the same arguments see the same inputs (C1: against the oracle as well)."""
+    import subprocess
+    import sys
+
+    import bench
+
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C1", "--steps", "2",
+                            "--warmup", "1", "--loops", "1", "--no-spin-up", "--no-cpu-baseline",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        assert sorted(line["dumped_outputs"]["arrays"]) == sorted(
+            ["out", "ds_dpoints", "ds_drotation", "ds_dtranslation", "ds_dbackground", "ds_dout_weight",
+             "ds_dpoint_weight"])
+        dumps.append({n: np.load(d / f"{n}.npy") for n in line["dumped_outputs"]["arrays"]})
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float64, n
+        assert_close(dumps[1][n], a, 1e-12)  # (atomics: equal up to the summation order)
+    # what the step computed: C1's seeded inputs through the oracle
+    pts = bench.synth_points("C1")
+    R, t = bench.synth_poses("C1", 1, seed=1)
+    ref = oracle.raster((5, 5), pts, R, t)
+    assert_close(dumps[0]["out"], ref[..., 0], 1e-12, "out")
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(2)  # bench.py's ds_dout of rank 0: randn of the reversed grid shape, seen [i1, i2]
+    g = torch.randn((5, 5), device=dev, dtype=torch.float64, generator=gen).permute(1, 0).cpu().numpy()
+    rpb = oracle.raster_pullback(g[..., None], pts, R, t)
+    for n, e in (("ds_dpoints", rpb.points), ("ds_drotation", rpb.rotation[0]),
+                 ("ds_dtranslation", rpb.translation[0]), ("ds_dbackground", rpb.background[0]),
+                 ("ds_dout_weight", rpb.out_weight[0]), ("ds_dpoint_weight", rpb.point_weight)):
+        assert_close(dumps[0][n], e, 1e-10, n)
+
+
 # ------------------------------------------------------------------ the FULL jobs, checked once
 def test_c4_full_job_512_poses_against_the_oracle(oracle, dev):
     """BASELINE.json configs[3] as ONE GPU runs it for the N > 1 curve's one-GPU point
