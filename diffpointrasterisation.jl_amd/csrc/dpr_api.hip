@@ -131,8 +131,7 @@ static bool chunkown_preferred(int op, int n_in, int n_out, const int64_t* grid,
 // which forward the 3-D algorithm runs: chunk lists (small tiles) for a sparse cloud over several
 // poses, owner-computes large tiles otherwise
 static bool chunked3d_lists(const int64_t* grid, int64_t G, int64_t P, int64_t B) {
-    static const bool off = env_knob("DPR_CHUNKED3D_NO_LISTS", 0, 0, 1) != 0;  // (experiments: owner tiles everywhere)
-    return !off && B >= 4 && P * 10 <= G && chunked_supported(3, grid);
+    return B >= 4 && P * 10 <= G && chunked_supported(3, grid);
 }
 static bool chunked3d_preferred(int op, int n_out, const int64_t* grid, int64_t G, int64_t P,
                                 int64_t B, unsigned flags) {

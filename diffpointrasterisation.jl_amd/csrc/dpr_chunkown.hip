@@ -45,33 +45,16 @@
 namespace dpr {
 
 constexpr int kCOThreads = 1024;
-#ifndef DPR_CO_SPLAT_OCC
-#define DPR_CO_SPLAT_OCC 8  // waves per SIMD the fp32 forward kernel is compiled for
-#endif
-#ifndef DPR_CO_PPT
-#define DPR_CO_PPT 4
-#endif
-#ifndef DPR_CO_WIDE_BLOCKS
-#define DPR_CO_WIDE_BLOCKS 1024
-#endif
-constexpr int kCOWideBlocks = DPR_CO_WIDE_BLOCKS; // grid of k_co_splat_wide (walks a work list)
-#ifndef DPR_CO_WIDE_GROUP
-#define DPR_CO_WIDE_GROUP 8
-#endif
-constexpr int kCOWideGroup = DPR_CO_WIDE_GROUP;   // poses per work item of k_co_splat_wide
-constexpr int kCOPPT = DPR_CO_PPT;               // points per thread
+constexpr int kCOSplatOcc = 8;                   // waves per SIMD the fp32 forward kernel is compiled for
+constexpr int kCOWideBlocks = 1024;              // grid of k_co_splat_wide (walks a work list)
+constexpr int kCOWideGroup = 8;                  // poses per work item of k_co_splat_wide
+constexpr int kCOPPT = 4;                        // points per thread
 constexpr int kCOChunk = kCOThreads * kCOPPT;    // 4096 points per block
 constexpr int kCOWaves = kCOThreads / kWave;
-#ifndef DPR_CO_CAP
-#define DPR_CO_CAP 9984
-#endif
-constexpr int kCOCap = DPR_CO_CAP;               // LDS tile cells (8 bytes each): 78 KiB, 2 blocks / CU
+constexpr int kCOCap = 9984;                     // LDS tile cells (8 bytes each): 78 KiB, 2 blocks / CU
                                                  // (round 2: 9216; fewer wide pairs, C4 forward -2 %)
-constexpr int kCOWideCap = 2 * kCOCap;            // tile of k_co_splat_wide (one workgroup per CU)
-#ifndef DPR_CO_GATHER_CAP
-#define DPR_CO_GATHER_CAP 8192
-#endif
-constexpr int kCOGatherCap = DPR_CO_GATHER_CAP;   // cells (of T) of the pullback's ds_dout tile
+constexpr int kCOWideCap = 2 * kCOCap;           // tile of k_co_splat_wide (one workgroup per CU)
+constexpr int kCOGatherCap = 8192;               // cells (of T) of the pullback's ds_dout tile
 constexpr int kCOMaxSlice = 64;                  // poses per block (per-pose sums live in LDS)
 static_assert(kCOChunk / kWave == kCOWaves * kCOPPT, "spread assignment covers the chunk");
 
@@ -229,7 +212,6 @@ __device__ __forceinline__ int64_t co_footprint(const T (&c)[NI], const T (&h)[N
     return cells;
 }
 
-#ifndef DPR_CO_NO_FOOT_TABLE
 // Footprints of the block's poses, computed ONCE per pose by one thread each and parked in LDS
 // (every thread recomputing them cost ~50 VALU per pose: a tenth of the pose loop's instructions).
 // Ends with a barrier.  foot[j] = {lo0, lo1, hi0, hi1} of pose b_lo + j.
@@ -268,7 +250,6 @@ __device__ __forceinline__ int64_t co_read_footprint(const int (*foot)[4], int j
     const int W = hi[0] - lo[0] + 1, H = hi[1] - lo[1] + 1;
     return (W > 0 && H > 0) ? (int64_t)W * H : 0;
 }
-#endif
 
 // What a DPR_FLAG_KEEP_BINNING forward leaves at the start of the workspace: the identity of the
 // cloud whose sorted copy (+ permutation) follows.  A DPR_FLAG_REUSE_BINNING pullback skips its
@@ -294,12 +275,6 @@ __device__ __forceinline__ bool sort_header_ok(const SortHeader* hdr, const Sort
            hdr->pw == want.pw;
 }
 
-// DPR_FIXED_POINT=0 (experiment knob, read once): f64 LDS accumulators for fp32 data too
-static int co_fixed_point() {
-    static const int v = env_knob("DPR_FIXED_POINT", 1, 0, 1);
-    return v;
-}
-
 // ------------------------------------------------------------------ forward
 // Two kernels.  k_co_splat covers every (chunk, pose) whose footprint fits the LDS tile in one
 // pass -- nearly all of them on a sorted cloud -- with a short inner loop (at most 64 VGPRs for
@@ -307,7 +282,7 @@ static int co_fixed_point() {
 // grids much larger than the cloud's resolution) is only FLAGGED per block, and k_co_splat_wide,
 // launched after it over the same grid, handles those poses of the flagged blocks in row bands.
 template <typename T> struct COSplatOcc {
-    static constexpr int value = sizeof(T) == 4 ? DPR_CO_SPLAT_OCC : 4;
+    static constexpr int value = sizeof(T) == 4 ? kCOSplatOcc : 4;
 };
 
 template <typename T, int NI, bool HAS_PW>
@@ -333,22 +308,16 @@ __global__ __launch_bounds__(kCOThreads, COSplatOcc<T>::value) void k_co_splat(
     // pixels, and float atomics of many workgroups into the same rows at the same time run an
     // order of magnitude slower than spread ones.
     const int rot0 = nbs > 0 ? (int)(blockIdx.x % (unsigned)nbs) : 0;
-#ifndef DPR_CO_NO_FOOT_TABLE
     __shared__ int foot[kCOMaxSlice][4];
     __shared__ int fexp[kCOMaxSlice];
     co_fill_footprints<T, NI>(foot, c, h, gd, rot, trans, b_lo, nbs, fexp, ow, maxpw, fixed);
-#endif
     unsigned long long wide_mask = 0;  // poses of this slice whose footprint outgrows the tile
     static_assert(kCOMaxSlice <= 64, "one bit per pose of a slice");
     for (int jb = 0; jb < nbs; ++jb) {
         const int64_t b = b_lo + (jb + rot0) % nbs;
         const Pose<T, NI, 2> ps = load_pose<T, NI, 2>(rot, trans, ow, b);
         int lo[2], hi[2];
-#ifndef DPR_CO_NO_FOOT_TABLE
         const int64_t cells = co_read_footprint(foot, (int)(b - b_lo), lo, hi);
-#else
-        const int64_t cells = co_footprint<T, NI>(c, h, ps, gd, lo, hi);
-#endif
         if (cells == 0) continue;  // uniform
         if (cells > kCOCap) {  // uniform: left to k_co_splat_wide
             wide_mask |= 1ull << (unsigned)(b - b_lo);
@@ -362,13 +331,7 @@ __global__ __launch_bounds__(kCOThreads, COSplatOcc<T>::value) void k_co_splat(
         // fp32 data: exact 64-bit fixed-point sums in the LDS tile (FixScale, dpr_device.h): the
         // kernel was bound by ds_add_f64 (2.56 G atomics / 1544 G/s = 1.66 of its 2.11 ms at C4's
         // share); ds_add_u64 retires twice as fast
-#ifndef DPR_CO_NO_FOOT_TABLE
         const int fe = fexp[(int)(b - b_lo)];
-#else
-        const int fe0 = fix_exponent(sizeof(T) == 4 ? fabsf((float)ps.ow) * maxpw : __builtin_inff(),
-                                     (uint32_t)kCOChunk, fixed);
-        const int fe = fe0 == kFixNone ? kFixOff : fe0;
-#endif
         const FixScale fs = fix_scale_from_exponent(fe == kFixOff ? kFixNone : fe);
         auto pose_points = [&](auto fix_tag) {
             constexpr bool FIX = decltype(fix_tag)::value;
@@ -568,11 +531,7 @@ __global__ __launch_bounds__(kCOThreads) void k_co_gather(
     // into registers before pose b is gathered and written to the other tile after it, so its
     // latency hides behind the arithmetic and one barrier per pose is enough (the kernel runs one
     // workgroup per CU by its 1024 threads x ~100 VGPRs anyway, so the LDS is there).
-#ifndef DPR_CO_NO_FOOT_TABLE
     constexpr bool PIPE = sizeof(T) == 4;
-#else
-    constexpr bool PIPE = false;
-#endif
     constexpr int CAP = PIPE ? kCOGatherCap : kCOCap;
     constexpr int NBUF = PIPE ? 2 : 1;
     constexpr int kRed = NVAL * kCOThreads;
@@ -597,10 +556,8 @@ __global__ __launch_bounds__(kCOThreads) void k_co_gather(
     }
     const int64_t b_lo = (int64_t)blockIdx.y * poses_per_slice;
     const int64_t b_hi = (b_lo + poses_per_slice < B) ? b_lo + poses_per_slice : B;
-#ifndef DPR_CO_NO_FOOT_TABLE
     __shared__ int foot[kCOMaxSlice][4];
     co_fill_footprints<T, NI>(foot, c, h, gd, rot, trans, b_lo, any ? (int)(b_hi - b_lo) : 0);
-#endif
     // stage the footprint of ds_dout (residual mode: scale * (out - target)); no barrier
     auto stage = [&](T* tile, const int (&lo)[2], int W, int H, int64_t b) {
         const T* gb = g + b * gd.G;
@@ -704,7 +661,6 @@ __global__ __launch_bounds__(kCOThreads) void k_co_gather(
     // parks its NVAL sums in LDS; after a barrier wave q adds up value q.
     auto reduce_parked = [&](const T* red, int j) {
         if (wave < NVAL) {
-#ifndef DPR_CO_RED_F64
             if constexpr (sizeof(T) == 4) {
                 // fp32 data: the block's 4096 terms are summed in f32 as a tree (4 per thread, 16 per
                 // reducer lane, 64 lanes: what the reference's pairwise `sum` does in the same
@@ -718,7 +674,6 @@ __global__ __launch_bounds__(kCOThreads) void k_co_gather(
                 if (lane == kWave - 1) pacc[j][wave] = (double)sum;
                 return;
             }
-#endif
             double sum = 0.0;
 #pragma unroll
             for (int i = 0; i < kCOThreads / kWave; ++i) sum += (double)red[wave * kCOThreads + i * kWave + lane];
@@ -727,7 +682,6 @@ __global__ __launch_bounds__(kCOThreads) void k_co_gather(
         }
     };
     if constexpr (PIPE) {
-#ifndef DPR_CO_NO_FOOT_TABLE
         // Prefetch: thread t requests cells t, t + 1024, ... of the next footprint (row-major, width
         // Wn) -- all of a tile's loads are in flight at once, every lane takes part, the LDS writes are
         // linear.  (Measured against a wave-per-row mapping, which needs no division per cell: 3.09
@@ -801,16 +755,11 @@ __global__ __launch_bounds__(kCOThreads) void k_co_gather(
             cells = cells_n;
             staged = pref_n;
         }
-#endif
     } else {
         for (int64_t b = b_lo; any && b < b_hi; ++b) {
             const Pose<T, NI, 2> ps = load_pose<T, NI, 2>(rot, trans, ow, b);
             int lo[2], hi[2];
-#ifndef DPR_CO_NO_FOOT_TABLE
             const int64_t cells = co_read_footprint(foot, (int)(b - b_lo), lo, hi);
-#else
-            const int64_t cells = co_footprint<T, NI>(c, h, ps, gd, lo, hi);
-#endif
             if (cells == 0) continue;  // uniform: no neighbour of the chunk is in the grid (sums stay 0)
             // A footprint that does not fit the LDS tile (sparse tails of the cloud, incoherent
             // input) is gathered from global memory directly (L2-resident image; unlike the
@@ -1010,9 +959,7 @@ static COPlan co_plan(size_t elem, int op, unsigned flags, int n_in, int64_t P, 
 template <typename T>
 static int co_sort(hipStream_t st, int n_in, int64_t P, int64_t B, const T* points, const T* pw, T* spts, T* spw,
                    uint32_t* perm, char* scratch) {
-    static const int mode = env_knob("DPR_CO_SORT", 0, 0, 2);  // 1: cells, 2: radix (A/B runs)
-    const bool radix = mode == 2 || (mode == 0 && B > 96);
-    if (!radix) return coarse_sort_with_perm<T>(st, n_in, P, points, pw, spts, spw, perm, scratch);
+    if (B <= 96) return coarse_sort_with_perm<T>(st, n_in, P, points, pw, spts, spw, perm, scratch);
     return sort_points_impl<T>((void*)st, n_in, P, points, spts, perm, pw, spw, scratch, sort_workspace_bytes(P),
                                nullptr, false);
 }
@@ -1089,17 +1036,17 @@ int raster_chunkown(hipStream_t st, unsigned flags, const int64_t* grid, int64_t
         if (pws) {
             hipLaunchKernelGGL((k_co_splat<T, NI, true>), gg, dim3(kCOThreads), 0, st, gd, P, B,
                                pl.poses_per_slice, pts, pws, rot, trans, ow, out, wide_count,
-                               wide_items, co_fixed_point());
+                               wide_items, 1);
             hipLaunchKernelGGL((k_co_splat_wide<T, NI, true>), dim3(kCOWideBlocks),
                                dim3(kCOThreads), 0, st, gd, P, pts, pws, rot, trans, ow, out,
-                               wide_count, wide_items, co_fixed_point());
+                               wide_count, wide_items, 1);
         } else {
             hipLaunchKernelGGL((k_co_splat<T, NI, false>), gg, dim3(kCOThreads), 0, st, gd, P, B,
                                pl.poses_per_slice, pts, pws, rot, trans, ow, out, wide_count,
-                               wide_items, co_fixed_point());
+                               wide_items, 1);
             hipLaunchKernelGGL((k_co_splat_wide<T, NI, false>), dim3(kCOWideBlocks),
                                dim3(kCOThreads), 0, st, gd, P, pts, pws, rot, trans, ow, out,
-                               wide_count, wide_items, co_fixed_point());
+                               wide_count, wide_items, 1);
         }
     }
     stage_mark(st);

@@ -64,20 +64,11 @@ constexpr int kSC = 16;              // points per sub-chunk (level-0 box, one l
 constexpr int kFan = 64;             // sub-chunks per chunk (level-1 box, one wave's box tests)
 constexpr int kL1 = kSC * kFan;      // 1024 points
 constexpr int kL2 = 64;              // chunks per level-2 box (65536 points)
-// (experiment builds override the tile kernels' block and tile: -DDPR_OWN_THREADS=512 -DDPR_OWN_TY=16 -DDPR_OWN_TZ=13
-// is the half tile that fits two workgroups per CU, profiles/r06_experiments.md)
-#ifndef DPR_OWN_THREADS
-#define DPR_OWN_THREADS 1024
-#endif
-#ifndef DPR_OWN_TY
-#define DPR_OWN_TY 32
-#endif
-#ifndef DPR_OWN_TZ
-#define DPR_OWN_TZ 14
-#endif
-constexpr int kOT = DPR_OWN_THREADS; // threads of the tile kernels
+// (half tile, 512 threads / 32 x 16 x 13, fits two workgroups per CU and is slower:
+// profiles/r06_experiments.md)
+constexpr int kOT = 1024;            // threads of the tile kernels
 constexpr int kOW = kOT / kWave;     // 16 waves
-constexpr int kTX = 32, kTY = DPR_OWN_TY, kTZ = DPR_OWN_TZ;
+constexpr int kTX = 32, kTY = 32, kTZ = 14;
 constexpr int kCells = kTX * kTY * kTZ;                     // 14336 owned cells
 // forward: the LDS tile is PADDED by one cell on every side (34 x 34 x 16 cells of 8 bytes = 148 KB):
 // all eight neighbours of every point the tile looks at have a cell, no ownership tests; the pad
@@ -634,7 +625,7 @@ struct OwnTileArgs {
     int max_items;
     int64_t nL1, nSC;
     const IBox* b0;    // [pose copy][nSC]
-    size_t dbg_words;  // (stats build: 32-bit words of the slab area, per-item records at its end)
+    size_t dbg_words;  // (unused; was read by the counter build, keeps the kernels' argument layout)
 };
 
 // work item of this block: buckets from the heaviest down
@@ -708,9 +699,6 @@ __device__ __forceinline__ void own_walk(const OwnTileArgs& ta, const OwnItem& i
     bool have_c = acquire();
     int stage = 0;  // 0: candidates, 2: pooled batches
     uint32_t pool_pos = 0, pool_total = 0;
-#ifdef DPR_OWN_STATS
-    uint32_t st_batches = 0, st_take = 0, st_tests = 0;
-#endif
     for (;;) {
         if (qn >= (uint32_t)kBatchSC || (stage == 2 && qn > 0)) {
             const uint32_t take = qn >= (uint32_t)kBatchSC ? kBatchSC : qn;
@@ -718,10 +706,6 @@ __device__ __forceinline__ void own_walk(const OwnTileArgs& ta, const OwnItem& i
             const uint32_t e = (uint32_t)lane / kLanesPerSC;
             const bool have = e < take;
             const uint32_t sc = queue[base + (have ? e : 0u)];  // (idle lanes: a valid sub-chunk, not worked on)
-#ifdef DPR_OWN_STATS
-            ++st_batches;
-            st_take += take * kLanesPerSC;
-#endif
             visit(sc, lane % kLanesPerSC, have);
             qn = base;
             continue;
@@ -732,9 +716,6 @@ __device__ __forceinline__ void own_walk(const OwnTileArgs& ta, const OwnItem& i
                 const unsigned long long mask = __ballot(hit);
                 if (hit) queue[qn + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)sc_mine;
                 qn += (uint32_t)__popcll(mask);
-#ifdef DPR_OWN_STATS
-                ++st_tests;
-#endif
                 have_c = acquire();
                 continue;
             }
@@ -744,13 +725,7 @@ __device__ __forceinline__ void own_walk(const OwnTileArgs& ta, const OwnItem& i
             pos = __builtin_amdgcn_readfirstlane(pos);
             if ((uint32_t)lane < qn) wl->pool[pos + lane] = queue[lane];
             qn = 0;
-#ifdef DPR_OWN_STATS
-            if (threadIdx.x == 0) wl->pad[5] = (uint32_t)wall_clock64();
-#endif
             __syncthreads();
-#ifdef DPR_OWN_STATS
-            if (threadIdx.x == 0) wl->pad[6] = (uint32_t)wall_clock64();
-#endif
             pool_total = wl->pool_n;
             pool_pos = (uint32_t)wave * kBatchSC;
             stage = 2;
@@ -761,13 +736,6 @@ __device__ __forceinline__ void own_walk(const OwnTileArgs& ta, const OwnItem& i
         qn = n;
         pool_pos += kOW * kBatchSC;
     }
-#ifdef DPR_OWN_STATS
-    if (lane == 0) {
-        atomicAdd(&wl->pad[2], st_batches);
-        atomicAdd(&wl->pad[3], st_take);
-        atomicAdd(&wl->pad[4], st_tests);
-    }
-#endif
 }
 
 // the four points of a lane's quarter of a sub-chunk: body(point index in the sub-chunk, live, pt[3], w)
@@ -819,12 +787,6 @@ __global__ __launch_bounds__(kOT) void k_own_splat(OGeom tg, GridDesc<3> gd, int
     OwnItem rec;
     if (!own_item(ta, bl, blockIdx.x, rec)) return;
     const uint32_t tile = rec.tile, part = rec.part_nparts & 0xffffu, nparts = rec.part_nparts >> 16;
-#ifdef DPR_OWN_STATS
-    const uint64_t st_t0 = wall_clock64();
-#define DPR_STAMP(k) do { if (threadIdx.x == 0) wl->pad[8 + (k)] = (uint32_t)(wall_clock64() - st_t0); } while (0)
-#else
-#define DPR_STAMP(k) do { } while (0)
-#endif
     int tc[3], x0[3];
     tile_coords((int)tile, tg, tc, x0);
     const double bgv = bg ? (double)bg[b] : 0.0;
@@ -849,15 +811,7 @@ __global__ __launch_bounds__(kOT) void k_own_splat(OGeom tg, GridDesc<3> gd, int
     const Pose<T, 3, 3> ps = load_pose<T, 3, 3>(rot, trans, ow, b);
     const FixScale fs = fix_scale_from_exponent(rec.sexp);
     const OwnXform<T> xf = own_xform<T>(ps, gd);
-    DPR_STAMP(0);
     __syncthreads();
-    DPR_STAMP(1);
-#ifdef DPR_OWN_STATS
-    uint32_t st_vis = 0, st_touch = 0;
-#endif
-#ifdef DPR_OWN_EXP
-    double exp_sink = 0.0;
-#endif
     auto run = [&](auto fix_tag) {
         constexpr bool FIX = decltype(fix_tag)::value;
         auto visit = [&](uint32_t sc, int quarter, bool have) {
@@ -868,28 +822,15 @@ __global__ __launch_bounds__(kOT) void k_own_splat(OGeom tg, GridDesc<3> gd, int
                 // padded tile coordinates of the lower neighbour: 0 .. T
                 const uint32_t l0 = l[0], l1 = l[1], l2 = l[2];
                 const bool touches = ok && l0 <= (uint32_t)kTX && l1 <= (uint32_t)kTY && l2 <= (uint32_t)kTZ;
-#if defined(DPR_OWN_STATS) && DPR_OWN_STATS >= 2  /* (per-point counters slow the kernel down 2x) */
-                st_vis += live ? 1u : 0u;
-                st_touch += touches ? 1u : 0u;
-#endif
-#if defined(DPR_OWN_EXP) && DPR_OWN_EXP == 2  /* transform + test only */
-                exp_sink += touches ? (double)dlo[0] : 0.0;
-                if (false) {
-#else
                 if (touches) {
-#endif
                     const T w = HAS_PW ? ps.ow * pwi : ps.ow;  // src/raster.jl:52
                     double* cell = acc + (l0 + kPX * l1 + kPX * kPY * l2);
                     // all eight neighbours have a cell (pad cells, and owned cells beyond the grid
                     // edge, are never flushed: the individual drop of src/raster.jl:62)
 #pragma unroll
                     for (int s = 0; s < 8; ++s) {
-#if defined(DPR_OWN_EXP) && DPR_OWN_EXP == 1  /* no LDS atomics: where does the time go? */
-                        exp_sink += (double)voxel_weight<T, 3>(dlo, s, w) * fs.mul + (double)(size_t)cell;
-#else
                         cell_add<FIX, T>(cell + ((s & 1) + kPX * ((s >> 1) & 1) + kPX * kPY * (s >> 2)),
                                          voxel_weight<T, 3>(dlo, s, w), fs);
-#endif
                     }
                 }
             });
@@ -898,48 +839,6 @@ __global__ __launch_bounds__(kOT) void k_own_splat(OGeom tg, GridDesc<3> gd, int
     };
     if (fs.mul != 0.0) run(std::true_type{});  // (uniform)
     else run(std::false_type{});
-#ifdef DPR_OWN_STATS
-    {
-        const uint32_t a = (uint32_t)wave_sum<int>((int)st_vis), c = (uint32_t)wave_sum<int>((int)st_touch);
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&wl->pad[0], a);
-            atomicAdd(&wl->pad[1], c);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t* ctl = (uint32_t*)(ta.ws + ta.off_ctl);
-            atomicAdd(&ctl[4], wl->pad[0]);
-            atomicAdd(&ctl[5], wl->pad[1]);
-            atomicAdd(&ctl[6], wl->pad[2]);
-            atomicAdd(&ctl[7], wl->pad[3]);
-            atomicAdd(&ctl[9], wl->pad[4]);
-            atomicAdd(&ctl[8], 1u);
-            const uint32_t dt = (uint32_t)(wall_clock64() - st_t0);
-            atomicAdd(&ctl[10], dt);
-            atomicMax(&ctl[11], dt);
-            // per-item record at the end of the slab area: {ticks, visits, tile, part | nparts << 16, start tick}
-            uint32_t* dbg = (uint32_t*)(slabs) + (size_t)ta.dbg_words - 8 * ((size_t)blockIdx.x + 1);
-            dbg[0] = dt;
-            dbg[1] = wl->pad[0];
-            dbg[2] = tile;
-            dbg[3] = part | (nparts << 16);
-            dbg[4] = (uint32_t)st_t0;
-            dbg[5] = rec.count;
-            // phases (ticks of 10 ns): setup | zero+barrier | wave 0 to the pool barrier | its wait there | pooled batches + final barrier
-            const uint32_t t_end_walk = (uint32_t)(wall_clock64() - st_t0);
-            atomicAdd(&ctl[12], wl->pad[8]);
-            atomicAdd(&ctl[13], wl->pad[9] - wl->pad[8]);
-            atomicAdd(&ctl[14], (wl->pad[5] - (uint32_t)st_t0) - wl->pad[9]);
-            atomicAdd(&ctl[15], wl->pad[6] - wl->pad[5]);
-            atomicAdd(&ctl[1 + 2], 0u);
-            dbg[6] = t_end_walk - (wl->pad[6] - (uint32_t)st_t0);
-            dbg[7] = wl->pad[8];
-        }
-    }
-#endif
-#ifdef DPR_OWN_EXP
-    if (exp_sink == 1.2345) acc[threadIdx.x] = exp_sink;
-#endif
     __syncthreads();
     // flush the owned cells: thread -> 4 cells along x
     const bool to_slab = nparts > 1;
@@ -1482,22 +1381,6 @@ struct OwnPlan {
     size_t rec_stride, list_stride, items_stride, split_stride;
 };
 
-struct OwnKnobs {
-    int cap_div, cap_min, max_slabs, fixed;
-};
-static const OwnKnobs& oknobs() {
-    static const OwnKnobs k = [] {
-        auto env_int = [](const char* name, int dflt, int lo, int hi) { return env_knob(name, dflt, lo, hi); };
-        OwnKnobs q;
-        q.cap_div = env_int("DPR_OWN_CAP_DIV", 512, 1, 1 << 20);     // a part: ~1.6 P / 512 visits
-        q.cap_min = env_int("DPR_OWN_CAP_MIN", 8192, 64, 1 << 24);
-        q.max_slabs = env_int("DPR_OWN_MAX_SLABS", 0, 0, 1 << 16);   // 0: 1024 for one or two poses, 2048 for batches
-        q.fixed = env_int("DPR_FIXED_POINT", 1, 0, 1);
-        return q;
-    }();
-    return k;
-}
-
 static OwnPlan make_oplan(int op, const OGeom& tg, int64_t P, int64_t B) {
     OwnPlan pl;
     pl.nSC = (P + kSC - 1) / kSC;
@@ -1507,9 +1390,9 @@ static OwnPlan make_oplan(int op, const OGeom& tg, int64_t P, int64_t B) {
     // a part holds ~1/512 of the visits of the whole pose group: the number of parts -- and of the slabs they
     // leave their tiles in -- stays bounded whatever the batch (with a per-pose cap a clustered cloud ran out of
     // slabs at 4 poses, its heaviest tiles stayed whole: 10.5 ms instead of 1.5)
-    const int64_t cap = (P + P / 2) * pl.Bw / oknobs().cap_div;
-    pl.cap = (uint32_t)(cap < oknobs().cap_min ? oknobs().cap_min : (cap > 0x3fffffff ? 0x3fffffff : cap));
-    pl.max_slabs = oknobs().max_slabs ? oknobs().max_slabs : (pl.Bw <= 2 ? 1024 : 2048);
+    const int64_t cap = (P + P / 2) * pl.Bw / 512;
+    pl.cap = (uint32_t)(cap < 8192 ? 8192 : (cap > 0x3fffffff ? 0x3fffffff : cap));
+    pl.max_slabs = pl.Bw <= 2 ? 1024 : 2048;
     pl.max_split = pl.max_slabs / 2 + 1;
     pl.max_items = tg.NT + pl.max_slabs;
     // candidate chunks per tile: 64 times the average of a cloud that fills the grid, 256 .. 8192;
@@ -1597,7 +1480,7 @@ static OwnPlanArgs plan_args(const OwnPlan& pl, char* ws) {
     pa.max_slabs = pl.max_slabs;
     pa.max_split = pl.max_split;
     pa.cap = pl.cap;
-    pa.fixed = oknobs().fixed;
+    pa.fixed = 1;
     pa.b1 = (const IBox*)(ws + pl.off_b1);
     pa.b2 = (const IBox*)(ws + pl.off_b2);
     pa.mw1 = nullptr;
@@ -1730,12 +1613,6 @@ static int own_pullback_blocks(int64_t P, int64_t G) {
     return (int)(nb < 1 ? 1 : nb);
 }
 
-// (experiments: DPR_OWN_BATCH_F64=0 -- a launch per pose for fp64 batches, round 5's choice)
-static bool own_batch_f64() {
-    static const bool v = env_knob("DPR_OWN_BATCH_F64", 1, 0, 1) != 0;
-    return v;
-}
-
 template <typename T>
 int pullback_owner(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G, int64_t P, int64_t B,
                    const T* g, const T* points, const T* rot, const T* trans, const T* ow, const T* pw,
@@ -1754,7 +1631,7 @@ int pullback_owner(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
     // (the partial sums sit at the start of the workspace: a forward's boxes and plan, further up in
     // a KEEP / REUSE pair's shared buffer, are not this call's business -- it overwrites the header)
     double* partials = (double*)ws_;
-    if (B > 1 && (sizeof(T) == 4 || own_batch_f64())) {
+    if (B > 1) {
         // pose loop inside the kernel, kDBatch poses per launch (further launches add to the point
         // gradients): fp32 1e7 points x 16 poses -> 256^3 2.87 -> 2.36 ms, x 4 poses 0.68 -> 0.56.  fp64 (round 6):
         // one point per thread, the per-pose sums parked in LDS and reduced per block -- with 13 wave reductions
@@ -1780,20 +1657,15 @@ int pullback_owner(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
         DPR_HIP(hipGetLastError());
         return DPR_OK;
     }
-    for (int64_t b = 0; b < B; ++b) {
-        // the point gradients accumulate over poses: one pose per launch (stream order = race-free
-        // read-modify-write)
-#define DPR_OWN_PB(HAS_PW, FIRST)                                                                            \
-    hipLaunchKernelGGL((k_own_pullback<T, HAS_PW, FIRST>), dim3((unsigned)nblocks), dim3(kDT), 0, st, gd, P, \
-                       per_block, cells_per_block, points, pw, g, rot, trans, ow, b, d_pts, d_pw, partials)
-        if (pw) {
-            if (b == 0) DPR_OWN_PB(true, true);
-            else DPR_OWN_PB(true, false);
-        } else {
-            if (b == 0) DPR_OWN_PB(false, true);
-            else DPR_OWN_PB(false, false);
-        }
-#undef DPR_OWN_PB
+    if (B == 1) {
+        // one pose: a launch that overwrites the point gradients, and its reduction
+        const int64_t b = 0;
+        if (pw)
+            hipLaunchKernelGGL((k_own_pullback<T, true, true>), dim3((unsigned)nblocks), dim3(kDT), 0, st, gd, P,
+                               per_block, cells_per_block, points, pw, g, rot, trans, ow, b, d_pts, d_pw, partials);
+        else
+            hipLaunchKernelGGL((k_own_pullback<T, false, true>), dim3((unsigned)nblocks), dim3(kDT), 0, st, gd, P,
+                               per_block, cells_per_block, points, pw, g, rot, trans, ow, b, d_pts, d_pw, partials);
         stage_mark(st);
         hipLaunchKernelGGL((k_own_reduce<T>), dim3(kNVal), dim3(1024), 0, st, (const double*)partials, nblocks, b,
                            d_rot, d_trans, d_bg, d_ow);

@@ -27,17 +27,8 @@
 // wave-instruction (profiles/r01_microbench_lds_atomics.txt).  It also makes fp32 results
 // practically independent of the accumulation order.
 //
-// Experiment knobs (environment variables in -DDPR_EXPERIMENTS builds only -- `make EXPERIMENTS=1`; the
-// compiled-in defaults are the measured best and all the shipped library knows):
-//   DPR_SCATTER_WC=0     plain scatter instead of the write-combining one
-//   DPR_SPLAT_BLOCKED=0|1  lane-adjacent (strided) / blocked record assignment in k_tile_splat
-//                        (default: chosen on the device from the order of the cloud)
-//   DPR_BWD_UNPERMUTE=0  owner threads store ds_dpoints directly instead of un-permuting
-//   DPR_POSE_GROUP=n     at most n poses per group (1 = per-pose pipeline)
-//   DPR_FIXED_POINT=0    f64 LDS accumulators instead of 64-bit fixed point in the fp32 forward
-//   DPR_FUSE_TILESCAN=0  k_tilescan / k_runscan as launches of their own
-//   DPR_BIN_DIRECT_STORE=0  fp64 batches stage their records in LDS like everything else
-// Always read (test hook, documented in include/dpr.h; it moves slab boundaries, never results):
+// The one environment variable read (test hook, documented in include/dpr.h; it moves slab
+// boundaries, never results):
 //   DPR_MAX_TILES=n      tiles per launch sequence (default 32768): lets a test walk slabs on small grids
 #include <hip/hip_runtime.h>
 
@@ -57,67 +48,32 @@ namespace dpr {
 // ------------------------------------------------------------------ tile geometry
 template <int NO> struct TileDims;
 // 3-D tile shape and K4 block size (A/B measured on C3, profiles/r01_tile_shape_sweep.txt)
-#ifndef DPR_TX3
-#define DPR_TX3 64
-#endif
-#ifndef DPR_TY3
-#define DPR_TY3 16
-#endif
-#ifndef DPR_TZ3
-#define DPR_TZ3 8
-#endif
 template <> struct TileDims<3> {
-    static constexpr int T[3] = {DPR_TX3, DPR_TY3, DPR_TZ3};
+    static constexpr int T[3] = {64, 16, 8};
 };
 template <> struct TileDims<2> {
     static constexpr int T[3] = {32, 32, 1};
 };
 constexpr int kMaxTiles = 32768;     // LDS cursor table: 4 B per tile, <= 128 KiB
 constexpr int kBinThreads = 1024;    // K1 / K3 block
-#ifndef DPR_WC_THREADS
-#define DPR_WC_THREADS 1024
-#endif
-#ifndef DPR_WC_PPT
-#define DPR_WC_PPT 4
-#endif
-constexpr int kWcThreads = DPR_WC_THREADS;  // block of the write-combining scatter
-#ifndef DPR_WC_SLICES
-#define DPR_WC_SLICES 1  // 0: the slice rule of the plain scatter for the write-combining one too
-#endif
-#ifndef DPR_SPLAT_THREADS
-#define DPR_SPLAT_THREADS 512
-#endif
-#ifndef DPR_GATHER_THREADS
-#define DPR_GATHER_THREADS 256
-#endif
-constexpr int kSplatThreads = DPR_SPLAT_THREADS;    // forward tile kernel block
-#ifndef DPR_SPLAT_RUNS_OCC
-#define DPR_SPLAT_RUNS_OCC (DPR_SPLAT_THREADS >= 1024 ? 8 : 4)  // waves per SIMD for two blocks per CU
-#endif
-#ifndef DPR_GATHER_THREADS_F64
-#define DPR_GATHER_THREADS_F64 512
-#endif
+constexpr int kWcThreads = 1024;     // block of the write-combining scatter
+constexpr int kWcPpt = 4;            // points per thread of a write-combining sub-chunk (fp32)
+constexpr int kSplatThreads = 512;   // forward tile kernel block
+constexpr int kSplatRunsOcc = 4;     // waves per SIMD of k_tile_splat_runs: two blocks per CU
 // fp64: the ds_dout tile is 80 KB, two workgroups per CU -- 512 threads each keep 16 waves on the CU
 // as the fp32 kernel's four workgroups of 256 do (with 256: 2.3 waves per SIMD, half the wave time
 // spent waiting; profiles/r04_c5_sq_counters.txt)
 template <typename T> __host__ __device__ constexpr int gather_threads() {
-    return sizeof(T) == 8 ? DPR_GATHER_THREADS_F64 : DPR_GATHER_THREADS;
+    return sizeof(T) == 8 ? 512 : 256;
 }
 // waves per SIMD the pullback tile kernels are compiled for (fp64: 128 VGPRs, so that two
 // workgroups of 512 fit a CU; fp32: four workgroups of 256 need no more than that either)
 template <typename T> __host__ __device__ constexpr int gather_waves_per_simd() { return 4; }
-#ifndef DPR_UPB
-#define DPR_UPB 4  // points per thread of the single-pose un-permute (a block = one scatter sub-chunk)
-#endif
-#ifndef DPR_GATHER_RB
-#define DPR_GATHER_RB 8  // rows of the ds_dout tile a wave requests before it stores the first
-#endif
+constexpr int kUpb = 4;        // points per thread of the single-pose un-permute (a block = one scatter sub-chunk)
+constexpr int kGatherRb = 8;   // rows of the ds_dout tile a wave requests before it stores the first
 // (the pullback tile kernels run 4 workgroups = 16 waves per CU: their 40 KB ds_dout tile sets
 // that, not the ~100 VGPRs)
-#ifndef DPR_BIN_BLOCKS
-#define DPR_BIN_BLOCKS 512
-#endif
-constexpr int kMaxBinBlocks = DPR_BIN_BLOCKS;  // rows of the counts table (2 per CU)
+constexpr int kMaxBinBlocks = 512;   // rows of the counts table (2 per CU)
 constexpr int kSplitChunks = 8;      // k_halo_gather work items per split tile (3-D: kSplitRows tile rows each;
                                      // 2-D: 256 voxels a step of the flat loop)
 constexpr int kSplitRows = 16;       // rows (l1, l2) of a 64 x 16 x 8 tile per work item
@@ -383,10 +339,7 @@ __global__ __launch_bounds__(kBinThreads) void k_count(GridDesc<NO> gd, TileGeom
         const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, nullptr, b0);
         // kCU points per thread are requested before the first one is used: with one load in
         // flight per thread (768 B per wave) the 32 waves of a CU cover ~3 TB/s of the chip
-#ifndef DPR_COUNT_UNROLL
-#define DPR_COUNT_UNROLL 4
-#endif
-        constexpr int kCU = DPR_COUNT_UNROLL;
+        constexpr int kCU = 4;
         for (int64_t base = lo + threadIdx.x; base < hi; base += (int64_t)kCU * kBinThreads) {
             T pt[kCU][NI];
             bool live[kCU];
@@ -804,10 +757,7 @@ __device__ __forceinline__ void tilescan_body(const uint32_t* __restrict__ total
 // (Round 3 tried ONE kernel whose last block -- arrival ticket, agent-scope fences -- runs the
 // tile scan: the scan stage went from 18.5 to 40 us at C3, 81 us with 16-tile blocks; the
 // device-wide release / acquire of 64-128 blocks costs more than a launch.  Two kernels stay.)
-#ifndef DPR_SCAN_TILES
-#define DPR_SCAN_TILES 32
-#endif
-constexpr int kScanTiles = DPR_SCAN_TILES, kScanGroups = 1024 / DPR_SCAN_TILES;
+constexpr int kScanTiles = 32, kScanGroups = 1024 / kScanTiles;
 __global__ __launch_bounds__(1024) void k_colscan(uint32_t* __restrict__ counts, int nblk, int NT,
                                                   uint32_t* __restrict__ totals,
                                                   uint32_t* __restrict__ zero_word = nullptr) {
@@ -1037,13 +987,7 @@ __global__ __launch_bounds__(kWcThreads) void k_scatter_wc(
     // its LDS phases.  Pose groups load at the top of the round instead: the second register set
     // pushed that kernel over 128 VGPRs (it spilled the prefetched points straight to scratch,
     // i.e. waited for them at once), and a group pays the latency once per nb poses anyway.
-#ifndef DPR_GROUP_PREFETCH
-#define DPR_GROUP_PREFETCH 0
-#endif
-#ifndef DPR_WC_PREFETCH
-#define DPR_WC_PREFETCH 1
-#endif
-    constexpr bool kPrefetch = DPR_WC_PREFETCH && (!GROUP || DPR_GROUP_PREFETCH);
+    constexpr bool kPrefetch = !GROUP;
     // Everything per point is addressed as (sub-chunk base: uniform, 64-bit, in scalar registers) +
     // (index inside the sub-chunk: 32-bit): with 64-bit per-point indices the pose-group variants kept
     // a dozen hoisted addresses alive across the pose loop and spilled 10-24 VGPRs.
@@ -1692,27 +1636,6 @@ __device__ __forceinline__ void splat_record(const R& rc, bool active, const Pos
     bool interior = true;
 #pragma unroll
     for (int d = 0; d < NO; ++d) interior = interior && low_ok[d];
-#if defined(DPR_ABL) && DPR_ABL == 1  // ablation: all the arithmetic, no LDS atomics (timing only, wrong results)
-    if (active) {
-        unsigned long long sink = 0;
-#pragma unroll
-        for (int s = 0; s < (1 << NO); ++s) sink ^= fix_bits((float)voxel_weight<T, NO>(dlo, s, w), fs) + lds_index<NO>(lb);
-        if (sink == 0x123456789abcull) acc[threadIdx.x] = 1.0;
-    }
-    return;
-#elif defined(DPR_ABL) && DPR_ABL == 7  // ablation: records loaded and looked at, NO arithmetic, NO LDS atomics
-    if (active && __float_as_uint((float)pt[0]) == 0x12345678u) acc[threadIdx.x] = 1.0;
-    return;
-#elif defined(DPR_ABL) && DPR_ABL == 2  // ablation: the LDS atomics only, at pseudo-random cells
-    if (active) {
-        uint32_t h = __float_as_uint((float)pt[0]) * 2654435761u;
-        h ^= h >> 15;
-        double* base = &acc[h % (uint32_t)(tile_voxels_halo<NO>() - nbr_lds_offset<NO>((1 << NO) - 1) - 1)];
-#pragma unroll
-        for (int s = 0; s < (1 << NO); ++s) atomicAdd((unsigned long long*)(base + nbr_lds_offset<NO>(s)), 12345ull);
-    }
-    return;
-#endif
     if (active && interior) {
         // common case: one base address, the 2^N neighbours are compile-time offsets
         // (they fold into the ds_add offset field)
@@ -1755,10 +1678,7 @@ __device__ __forceinline__ void flush_tile(const double* __restrict__ acc, const
     constexpr int RPW = kWave / TX;        // rows per wave pass (1 for TX = 64, 2 for TX = 32)
     static_assert(kWave % TX == 0, "tile rows must divide the wavefront");
     constexpr int NW = kSplatThreads / kWave;
-#ifndef DPR_FLUSH_BATCH
-#define DPR_FLUSH_BATCH 4
-#endif
-    constexpr int kFB = DPR_FLUSH_BATCH;
+    constexpr int kFB = 4;
     const int lane = threadIdx.x & (kWave - 1);
     const int x = lane % TX;
     const bool x_ok = x0[0] + x < gd.n[0];
@@ -1851,10 +1771,7 @@ __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
     // kPF records per thread are kept in flight: with one load per iteration the heaviest
     // item's per-thread chain (records / threads iterations x memory latency) sets the
     // kernel time, whatever the LDS atomic rate.
-#ifndef DPR_PF
-#define DPR_PF 2
-#endif
-    constexpr int kPF = DPR_PF;
+    constexpr int kPF = 2;
     RecT<T, W3> nxt[kPF];
 #pragma unroll
     for (int u = 0; u < kPF; ++u) {
@@ -1883,12 +1800,8 @@ __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
                 splat_record<FIX, T, NI, NO, HAS_PW>(cur[u], r_cur + u * step < r1, ps, gd, x0, acc, fs);
         }
     };
-#if defined(DPR_ABL) && DPR_ABL == 3  // ablation: no record loop (clear + flush + dispatch only)
-    (void)record_loop;
-#else
     if (fs.mul != 0.0) record_loop(std::true_type{});  // (uniform)
     else record_loop(std::false_type{});
-#endif
     lds_barrier();  // LDS phases only: prefetched records stay in flight
     if ((item.part_nparts >> 16) > 1) {
         // part of a split tile: the whole LDS tile goes to this part's overflow slab;
@@ -1918,7 +1831,7 @@ __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
 // ------------------------------------------------------------------ forward K4, local binning
 // (k_tile_splat with the record loop walking run descriptors; instantiated with RUNS = true)
 template <typename T, int NI, int NO, bool HAS_PW, bool W3, bool RUNS>
-__global__ __launch_bounds__(kSplatThreads, DPR_SPLAT_RUNS_OCC) void k_tile_splat_runs(  // (2 blocks / CU)
+__global__ __launch_bounds__(kSplatThreads, kSplatRunsOcc) void k_tile_splat_runs(  // (2 blocks / CU)
     GridDesc<NO> gd, TileGeom<NO> tg, const RecT<T, W3>* __restrict__ rec,
     const RunDesc* __restrict__ runs, uint32_t max_rec,
     const WorkItem* __restrict__ items, const uint32_t* __restrict__ n_items,
@@ -1945,10 +1858,7 @@ __global__ __launch_bounds__(kSplatThreads, DPR_SPLAT_RUNS_OCC) void k_tile_spla
     int x0[NO], tc[NO];
     tile_origin<NO>(tile, tg, x0, tc);
     if (b != b0) ps = load_pose<T, NI, NO>(rot, trans, ow, b);
-#ifndef DPR_PF
-#define DPR_PF 2
-#endif
-    constexpr int kPF = DPR_PF;
+    constexpr int kPF = 2;
     // fp32 data: exact 64-bit fixed-point sums (see FixScale).  Bound on the records of the item:
     // a run holds at most one sub-chunk (<= 4096 records).
     uint32_t n_bound = (item.end - item.begin) < (1u << 19) ? (item.end - item.begin) * 4096u : max_rec;
@@ -2555,7 +2465,7 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
         constexpr int TZ = (NO == 3) ? TileDims<NO>::T[NO - 1] : 0;
         constexpr int ROWS = NVH / (TX + 1);
         constexpr int RPW = kWave / TX;  // rows per wave pass (1 for TX = 64, 2 for TX = 32)
-        constexpr int kRB = DPR_GATHER_RB;  // row passes in flight
+        constexpr int kRB = kGatherRb;  // row passes in flight
         static_assert(kWave % TX == 0, "tile rows must divide the wavefront");
         const bool first_part = (item.part_nparts & 0xffffu) == 0;
         const int lane = threadIdx.x & (kWave - 1);
@@ -2599,12 +2509,8 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
             }
         }
         };
-#if defined(DPR_ABL) && DPR_ABL == 6  // ablation: the ds_dout tile is not staged (timing only, wrong results)
-        (void)stage_rows;
-#else
         if ((item.part_nparts >> 16) > 1) stage_rows(std::false_type{});
         else stage_rows(std::true_type{});
-#endif
         // the x == TX column (halo cells only): one cell per row
         for (int row = threadIdx.x; row < ROWS; row += GT) {
             const int l1 = row % (TY + 1), l2 = (NO == 3) ? row / (TY + 1) : 0;
@@ -2627,9 +2533,6 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
     pin_record(nxt);
     if (HAS_PW && !UNPERM) pin_value(nxt_idx);
     drain_vmem();
-#if defined(DPR_ABL) && DPR_ABL == 5  // ablation: no record loop (dispatch, ds_dout staging, reductions only)
-    r = r1;
-#endif
     while (r < r1) {
         const Rec4<T> rc = nxt;
         const uint32_t p = HAS_PW ? nxt_idx : slot_to_idx(rc.v[3]);
@@ -2664,19 +2567,12 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
         bool interior = true;
 #pragma unroll
         for (int d = 0; d < NO; ++d) interior = interior && low_ok[d];
-#if defined(DPR_ABL) && DPR_ABL == 4  // ablation: the record loop WITHOUT its 2^N LDS reads (timing only, wrong results)
-        if (interior) {
-#pragma unroll
-            for (int s = 0; s < (1 << NO); ++s) gv[s] = (T)(lds_index<NO>(lb) + s);
-        } else {
-#else
         if (interior) {
             // common case: one base address, neighbours at compile-time offsets
             const T* base = &tile_g[lds_index<NO>(lb)];
 #pragma unroll
             for (int s = 0; s < (1 << NO); ++s) gv[s] = base[nbr_lds_offset<NO>(s)];
         } else {
-#endif
 #pragma unroll
             for (int s = 0; s < (1 << NO); ++s) {
                 int l[NO];
@@ -2844,7 +2740,7 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
         constexpr int TZ = (NO == 3) ? TileDims<NO>::T[NO - 1] : 0;
         constexpr int ROWS = NVH / (TX + 1);
         constexpr int RPW = kWave / TX;  // rows per wave pass (1 for TX = 64, 2 for TX = 32)
-        constexpr int kRB = DPR_GATHER_RB;  // row passes in flight
+        constexpr int kRB = kGatherRb;  // row passes in flight
         static_assert(kWave % TX == 0, "tile rows must divide the wavefront");
         const bool first_part = (item.part_nparts & 0xffffu) == 0;
         const int lane = threadIdx.x & (kWave - 1);
@@ -3198,7 +3094,7 @@ __global__ __launch_bounds__(1024) void k_unpermute(int64_t P, int nb,
 }
 
 // ------------------------------------------------------------------ pullback K5
-// (pose groups and the direct-store mode: the reduction as a launch of its own)
+// (pose groups and batches un-permuted in one pass: the reduction as a launch of its own)
 template <typename T>
 __global__ __launch_bounds__(1024) void k_pose_reduce(PoseReduceArgs<T> pr) {
     pose_reduce_body<T>((int)blockIdx.x, blockIdx.y, gridDim.y > 1, pr);
@@ -3255,33 +3151,6 @@ __global__ __launch_bounds__(256) void k_unsort(int64_t P, const uint32_t* __res
 
 // ------------------------------------------------------------------ host side
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// Experiment knobs: in builds with -DDPR_EXPERIMENTS environment overrides of the compiled-in defaults, read
-// ONCE per process (function-local static: thread-safe, no getenv on the call path) and clamped to valid
-// ranges; in the shipped library the defaults (env_knob, dpr_tiled.h).
-struct Knobs {
-    int cap3d_div, cap2d_div, cap_min, pose_group, scatter_wc, bwd_unpermute, compact_records,
-        splat_blocked, fixed_point, fuse_tilescan, bin_direct_store;
-};
-static const Knobs& knobs() {
-    static const Knobs k = [] {
-        auto env_int = [](const char* name, int dflt, int lo, int hi) { return env_knob(name, dflt, lo, hi); };
-        Knobs q;
-        q.cap3d_div = env_int("DPR_CAP3D_DIV", 256, 1, 1 << 20);
-        q.cap2d_div = env_int("DPR_CAP2D_DIV", 2048, 0, 1 << 20);  // 0: use the 3-D rule
-        q.cap_min = env_int("DPR_CAP_MIN", 4096, 256, 1 << 24);
-        q.pose_group = env_int("DPR_POSE_GROUP", 16, 1, 16);
-        q.scatter_wc = env_int("DPR_SCATTER_WC", 1, 0, 1);
-        q.bwd_unpermute = env_int("DPR_BWD_UNPERMUTE", 1, 0, 1);
-        q.compact_records = env_int("DPR_COMPACT_RECORDS", 1, 0, 1);
-        q.splat_blocked = env_int("DPR_SPLAT_BLOCKED", 2, 0, 2);  // 2: decided on the device
-        q.fixed_point = env_int("DPR_FIXED_POINT", 1, 0, 1);  // 0: f64 LDS accumulators for fp32 data too
-        q.fuse_tilescan = env_int("DPR_FUSE_TILESCAN", 1, 0, 1);  // 0: k_tilescan as a launch of its own
-        q.bin_direct_store = env_int("DPR_BIN_DIRECT_STORE", 1, 0, 1);  // 0: fp64 batches stage records in LDS too
-        return q;
-    }();
-    return k;
-}
 
 // compute units of the current device (cached)
 static int cu_count() {
@@ -3341,10 +3210,9 @@ struct Plan {
 // 4.8 GB fp64) and by the caller through DPR_FLAG_MAX_POSE_GROUP(n) (include/dpr.h).
 constexpr int kMaxGroup = 16;
 static int pose_group(int NT, int64_t P, int64_t B, int max_group) {
-    int limit = knobs().pose_group;
-    if (max_group > 0 && max_group < limit) limit = max_group;
+    const int limit = (max_group > 0 && max_group < kMaxGroup) ? max_group : kMaxGroup;
     int bg = 1;
-    while (bg * 2 <= limit && bg * 2 <= kMaxGroup && bg * 2 <= B && NT * bg * 2 <= 4096 &&
+    while (bg * 2 <= limit && bg * 2 <= B && NT * bg * 2 <= 4096 &&
            P * bg * 2 <= ((int64_t)1 << 27))  // records of a group: <= 2 GiB (fp32)
         bg *= 2;
     return bg;
@@ -3359,14 +3227,12 @@ static Plan make_plan(size_t elem, int n_out, int NT1, int64_t P1, int64_t B, in
     if (share_batch) max_group = 1;  // a kept binning is per pose
     pl.pose_stride = 0;
     pl.sort_inside = !coherent && NT1 > 4096 && B >= 4 && P1 >= 200000;
-    // (the direct-store pullback mode, an experiment knob, needs the index array only the plain
-    // scatter writes)
-    // ... and local binning is per pose: a batch that forms pose groups (few tiles) keeps the
+    // Local binning is per pose: a batch that forms pose groups (few tiles) keeps the
     // grouped pipeline, which reads the points once per group (10 M points -> 512^2, 4 poses:
     // 0.56 ms grouped, 0.63 ms pose by pose on local bins)
     pl.bg = pose_group(NT1, P1, B, max_group);
     pl.local = (coherent || pl.sort_inside) && !slabbed && NT1 <= kMaxLocalTiles &&
-               knobs().bwd_unpermute && pl.bg == 1;
+               pl.bg == 1;
     // poses binned by one k_bin_local launch (the points are read once for all of them): every
     // pose of a kept batch, else up to 8 -- each needs its own records, P * lb <= 2^29
     pl.lb = 1;
@@ -3383,11 +3249,11 @@ static Plan make_plan(size_t elem, int n_out, int NT1, int64_t P1, int64_t B, in
     const int64_t P = P1 * pl.bg;        // records
     // Slices of the cloud = blocks of k_count / the scatter = rows of the counts table.
     int64_t nblk, chunk;
-    if (DPR_WC_SLICES && NT <= 4096) {
+    if (NT <= 4096) {
         // write-combining scatter (one workgroup per CU: its LDS): at most one slice per CU, so
         // that all of them run at once, and whole sub-chunks per slice (a partly filled round costs
         // as much as a full one; 3e6 points: 489 slices of 1.5 rounds -> 245 of 3: 0.131 -> 0.124 ms)
-        const int64_t sub = (elem == 4) ? DPR_WC_PPT * kWcThreads : DPR_WC_PPT * kWcThreads / 2;
+        const int64_t sub = (elem == 4) ? kWcPpt * kWcThreads : kWcPpt * kWcThreads / 2;
         chunk = ((P1 + 255) / 256 + sub - 1) / sub * sub;
         if (chunk < sub) chunk = sub;
     } else {
@@ -3417,13 +3283,13 @@ static Plan make_plan(size_t elem, int n_out, int NT1, int64_t P1, int64_t B, in
     // (a forward call that keeps nothing for a pullback splits later: the parts of a split tile
     // cost the halo pass more than a 2x longer item costs the fixed-point tile kernel -- 1 M points
     // -> 128^3: forward 0.065 -> 0.059 ms; the pullback's gather prefers the finer split)
-    int64_t cap = P / knobs().cap3d_div;
-    const int64_t cap_min = fwd_only ? 2 * (int64_t)knobs().cap_min : knobs().cap_min;
+    int64_t cap = P / 256;
+    const int64_t cap_min = fwd_only ? 2 * 4096 : 4096;
     if (cap < cap_min) cap = cap_min;
     if (n_out == 2) {
         // 2-D grids have few tiles (256 at 512^2) with cheap LDS tiles (8.7 KB): split
         // earlier so that a dense projection still gives the chip ~2048 items
-        cap = knobs().cap2d_div > 0 ? P / knobs().cap2d_div : cap;
+        cap = P / 2048;
         if (cap < 2048) cap = 2048;
     }
     pl.cap = (uint32_t)cap;
@@ -3502,9 +3368,9 @@ static Plan make_plan(size_t elem, int n_out, int NT1, int64_t P1, int64_t B, in
 
 // Identity of a workspace layout: a REUSE_BINNING pullback must read the lists where -- and in
 // the form in which -- the KEEP_BINNING forward wrote them.  The two calls compute their plans
-// independently (DPR_FLAG_COHERENT_POINTS, DPR_FLAG_MAX_POSE_GROUP and the environment knobs all
-// move regions), so the forward stores this id in the header and the pullback's kernels compare
-// it on the device like the rest of the header.
+// independently (DPR_FLAG_COHERENT_POINTS and DPR_FLAG_MAX_POSE_GROUP move regions), so the
+// forward stores this id in the header and the pullback's kernels compare it on the device like
+// the rest of the header.
 static uint32_t plan_layout_id(const Plan& pl) {
     uint64_t h = 1469598103934665603ull;  // FNV-1a over the fields that place or shape the lists
     auto mix = [&](uint64_t v) {
@@ -3646,30 +3512,23 @@ template <typename K> static int allow_big_lds(K kernel, size_t bytes) {
     return DPR_OK;
 }
 
-// Which scatter a binning uses: the write-combining one whenever its LDS tables fit and the
-// original indices are not needed as a separate array.
-static bool scatter_is_wc(int NT, int nb, bool has_pw, bool want_idx) {
-    const int wc = knobs().scatter_wc || nb > 1;
-    const bool needs_idx = has_pw && want_idx && knobs().bwd_unpermute == 0 && nb == 1;
-    return wc && NT * nb <= 4096 && !needs_idx;
-}
+// Which scatter a binning uses: the write-combining one whenever its LDS tables fit.
+static bool scatter_is_wc(int NT, int nb) { return NT * nb <= 4096; }
 
 // Compact 3-word records: default point weights, write-combining scatter, forward-only binning
 // (nothing downstream needs the original index or room for a gradient record).
 static bool records_are_compact(int NT, int nb, bool has_pw, bool want_idx) {
-    if (has_pw || want_idx || !knobs().compact_records) return false;
-    return scatter_is_wc(NT, nb, has_pw, want_idx);
+    return !has_pw && !want_idx && scatter_is_wc(NT, nb);
 }
 
 template <typename T, int NI, int NO, bool HAS_PW, bool WANT_IDX>
 static int launch_scatter(hipStream_t st, const GridDesc<NO>& gd, const TileGeom<NO>& tg,
                           const Plan& pl, char* ws, int64_t P, const T* points, const T* pw,
-                          const T* rot, const T* trans, int64_t b, int nb, T* d_pts, T* d_pw,
-                          int zero_dropped, const TileScanArgs& ts, bool fused) {
-    // write-combining variant: needs 2 NT counters + the sub-chunk in LDS, and does not
-    // produce rec_idx (only the direct-store pullback mode with point weights reads that)
-    if (scatter_is_wc(tg.NT, nb, HAS_PW, WANT_IDX)) {
-        constexpr int S = (sizeof(T) == 4) ? DPR_WC_PPT * kWcThreads : DPR_WC_PPT * kWcThreads / 2;
+                          const T* rot, const T* trans, int64_t b, int nb, const TileScanArgs& ts,
+                          bool fused) {
+    // write-combining variant: needs 2 NT counters + the sub-chunk in LDS
+    if (scatter_is_wc(tg.NT, nb)) {
+        constexpr int S = (sizeof(T) == 4) ? kWcPpt * kWcThreads : kWcPpt * kWcThreads / 2;
         const size_t lds2 = (size_t)tg.NT * (nb + 1) * 4;
 #define DPR_LAUNCH_WC(GROUP, W3)                                                                  \
     hipLaunchKernelGGL((k_scatter_wc<T, NI, NO, HAS_PW, S, GROUP, W3>),                          \
@@ -3678,8 +3537,9 @@ static int launch_scatter(hipStream_t st, const GridDesc<NO>& gd, const TileGeom
                        b, nb, (const uint32_t*)(ws + pl.off_counts),                             \
                        (const uint32_t*)(ws + pl.off_tile_start),                                \
                        (RecT<T, W3>*)(ws + pl.off_rec),                     \
-                       WANT_IDX ? (uint32_t*)(ws + pl.off_slot) : (uint32_t*)nullptr, d_pts,     \
-                       d_pw, zero_dropped, (uint32_t*)(ws + pl.off_nitems) + 2, fused ? 1 : 0, ts)
+                       WANT_IDX ? (uint32_t*)(ws + pl.off_slot) : (uint32_t*)nullptr,            \
+                       (T*)nullptr, (T*)nullptr, 0, (uint32_t*)(ws + pl.off_nitems) + 2,          \
+                       fused ? 1 : 0, ts)
         if constexpr (!HAS_PW) {
             if (records_are_compact(tg.NT, nb, false, WANT_IDX)) {
                 if (nb > 1) DPR_LAUNCH_WC(true, true);
@@ -3698,8 +3558,8 @@ static int launch_scatter(hipStream_t st, const GridDesc<NO>& gd, const TileGeom
                        lds, st, gd, tg, P, pl.chunk, points, pw, rot, trans, b,
                        (const uint32_t*)(ws + pl.off_counts),
                        (const uint32_t*)(ws + pl.off_tile_start), (Rec4<T>*)(ws + pl.off_rec),
-                       (uint32_t*)(ws + pl.off_idx), (uint32_t*)(ws + pl.off_slot), d_pts, d_pw,
-                       zero_dropped, (uint32_t*)(ws + pl.off_nitems) + 2);
+                       (uint32_t*)(ws + pl.off_idx), (uint32_t*)(ws + pl.off_slot), (T*)nullptr,
+                       (T*)nullptr, 0, (uint32_t*)(ws + pl.off_nitems) + 2);
     return DPR_OK;
 }
 
@@ -3707,9 +3567,8 @@ static int launch_scatter(hipStream_t st, const GridDesc<NO>& gd, const TileGeom
 template <typename T, int NI, int NO>
 static int bin_points(hipStream_t st, const GridDesc<NO>& gd, const TileGeom<NO>& tg,
                       const Plan& pl, char* ws, int64_t P, const T* points, const T* pw,
-                      const T* rot, const T* trans, int64_t b, int nb, bool want_idx, T* d_pts,
-                      T* d_pw, int zero_dropped, bool keep_valid = false,
-                      const T* hdr_points = nullptr, const T* hdr_pw = nullptr) {
+                      const T* rot, const T* trans, int64_t b, int nb, bool want_idx,
+                      bool keep_valid, const T* hdr_points, const T* hdr_pw) {
     // (the header names the caller's buffers; `points` may be the library's sorted copy)
     if (!hdr_points) {
         hdr_points = points;
@@ -3759,27 +3618,22 @@ static int bin_points(hipStream_t st, const GridDesc<NO>& gd, const TileGeom<NO>
                        counts, pl.nblk, NTe, totals, (uint32_t*)(ws + pl.off_nitems) + 2);
     // The tile scan rides in the scatter launch as one extra workgroup when the write-combining
     // scatter runs (its workgroups scan the totals themselves) and a CU is left for it.
-    const bool fused = knobs().fuse_tilescan && scatter_is_wc(tg.NT, nb, pw != nullptr, want_idx) &&
-                       pl.nblk < cu_count();
+    const bool fused = scatter_is_wc(tg.NT, nb) && pl.nblk < cu_count();
     if (!fused) hipLaunchKernelGGL(k_tilescan, dim3(1), dim3(1024), 0, st, ts);
     stage_mark(st);
     int rc;
     if (pw) {
-        rc = want_idx ? launch_scatter<T, NI, NO, true, true>(st, gd, tg, pl, ws, P, points, pw,
-                                                              rot, trans, b, nb, d_pts,
-                                                              d_pw, zero_dropped, ts, fused)
-                      : launch_scatter<T, NI, NO, true, false>(st, gd, tg, pl, ws, P, points, pw,
-                                                               rot, trans, b, nb, d_pts,
-                                                               d_pw, zero_dropped, ts, fused);
+        rc = want_idx ? launch_scatter<T, NI, NO, true, true>(st, gd, tg, pl, ws, P, points, pw, rot, trans,
+                                                              b, nb, ts, fused)
+                      : launch_scatter<T, NI, NO, true, false>(st, gd, tg, pl, ws, P, points, pw, rot,
+                                                               trans, b, nb, ts, fused);
     } else {
         // without point weights the original index rides in the record for free; slot_of is
         // only written when a pullback will consume the binning
-        rc = want_idx ? launch_scatter<T, NI, NO, false, true>(st, gd, tg, pl, ws, P, points, pw,
-                                                               rot, trans, b, nb, d_pts,
-                                                               d_pw, zero_dropped, ts, fused)
-                      : launch_scatter<T, NI, NO, false, false>(st, gd, tg, pl, ws, P, points, pw,
-                                                                rot, trans, b, nb, d_pts,
-                                                                d_pw, zero_dropped, ts, fused);
+        rc = want_idx ? launch_scatter<T, NI, NO, false, true>(st, gd, tg, pl, ws, P, points, pw, rot,
+                                                               trans, b, nb, ts, fused)
+                      : launch_scatter<T, NI, NO, false, false>(st, gd, tg, pl, ws, P, points, pw, rot,
+                                                                trans, b, nb, ts, fused);
     }
     stage_mark(st);
     return rc;
@@ -3805,9 +3659,8 @@ template <typename K> static int allow_lds_bytes(K kernel, size_t bytes) {
 template <typename T, int NI, int NO>
 static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGeom<NO>& tg,
                             const Plan& pl, char* ws, int64_t P, const T* points, const T* pw,
-                            const T* rot, const T* trans, int64_t b, int nb, bool want_idx, T* d_pts,
-                            T* d_pw, int zero_dropped, bool keep_valid,
-                            const T* hdr_points = nullptr, const T* hdr_pw = nullptr) {
+                            const T* rot, const T* trans, int64_t b, int nb, bool want_idx,
+                            bool keep_valid, const T* hdr_points, const T* hdr_pw) {
     if (!hdr_points) {  // the header names the caller's buffers
         hdr_points = points;
         hdr_pw = pw;
@@ -3835,11 +3688,11 @@ static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGe
                                 STAGE>;                                                           \
         if (int rc = allow_lds_bytes(kern, lds)) return rc;                                       \
         hipLaunchKernelGGL(kern, dim3((unsigned)pl.nsub), dim3(TH), lds, st, gd, tg, P, points,   \
-                           pw, rot, trans, b, nb, la, want_idx ? 1 : 0, spare, d_pts, d_pw,       \
-                           zero_dropped);                                                         \
+                           pw, rot, trans, b, nb, la, want_idx ? 1 : 0, spare, (T*)nullptr,       \
+                           (T*)nullptr, 0);                                                       \
     } while (0)
     // fp64 batches: two 512-thread workgroups per CU without LDS staging (see k_bin_local)
-    const bool direct_store = sizeof(T) == 8 && nb > 1 && knobs().bin_direct_store;
+    const bool direct_store = sizeof(T) == 8 && nb > 1;
     // (the 512-thread variant exists for fp64 only: the branch is not even instantiated for fp32 data)
 #define DPR_LAUNCH_LOCAL(HAS_PW, W3)                                        \
     do {                                                                    \
@@ -3849,7 +3702,7 @@ static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGe
         } else DPR_LAUNCH_LOCAL2(HAS_PW, W3, false, 1024, true);            \
     } while (0)
     if (pw) DPR_LAUNCH_LOCAL(true, false);
-    else if (!want_idx && knobs().compact_records) DPR_LAUNCH_LOCAL(false, true);
+    else if (!want_idx) DPR_LAUNCH_LOCAL(false, true);
     else DPR_LAUNCH_LOCAL(false, false);
 #undef DPR_LAUNCH_LOCAL
 #undef DPR_LAUNCH_LOCAL2
@@ -3880,7 +3733,7 @@ static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGe
     ra.trans_words = (int)(NO * sizeof(T) / 4);
     // the run scan rides in the placement launch when every placement workgroup can scan the
     // descriptor counts itself (up to 4096 tiles)
-    const bool fused = knobs().fuse_tilescan && tg.NT <= 4096;
+    const bool fused = tg.NT <= 4096;
     ra.clear_cursors = 0;  // (cleared with the totals above)
     if (!fused) hipLaunchKernelGGL(k_runscan, dim3((unsigned)nb), dim3(1024), 0, st, ra);
     int64_t pblocks = (pl.nsub + 15) / 16;  // a wave per sub-chunk slot, 16 waves per workgroup
@@ -3939,7 +3792,6 @@ int raster_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G,
     T* halo = (T*)(ws + pl.off_aux);
     T* ovf = (T*)(ws + pl.off_aux +
                   align_up((size_t)NTmax * pl.bg * halo_count<NO>() * sizeof(T)));
-    const int blocked = knobs().splat_blocked;
     // copy of the per-pose workspace pose b lives in: its own when the binning is kept, else its
     // place in the local batch
     auto copy_of = [&](int64_t b) { return (flags & 3u) && B > 1 ? b : (pl.local ? b % pl.lb : 0); };
@@ -3956,14 +3808,14 @@ int raster_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G,
             if (b % pl.lb == 0) {  // first pose of a local batch: bin all its poses
                 const int nlb = (int)((B - b < pl.lb) ? B - b : pl.lb);
                 if (int rc = bin_points_local<T, NI, NO>(st, gd, tg, pl, wsb, P, points, pw, rot, trans,
-                                                         b, nlb, keep, (T*)nullptr, (T*)nullptr, 0,
-                                                         keep, user_points, user_pw))
+                                                         b, nlb, keep, keep, user_points, user_pw))
                     return rc;
             }
         } else if (int rc = bin_points<T, NI, NO>(st, gd, tg, pl, wsb, P, points, pw, rot, trans, b,
-                                                  (int)nb, keep, (T*)nullptr, (T*)nullptr, 0, keep,
-                                                  user_points, user_pw))
+                                                  (int)nb, keep, keep, user_points, user_pw))
             return rc;
+        // (k_tile_splat's record assignment: 2 = chosen on the device from the order of the cloud;
+        // the last argument asks for fixed-point sums wherever FixScale allows them)
 #define DPR_LAUNCH_SPLAT_RUNS(HAS_PW, W3)                                                        \
     hipLaunchKernelGGL((k_tile_splat_runs<T, NI, NO, HAS_PW, W3, true>), dim3(pl.max_items),    \
                        dim3(kSplatThreads), 0, st, gd, tg,                                      \
@@ -3972,9 +3824,8 @@ int raster_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G,
                        (const WorkItem*)(wsb + pl.off_items),                                   \
                        (const uint32_t*)(wsb + pl.off_nitems),                                  \
                        (const uint32_t*)(wsb + pl.off_tslab), rot, trans, ow, bg, b, out, halo, \
-                       ovf, (pl.sort_inside || knobs().splat_blocked == 0) ? 0 : 1,                 \
-                       (const uint32_t*)(ws0 + pl.off_ltot) + 2 * tg.NT,                        \
-                       knobs().fixed_point)
+                       ovf, pl.sort_inside ? 0 : 1, (const uint32_t*)(ws0 + pl.off_ltot) + 2 * tg.NT, \
+                       1)
 #define DPR_LAUNCH_SPLAT(HAS_PW, W3)                                                             \
     hipLaunchKernelGGL((k_tile_splat<T, NI, NO, HAS_PW, W3>), dim3(pl.max_items),               \
                        dim3(kSplatThreads), 0, st, gd, tg,                                      \
@@ -3982,11 +3833,10 @@ int raster_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G,
                        (const WorkItem*)(wsb + pl.off_items),                                   \
                        (const uint32_t*)(wsb + pl.off_nitems),                                  \
                        (const uint32_t*)(wsb + pl.off_tslab), rot, trans, ow, bg, b, out, halo, \
-                       ovf, blocked, (const uint32_t*)(wsb + pl.off_nitems) + 2,                \
-                       knobs().fixed_point)
+                       ovf, 2, (const uint32_t*)(wsb + pl.off_nitems) + 2, 1)
         if (pl.local) {
             if (pw) DPR_LAUNCH_SPLAT_RUNS(true, false);
-            else if (!keep && knobs().compact_records) DPR_LAUNCH_SPLAT_RUNS(false, true);
+            else if (!keep) DPR_LAUNCH_SPLAT_RUNS(false, true);
             else DPR_LAUNCH_SPLAT_RUNS(false, false);
         } else if (pw) DPR_LAUNCH_SPLAT(true, false);
         else if (records_are_compact(tg.NT, (int)nb, false, keep)) DPR_LAUNCH_SPLAT(false, true);
@@ -4054,7 +3904,6 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
     }
     double* partials = (double*)(ws + pl.off_aux);
     constexpr int NVAL = NO * NI + NO + 2;  // + 1 loss column in residual mode
-    const bool unperm1 = knobs().bwd_unpermute != 0;
     BinHeader want = make_header<T, NI, NO>(grid, P, user_points, user_pw);
     want.layout = plan_layout_id(pl);
     if (!reuse) want.magic = 0;  // own binning: nothing to validate
@@ -4062,7 +3911,7 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
     // over all of them at the end instead of a read-modify-write of the gradients per pose
     // (the same for the poses of a local batch, which were binned together into their own copies:
     // one pass per batch, the first one overwriting, the later ones accumulating)
-    const bool batch_unperm = pl.pose_stride > 0 && B > 1 && unperm1 && pl.bg == 1 && P > 0 &&
+    const bool batch_unperm = pl.pose_stride > 0 && B > 1 && pl.bg == 1 && P > 0 &&
                               (reuse || pl.local);
     // poses whose gradient records are summed by one un-permute pass
     const int64_t ub = !batch_unperm ? 1 : ((flags & 3u) ? B : pl.lb);
@@ -4095,18 +3944,10 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
         pr.accumulate = slab > 0 ? 1 : 0;
         const unsigned n_reduce = (unsigned)(rs.target ? NVAL + 1 : NVAL);
         bool reduced = false;
-        // a pose group always goes through the gradient records (several (pose, tile) blocks
-        // own the same point, so they cannot store to ds_dpoints directly)
-        const bool unperm = unperm1 || nb > 1;
         if (reuse) {
             // The binning of the preceding raster call (same points / pose / grid) is in the
-            // workspace.  Direct-store mode: points without an in-range voxel are in no tile,
-            // clear the outputs first (the un-permute mode reads zeros from the spare slot).
-            // (once, before the first pose: the later poses of a kept batch accumulate)
-            if (P > 0 && !unperm && b == 0) {
-                DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
-                if (d_pw) DPR_HIP(hipMemsetAsync(d_pw, 0, sizeof(T) * (size_t)P, st));
-            }
+            // workspace (points without an in-range voxel are in no tile: the un-permute reads
+            // zeros from the spare slot for them).
             stage_mark(st);
             stage_mark(st);
             stage_mark(st);
@@ -4114,9 +3955,7 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
             if (b % pl.lb == 0) {  // first pose of a local batch: bin all its poses
                 const int nlb = (int)((B - b < pl.lb) ? B - b : pl.lb);
                 if (int rc = bin_points_local<T, NI, NO>(st, gd, tg, pl, wsb, P, points, pw, rot, trans,
-                                                         b, nlb, true, d_pts, d_pw,
-                                                         (first_acc && !unperm) ? 1 : 0, false,
-                                                         user_points, user_pw))
+                                                         b, nlb, true, false, user_points, user_pw))
                     return rc;
             } else {
                 stage_mark(st);
@@ -4124,68 +3963,54 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
                 stage_mark(st);
             }
         } else if (int rc = bin_points<T, NI, NO>(st, gd, tg, pl, wsb, P, points, pw, rot, trans, b,
-                                                  (int)nb, true, d_pts, d_pw,
-                                                  (first_acc && !unperm) ? 1 : 0, false, user_points,
-                                                  user_pw))
+                                                  (int)nb, true, false, user_points, user_pw))
             return rc;
-#define DPR_LAUNCH_GATHER_RUNS(HAS_PW, FIRST, UNP)                                               \
-    hipLaunchKernelGGL((k_tile_gather_runs<T, NI, NO, HAS_PW, FIRST, UNP, true>),                \
+        // The gradient {d point, d point_weight} of every point overwrites its record; k_unpermute
+        // brings the records back to the original order
+#define DPR_LAUNCH_GATHER_RUNS(HAS_PW)                                                           \
+    hipLaunchKernelGGL((k_tile_gather_runs<T, NI, NO, HAS_PW, true, true, true>),                \
                        dim3(pl.max_items), dim3(gather_threads<T>()), 0, st, gd, tg,                  \
                        (Rec4<T>*)(wsb + pl.off_rec), (const RunDesc*)(wsb + pl.off_sdesc),       \
                        pl.nsub * pl.sub, (const uint32_t*)(wsb + pl.off_idx),                    \
                        (const WorkItem*)(wsb + pl.off_items),                                    \
                        (const uint32_t*)(wsb + pl.off_nitems), pl.max_items, g, rot, trans, ow,  \
                        b, d_pts, d_pw, partials, rs, want, hdr)
-#define DPR_LAUNCH_GATHER_PLAIN(HAS_PW, FIRST, UNP)                                              \
-    hipLaunchKernelGGL((k_tile_gather<T, NI, NO, HAS_PW, FIRST, UNP>), dim3(pl.max_items),       \
+#define DPR_LAUNCH_GATHER_PLAIN(HAS_PW)                                                          \
+    hipLaunchKernelGGL((k_tile_gather<T, NI, NO, HAS_PW, true, true>), dim3(pl.max_items),       \
                        dim3(gather_threads<T>()), 0, st, gd, tg, (Rec4<T>*)(wsb + pl.off_rec), P * nb, \
                        (const uint32_t*)(wsb + pl.off_idx), (const WorkItem*)(wsb + pl.off_items), \
                        (const uint32_t*)(wsb + pl.off_nitems), pl.max_items, g, rot, trans, ow,   \
                        b, d_pts, d_pw, partials, rs, want, hdr)
-#define DPR_LAUNCH_GATHER(HAS_PW, FIRST, UNP)                       \
-    do {                                                            \
-        if (pl.local) DPR_LAUNCH_GATHER_RUNS(HAS_PW, FIRST, UNP);   \
-        else DPR_LAUNCH_GATHER_PLAIN(HAS_PW, FIRST, UNP);           \
-    } while (0)
-        if (unperm) {
-            if (pw) DPR_LAUNCH_GATHER(true, true, true);
-            else DPR_LAUNCH_GATHER(false, true, true);
-            stage_mark(st);
-            if (P > 0) {
-                // one pose: a block covers a whole scatter sub-chunk (4 points per thread); a
-                // pose group already has nb gradient records in flight per point
+        if (pl.local) {
+            if (pw) DPR_LAUNCH_GATHER_RUNS(true);
+            else DPR_LAUNCH_GATHER_RUNS(false);
+        } else if (pw) DPR_LAUNCH_GATHER_PLAIN(true);
+        else DPR_LAUNCH_GATHER_PLAIN(false);
+#undef DPR_LAUNCH_GATHER_RUNS
+#undef DPR_LAUNCH_GATHER_PLAIN
+        stage_mark(st);
+        if (P > 0) {
+            // one pose: a block covers a whole scatter sub-chunk (4 points per thread); a
+            // pose group already has nb gradient records in flight per point
 #define DPR_LAUNCH_UNPERM(FIRST, UPB, RB)                                                        \
     hipLaunchKernelGGL((k_unpermute<T, NI, FIRST, UPB>),                                         \
                        dim3((unsigned)((P + UPB * 1024 - 1) / (UPB * 1024)) + (RB)), dim3(1024), \
                        0, st, P, (int)nb, (const Rec4<T>*)(wsb + pl.off_rec),                    \
                        (const uint32_t*)(wsb + pl.off_slot), d_pts, d_pw, (const BinHeader*)hdr, \
                        (int)(RB), pr, (size_t)0)
-                if (batch_unperm) {
-                    // a kept batch: the records of all poses are summed once, after the loop
-                } else if (nb > 1) {
-                    if (first_acc) DPR_LAUNCH_UNPERM(true, 1, 0);
-                    else DPR_LAUNCH_UNPERM(false, 1, 0);
-                } else {
-                    // one pose: the per-pose reduction rides in the same launch
-                    if (first_acc) DPR_LAUNCH_UNPERM(true, DPR_UPB, n_reduce);
-                    else DPR_LAUNCH_UNPERM(false, DPR_UPB, n_reduce);
-                    reduced = true;
-                }
-#undef DPR_LAUNCH_UNPERM
-            }
-        } else {
-            if (pw) {
-                if (b == 0) DPR_LAUNCH_GATHER(true, true, false);
-                else DPR_LAUNCH_GATHER(true, false, false);
+            if (batch_unperm) {
+                // a kept batch: the records of all poses are summed once, after the loop
+            } else if (nb > 1) {
+                if (first_acc) DPR_LAUNCH_UNPERM(true, 1, 0);
+                else DPR_LAUNCH_UNPERM(false, 1, 0);
             } else {
-                if (b == 0) DPR_LAUNCH_GATHER(false, true, false);
-                else DPR_LAUNCH_GATHER(false, false, false);
+                // one pose: the per-pose reduction rides in the same launch
+                if (first_acc) DPR_LAUNCH_UNPERM(true, kUpb, n_reduce);
+                else DPR_LAUNCH_UNPERM(false, kUpb, n_reduce);
+                reduced = true;
             }
-            stage_mark(st);
+#undef DPR_LAUNCH_UNPERM
         }
-#undef DPR_LAUNCH_GATHER
-#undef DPR_LAUNCH_GATHER_RUNS
-#undef DPR_LAUNCH_GATHER_PLAIN
         stage_mark(st);
         if (!reduced)
             hipLaunchKernelGGL((k_pose_reduce<T>), dim3(n_reduce, (unsigned)nb), dim3(1024), 0, st,

@@ -176,11 +176,9 @@ extern "C" {
  * ~2^-12 of the local weight), which keep at least 16 good bits.  Default weights (NULL) never trip the guard.
  * tests/test_parity_gpu.py::test_fp32_cells_reached_only_by_small_weights_keep_their_relative_precision.
  *
- * ENVIRONMENT.  The library reads one variable, DPR_MAX_TILES (16..32768, default 32768): the number of tiles
- * DPR_ALGO_TILED handles per launch sequence before it cuts the grid into slabs along the last axis -- a test
- * hook that lets a small grid walk the slab code; it moves slab boundaries, never results.  The A/B switches
- * named in profiles/r0N_experiments.md (DPR_FIXED_POINT, DPR_SORT_BITS, DPR_CO_SORT, DPR_OWN_*, ...) exist
- * only in builds made with `make EXPERIMENTS=1` (-DDPR_EXPERIMENTS); the shipped library ignores them. */
+ * ENVIRONMENT.  DPR_MAX_TILES is the only variable the library reads (16..32768, default 32768): the number
+ * of tiles DPR_ALGO_TILED handles per launch sequence before it cuts the grid into slabs along the last axis
+ * -- a test hook that lets a small grid walk the slab code; it moves slab boundaries, never results. */
 
 /* flags (the *_ex entry points).  DPR_ALGO_TILED: any B -- with B > 1 every pose keeps its own
  * binning (the per-pose part of the workspace is laid out B times; pose groups are off);

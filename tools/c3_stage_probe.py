@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Per-stage times of the C3 step (10 M points 0.4*N(0,I) -> 256^3 fp32, one pose, tiled KEEP / REUSE pair,
-as bench.py runs it) for the library named by DPR_LIB_OVERRIDE -- the A/B harness of the round-6 kernel
-experiments (ablation builds: `make -C diffpointrasterisation.jl_amd/csrc ../libdpr_abl<N>.so`).
+as bench.py runs it) for the library named by DPR_LIB_OVERRIDE (default: the package's libdpr.so).
   python tools/c3_stage_probe.py [--coherent] [--P 10000000] [--grid 256] [--reps 30] [--tag name]
 Prints one JSON line: {"tag", "raster": {stage: ms}, "pullback": {stage: ms}, "pair_ms": event-timed step}."""
 import argparse, json, os, sys

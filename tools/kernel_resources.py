@@ -4,7 +4,7 @@
     python tools/kernel_resources.py            # kernels with spills or scratch
     python tools/kernel_resources.py --all      # every kernel
 
-`tests/test_abi.py::test_no_kernel_spills_or_uses_scratch` uses `kernel_resources()` as the
+`tests/test_abi.py::test_scratch_use_matches_the_allow_list` uses `kernel_resources()` as the
 zero-scratch gate of the shipped library."""
 import os
 import re

@@ -1,4 +1,4 @@
-"""Batched poses: per-pose pipeline (DPR_POSE_GROUP=1) vs pose groups, one GPU."""
+"""Batched poses: per-pose pipeline (max_pose_group=1) vs pose groups, one GPU."""
 import sys, os, argparse
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
