@@ -11,6 +11,8 @@ from .interface import (ColumnMajorRotation, DimensionMismatch, PullbackResult, 
                         sharing_effective, sort_points, to_grid_layout, workspace_bytes)
 from .timing import stage_times
 from .autograd import raster_ad
+from .channels import (empty_channel_grid, raster_channels, raster_channels_, raster_channels_ad,
+                       raster_pullback_channels_, resolve_algo_channels, workspace_bytes_channels)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -20,4 +22,6 @@ __all__ = [
     "empty_grid", "to_grid_layout", "workspace_bytes", "resolve_algo", "sharing_effective", "sort_points", "build", "lib",
     "stage_times", "raster_sharded", "raster_pullback_sharded_", "shard_range",
     "raster_point_sharded", "raster_pullback_point_sharded_",
+    "raster_channels", "raster_channels_", "raster_pullback_channels_", "raster_channels_ad", "empty_channel_grid",
+    "resolve_algo_channels", "workspace_bytes_channels",
 ]

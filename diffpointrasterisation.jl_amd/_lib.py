@@ -52,6 +52,9 @@ EXPORTS = [
     "dpr_raster_residual_pullback_ex_f32", "dpr_raster_residual_pullback_ex_f64",
     "dpr_comm_unique_id", "dpr_comm_init", "dpr_comm_destroy", "dpr_comm_world", "dpr_comm_rank",
     "dpr_shard_range", "dpr_raster_pullback_sharded_f32", "dpr_raster_pullback_sharded_f64",
+    "dpr_resolve_algo_channels", "dpr_workspace_bytes_channels_ex_f32", "dpr_workspace_bytes_channels_ex_f64",
+    "dpr_raster_channels_ex_f32", "dpr_raster_channels_ex_f64",
+    "dpr_raster_pullback_channels_ex_f32", "dpr_raster_pullback_channels_ex_f64",
 ]
 
 _lib = None
@@ -137,6 +140,20 @@ def lib() -> ctypes.CDLL:
         f.restype = i
         f.argtypes = ([vp, i, ctypes.c_uint, i, i, vp, i64, i64, vp, vp, ctypes.c_double]
                       + [vp] * 12 + [vp, sz])
+    L.dpr_resolve_algo_channels.restype = i
+    L.dpr_resolve_algo_channels.argtypes = [i, i, i, vp, i64, i64, i64]
+    for suf in ("f32", "f64"):
+        f = getattr(L, f"dpr_workspace_bytes_channels_ex_{suf}")
+        f.restype = sz
+        f.argtypes = [i, i, ctypes.c_uint, i, i, vp, i64, i64, i64]
+        # stream, algo, flags, n_in, n_out, grid, P, B, C, out, points, rot, trans, bg, ow, pw, ws, ws_bytes
+        f = getattr(L, f"dpr_raster_channels_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 7 + [vp, sz]
+        # ..., C, ds_dout, points, rot, trans, ow, pw, 6 outputs, ws, ws_bytes
+        f = getattr(L, f"dpr_raster_pullback_channels_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 12 + [vp, sz]
     L.dpr_comm_unique_id.restype = i
     L.dpr_comm_unique_id.argtypes = [vp, sz]
     L.dpr_comm_init.restype = i

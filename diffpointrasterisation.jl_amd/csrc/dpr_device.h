@@ -11,6 +11,7 @@
 namespace dpr {
 
 constexpr int kWave = 64;  // CDNA wavefront
+constexpr int kMaxChannels = 16;  // weight channels of the multi-channel entry points (dpr_raster_channels_ex_*)
 
 template <typename T> __device__ __forceinline__ T ceil_t(T x);
 template <> __device__ __forceinline__ float ceil_t<float>(float x) { return ceilf(x); }

@@ -33,6 +33,15 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
                    const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw,
                    void* ws, size_t ws_bytes, Residual<T> rs);
 
+// multi-channel forward on DPR_ALGO_TILED (per-pose binning of single-slab grids; dpr_tiled.hip)
+bool tiled_channels_supported(int n_out, const int64_t* grid, int64_t P);
+size_t tiled_channels_workspace_bytes(size_t elem, int n_in, int n_out, const int64_t* grid, int64_t P,
+                                      int64_t B, int C);
+template <typename T, int NI, int NO>
+int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C, T* out,
+                          const T* points, const T* rot, const T* trans, const T* bg, const T* ow,
+                          const T* pw, void* ws, size_t ws_bytes);
+
 // DPR_ALGO_CHUNKED on 2-D grids: chunk-owned LDS tiles, pose loop inside (dpr_chunkown.hip)
 size_t chunkown_workspace_bytes(size_t elem, int op, unsigned flags, int n_in, int64_t P,
                                 int64_t B);

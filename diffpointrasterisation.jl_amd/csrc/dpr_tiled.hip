@@ -1721,14 +1721,18 @@ __device__ __forceinline__ void flush_tile(const double* __restrict__ acc, const
 }
 
 // ------------------------------------------------------------------ forward K4
-template <typename T, int NI, int NO, bool HAS_PW, bool W3>
+// WPL (multi-channel forward, raster_tiled_channels): the records carry no weight (4-word records
+// with the index), the weight of record r is wplane[r] -- one channel's plane of the weights in
+// binned order -- and maxpw points at that channel's max / min |weight| words.
+template <typename T, int NI, int NO, bool HAS_PW, bool W3, bool WPL = false>
 __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
     GridDesc<NO> gd, TileGeom<NO> tg, const RecT<T, W3>* __restrict__ rec,
     const WorkItem* __restrict__ items, const uint32_t* __restrict__ n_items,
     const uint32_t* __restrict__ tile_slab, const T* __restrict__ rot,
     const T* __restrict__ trans, const T* __restrict__ ow, const T* __restrict__ bg, int64_t b0,
     T* __restrict__ out, T* __restrict__ halo, T* __restrict__ ovf, int blocked,
-    const uint32_t* __restrict__ maxpw, int fixed) {
+    const uint32_t* __restrict__ maxpw, int fixed, const T* __restrict__ wplane) {
+    static_assert(!WPL || (HAS_PW && !W3), "weight planes go with 4-word records and point weights");
     constexpr int NVH = tile_voxels_halo<NO>();
     __shared__ double acc[NVH];
     // Everything the block needs from memory before it can touch its records is requested at
@@ -1773,10 +1777,13 @@ __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
     // kernel time, whatever the LDS atomic rate.
     constexpr int kPF = 2;
     RecT<T, W3> nxt[kPF];
+    T nxt_w[WPL ? kPF : 1];
 #pragma unroll
     for (int u = 0; u < kPF; ++u) {
         const uint32_t ru = r + u * step;
-        nxt[u] = rec[ru < r1 ? ru : (r1 > item.begin ? r1 - 1 : item.begin)];
+        const uint32_t rl = ru < r1 ? ru : (r1 > item.begin ? r1 - 1 : item.begin);
+        nxt[u] = rec[rl];
+        if constexpr (WPL) nxt_w[u] = wplane[rl];
     }
     lds_barrier();  // LDS phases only: prefetched records stay in flight
     // fp32 data: exact 64-bit fixed-point sums (see FixScale); fp64 data and non-finite weights: f64
@@ -1788,12 +1795,17 @@ __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
             RecT<T, W3> cur[kPF];
 #pragma unroll
             for (int u = 0; u < kPF; ++u) cur[u] = nxt[u];
+            if constexpr (WPL) {
+#pragma unroll
+                for (int u = 0; u < kPF; ++u) cur[u].v[3] = nxt_w[u];  // (the index slot: unused here)
+            }
             const uint32_t r_cur = r;
             r += kPF * step;
 #pragma unroll
             for (int u = 0; u < kPF; ++u) {
                 const uint32_t ru = r + u * step;
                 nxt[u] = rec[ru < r1 ? ru : r1 - 1];  // clamped prefetch (branch-free loop body)
+                if constexpr (WPL) nxt_w[u] = wplane[ru < r1 ? ru : r1 - 1];
             }
 #pragma unroll
             for (int u = 0; u < kPF; ++u)
@@ -3833,7 +3845,7 @@ int raster_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G,
                        (const WorkItem*)(wsb + pl.off_items),                                   \
                        (const uint32_t*)(wsb + pl.off_nitems),                                  \
                        (const uint32_t*)(wsb + pl.off_tslab), rot, trans, ow, bg, b, out, halo, \
-                       ovf, 2, (const uint32_t*)(wsb + pl.off_nitems) + 2, 1)
+                       ovf, 2, (const uint32_t*)(wsb + pl.off_nitems) + 2, 1, (const T*)nullptr)
         if (pl.local) {
             if (pw) DPR_LAUNCH_SPLAT_RUNS(true, false);
             else if (!keep) DPR_LAUNCH_SPLAT_RUNS(false, true);
@@ -4044,6 +4056,147 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
     return DPR_OK;
 }
 
+// ------------------------------------------------------------------ multi-channel forward
+// dpr_raster_channels_ex_* on DPR_ALGO_TILED: every pose is binned ONCE (count / scan / scatter, 4-word
+// records with the point index, slot map), then one splat + halo pass per channel writes that channel's
+// plane through the single-channel tile kernels.  The binning is the one a single-channel call of the
+// same shape without pose groups makes, so each plane is the single-channel result of its weights: the
+// fixed-point scale and the range guard are taken per channel, from that channel's weights of the binned
+// points.  Per-pose binning on a single-slab grid only (no pose groups, slabs or local binning).
+// (The binning asks for the slot map -- want_idx -- only because that is what keeps the point index in the
+// 4-word records on every scatter variant; the map itself is not read.)
+//   channel part of the workspace: w_sorted[C][P + 1] (channel-planar weights in binned order) | keys[C][2]
+
+// w_sorted[c][r] = point_weight[c, idx(r)] for every record r of the binning (tile_start[NT] of them; the
+// index rides in the 4-word record): the planes are written in binned order, coalesced, and a point's C
+// weights are gathered as one run -- a cache line per record for ALL channels, where scattering them through
+// the slot map (C scattered 4-byte stores per point) cost ~0.1 ms per channel at 10 M points.  Per channel
+// also the max / min non-zero |weight| of the binned points (keys[2c], keys[2c + 1], pre-zeroed; the words
+// k_tile_splat reads).
+template <typename T>
+__global__ __launch_bounds__(256) void k_channel_weights(int64_t P, int C, const T* __restrict__ pw,
+                                                        const Rec4<T>* __restrict__ rec,
+                                                        const uint32_t* __restrict__ n_rec,
+                                                        T* __restrict__ w_sorted, int64_t plane,
+                                                        uint32_t* __restrict__ keys) {
+    uint32_t key[kMaxChannels];
+#pragma unroll
+    for (int c = 0; c < kMaxChannels; ++c) key[c] = 0;
+    const int64_t n = *n_rec;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        uint32_t idx = slot_to_idx(rec[r].v[3]);
+        idx = idx < (uint64_t)P ? idx : 0u;  // (records of a complete binning always hold a point index)
+#pragma unroll
+        for (int c = 0; c < kMaxChannels; ++c) {
+            if (c < C) {
+                const T w = pw[(int64_t)idx * C + c];
+                w_sorted[(int64_t)c * plane + r] = w;
+                key[c] = wrange_merge(key[c], abs_key(w));
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < kMaxChannels; ++c)
+        if (c < C) publish_max_abs(keys + 2 * c, key[c]);  // (C is uniform: every lane calls)
+}
+
+static size_t channel_part_bytes(size_t elem, int64_t P, int C) {
+    return align_up((size_t)C * (size_t)(P + 1) * elem) + align_up((size_t)C * 2 * 4);
+}
+
+// the single-channel plan of one pose (what a call with B = 1 and no flags runs)
+static Plan channel_plan(size_t elem, int n_in, int n_out, const SlabCut& sc, int64_t P) {
+    return make_plan(elem, n_out, slab_max_tiles(sc), P, 1, 1, false, n_in, false, false, true);
+}
+
+bool tiled_channels_supported(int n_out, const int64_t* grid, int64_t P) {
+    SlabCut sc;
+    return P < ((int64_t)1 << 32) && grid_cut(n_out, grid, &sc) && sc.nslab == 1;
+}
+
+size_t tiled_channels_workspace_bytes(size_t elem, int n_in, int n_out, const int64_t* grid, int64_t P,
+                                      int64_t B, int C) {
+    if (!tiled_channels_supported(n_out, grid, P)) return (size_t)-1;
+    SlabCut sc;
+    (void)grid_cut(n_out, grid, &sc);
+    // (at least the single-channel DPR_ALGO_TILED workspace of the batch: a workspace sized for the
+    // single-channel call of the same shape plus the channel part always serves)
+    size_t base = tiled_workspace_bytes(elem, DPR_OP_RASTER, 0u, n_in, n_out, grid, P, B);
+    const size_t own = channel_plan(elem, n_in, n_out, sc, P).total;
+    if (own > base) base = own;
+    return base + channel_part_bytes(elem, P, C);
+}
+
+template <typename T, int NI, int NO>
+int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C, T* out,
+                          const T* points, const T* rot, const T* trans, const T* bg, const T* ow,
+                          const T* pw, void* ws_, size_t ws_bytes) {
+    if (!tiled_channels_supported(NO, grid, P))
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "DPR_ALGO_TILED with channels: per-pose binning of a grid of at most %d tiles and P < 2^32 "
+                    "only", kMaxTiles);
+    SlabCut sc;
+    (void)make_slab_cut<NO>(grid, &sc);
+    const Plan pl = channel_plan(sizeof(T), NI, NO, sc, P);
+    const size_t need = tiled_channels_workspace_bytes(sizeof(T), NI, NO, grid, P, B, C);
+    if (!ws_ || ws_bytes < need)
+        return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_TILED channel raster needs %zu workspace bytes, got %zu", need,
+                    ws_ ? ws_bytes : (size_t)0);
+    char* ws = (char*)ws_;
+    const size_t off_ch = need - channel_part_bytes(sizeof(T), P, C);
+    T* w_sorted = (T*)(ws + off_ch);
+    uint32_t* keys = (uint32_t*)(ws + off_ch + align_up((size_t)C * (size_t)(P + 1) * sizeof(T)));
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    const TileGeom<NO> tg = slab_geom<NO>(grid, sc, 0, true);
+    T* halo = (T*)(ws + pl.off_aux);
+    T* ovf = (T*)(ws + pl.off_aux + align_up((size_t)tg.NT * halo_count<NO>() * sizeof(T)));
+    for (int64_t b = 0; b < B; ++b) {
+        // the binning ignores the weights (4-word records carry the point index)
+        if (int rc = bin_points<T, NI, NO>(st, gd, tg, pl, ws, P, points, (const T*)nullptr, rot, trans, b, 1,
+                                           true, false, points, pw))
+            return rc;
+        if (pw) {
+            DPR_HIP(hipMemsetAsync(keys, 0, (size_t)C * 2 * 4, st));
+            int64_t blocks = (P + 255) / 256;
+            if (blocks > 4096) blocks = 4096;
+            if (blocks < 1) blocks = 1;
+            hipLaunchKernelGGL(k_channel_weights<T>, dim3((unsigned)blocks), dim3(256), 0, st, P, C, pw,
+                               (const Rec4<T>*)(ws + pl.off_rec), (const uint32_t*)(ws + pl.off_tile_start) + tg.NT,
+                               w_sorted, P + 1, keys);
+        }
+        // one pass per channel; the pose's parameters, background and plane are passed as pose 0
+        const T* rot_b = rot + b * (NO * NI);
+        const T* trans_b = trans + b * NO;
+        const T* ow_b = ow ? ow + b : nullptr;
+        for (int c = 0; c < C; ++c) {
+            const T* bg_c = bg ? bg + b * C + c : nullptr;
+            T* out_c = out + (b * C + c) * G;
+            if (pw)
+                hipLaunchKernelGGL((k_tile_splat<T, NI, NO, true, false, true>), dim3(pl.max_items),
+                                   dim3(kSplatThreads), 0, st, gd, tg, (const Rec4<T>*)(ws + pl.off_rec),
+                                   (const WorkItem*)(ws + pl.off_items), (const uint32_t*)(ws + pl.off_nitems),
+                                   (const uint32_t*)(ws + pl.off_tslab), rot_b, trans_b, ow_b, bg_c, (int64_t)0,
+                                   out_c, halo, ovf, 2, (const uint32_t*)(keys + 2 * c), 1,
+                                   (const T*)(w_sorted + (int64_t)c * (P + 1)));
+            else
+                hipLaunchKernelGGL((k_tile_splat<T, NI, NO, false, false>), dim3(pl.max_items),
+                                   dim3(kSplatThreads), 0, st, gd, tg, (const Rec4<T>*)(ws + pl.off_rec),
+                                   (const WorkItem*)(ws + pl.off_items), (const uint32_t*)(ws + pl.off_nitems),
+                                   (const uint32_t*)(ws + pl.off_tslab), rot_b, trans_b, ow_b, bg_c, (int64_t)0,
+                                   out_c, halo, ovf, 2, (const uint32_t*)(ws + pl.off_nitems) + 2, 1,
+                                   (const T*)nullptr);
+            stage_mark(st);
+            hipLaunchKernelGGL((k_halo_gather<T, NO>), dim3(tg.NT + kSplitGrid), dim3(256), 0, st, gd, tg,
+                               (const T*)halo, (const T*)ovf, (const uint32_t*)(ws + pl.off_tparts),
+                               (const uint32_t*)(ws + pl.off_tslab), (const uint32_t*)(ws + pl.off_split) + 1,
+                               (const uint32_t*)(ws + pl.off_split), bg_c, (int64_t)0, 1, out_c);
+            stage_mark(st);
+        }
+    }
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
 #define DPR_INST(T, NI, NO)                                                                       \
     template int raster_tiled<T, NI, NO>(hipStream_t, unsigned, const int64_t*, int64_t, int64_t, \
                                          int64_t, T*, const T*, const T*, const T*, const T*,     \
@@ -4051,7 +4204,10 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
     template int pullback_tiled<T, NI, NO>(hipStream_t, unsigned, const int64_t*, int64_t,        \
                                            int64_t, int64_t, const T*, const T*, const T*,        \
                                            const T*, const T*, const T*, T*, T*, T*, T*, T*, T*,  \
-                                           void*, size_t, Residual<T>);
+                                           void*, size_t, Residual<T>);                           \
+    template int raster_tiled_channels<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t,         \
+                                                  int64_t, int, T*, const T*, const T*, const T*,        \
+                                                  const T*, const T*, const T*, void*, size_t);
 DPR_INST(float, 2, 2)
 DPR_INST(float, 3, 3)
 DPR_INST(float, 3, 2)

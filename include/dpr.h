@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define DPR_VERSION 105 /* 0.1.5: + DPR_OP_RESIDUAL_PULLBACK; fp32 fixed-point sums fall back to f64 on wide weight ranges */
+#define DPR_VERSION 106 /* 0.1.6: + multi-channel entry points (dpr_raster_channels_ex_*, dpr_raster_pullback_channels_ex_*) */
 
 /* status codes */
 #define DPR_OK 0
@@ -127,7 +127,10 @@ extern "C" {
                               batches: the pullback from 16 poses of 3e6 points on (8 of 1e7, 64 of
                               1e6), the forward from 32 poses of a dense cloud of 3e6 points and
                               from 16 poses of a sparse one (P * 10 <= G) of 2e5 points.
-                              Correct for any point order. */
+                              Correct for any point order.
+   The multi-channel entry points (MULTI-CHANNEL below) run DPR_ALGO_ATOMIC or, for the forward,
+   DPR_ALGO_TILED: AUTO takes DPR_ALGO_TILED where the single-channel rule above prefers it for the shape
+   and the grid is one slab, DPR_ALGO_ATOMIC otherwise (always for the pullback). */
 
 /* SUMMATION ORDER.  The reference promises none for its float atomics (src/raster.jl:64) and sums
  * serially per pose on the CPU (src/raster_pullback.jl:39-72).  Here, per algorithm and output:
@@ -156,6 +159,25 @@ extern "C" {
  *                        LDS atomics, rounding level.  3-D                                              inside) adds its waves' sums with f64 LDS atomics in
  *                        chunk lists (sparse clouds): f64 LDS                                           arrival order: rounding level of f64
  *                        atomics + diverted global atomics
+ *
+ *   channels (dpr_raster_channels_ex_* / dpr_raster_pullback_channels_ex_*, see MULTI-CHANNEL below):
+ *   DPR_ALGO_TILED       fp32, fixed-point regime: every plane
+ *   (forward only)       is BIT-IDENTICAL to the single-channel
+ *                        DPR_ALGO_TILED call with point_weight[c, :]
+ *                        and background[c, :] for B = 1 -- same
+ *                        binning, same split of heavy tiles (> cap
+ *                        records), same per-channel scale and guard.
+ *                        Exceptions, at rounding level: a tile split
+ *                        into parts (its parts' records vary run to
+ *                        run in the single-channel call as well), and
+ *                        B > 1 where the single-channel call bins
+ *                        pose groups or cell-sorts the cloud (a
+ *                        different cap / record order of split tiles).
+ *                        A channel whose guard trips (or fp64 data):
+ *                        f64 LDS atomics, as the single-channel call
+ *   DPR_ALGO_ATOMIC      global float atomics, each contribution     one thread per point, poses in index   as DPR_ALGO_ATOMIC; the channels are
+ *                        the single-channel value: rounding level    order, channels folded per gather:     folded per gather before the sums:
+ *                                                                    bit-reproducible                       rounding level
  *
  * "Rounding level" = the differences any two summation orders of the same terms show in the
  * accumulation type; no output depends on the order beyond that.  The contributions themselves
@@ -390,6 +412,70 @@ int dpr_raster_residual_pullback_ex_f64(void *stream, int algo, unsigned flags, 
                                         const double *rotation, const double *translation,
                                         const double *out_weight, const double *point_weight,
                                         double *loss, double *ds_dpoints, double *ds_drotation,
+                                        double *ds_dtranslation, double *ds_dbackground,
+                                        double *ds_dout_weight, double *ds_dpoint_weight,
+                                        void *workspace, size_t workspace_bytes);
+
+/* ---- MULTI-CHANNEL: C weights per point (1 <= C <= 16) ---------------------------------------
+ * For channel c and pose b:
+ *     out[i.., c, b] = background[c, b] + out_weight[b] * sum_p point_weight[c, p] * voxel_weight(i..; R_b p + t_b)
+ * i.e. every plane is what dpr_raster_* returns for that channel's weights, and the gradients decompose
+ * the same way: ds_dpoints, ds_drotation, ds_dtranslation, ds_dout_weight are the SUMS over c of the
+ * single-channel results, ds_dpoint_weight[c, :] and ds_dbackground[c, b] the single-channel results of
+ * channel c.  Layouts (column-major like the rest of this header):
+ *   out, ds_dout                      (n_1, .., n_N, C, B): plane (c, b) is contiguous at (b * C + c) * G
+ *                                     (memory of a contiguous NCHW / NCDHW (B, C, n_N, .., n_1) tensor)
+ *   point_weight, ds_dpoint_weight    C x P, channel fastest (Vector{SVector{C,T}}, AoS like points); NULL => 1
+ *   background, ds_dbackground        C x B; background NULL => 0
+ *   out_weight                        B (one scalar per pose, shared by the channels); NULL => 1
+ *   everything else                   as for dpr_raster_ex_* / dpr_raster_pullback_ex_*
+ * Algorithms.  Forward: DPR_ALGO_ATOMIC for every (n_in, n_out) (the geometry of a (point, pose) is computed
+ * once, C atomics per neighbour); DPR_ALGO_TILED for (2,2), (3,3), (3,2) on grids of at most 32768 tiles
+ * (no slabs) with P < 2^32: every pose is binned ONCE, the scatter's slot map places the C weights
+ * channel-planar in binned order, then one splat + halo pass per channel (no pose groups, no local binning
+ * -- DPR_FLAG_COHERENT_POINTS is accepted and ignored).  Pullback: DPR_ALGO_ATOMIC (one gather pass serves
+ * all channels).  AUTO (dpr_resolve_algo_channels): the forward takes DPR_ALGO_TILED where the single-channel
+ * rule prefers DPR_ALGO_TILED for the shape (tiled_preferred: the point density per tile) and the channel
+ * path supports it, DPR_ALGO_ATOMIC otherwise; the pullback always DPR_ALGO_ATOMIC.
+ * Errors (status, message, nothing launched): C outside 1..16 and a NULL required pointer
+ * DPR_ERR_INVALID_ARG; DPR_ALGO_CHUNKED, DPR_ALGO_TILED where unsupported (other dimension pairs, slabbed
+ * grids, any pullback), the KEEP / REUSE flags and DPR_OP_RESIDUAL_PULLBACK DPR_ERR_UNSUPPORTED_ALGO.
+ * DPR_FLAG_NO_POINT_WEIGHT_GRAD keeps its meaning; DPR_FLAG_MAX_POSE_GROUP is accepted (the channel path
+ * forms no pose groups).  Workspace: dpr_workspace_bytes_channels_ex_* with the call's op, algo and flags
+ * ((size_t)-1 on invalid arguments; 0 for DPR_ALGO_ATOMIC; for DPR_ALGO_TILED at least the single-channel
+ * DPR_ALGO_TILED workspace of the shape plus C * (P + 1) * sizeof(T)). */
+int dpr_resolve_algo_channels(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B,
+                              int64_t C);
+size_t dpr_workspace_bytes_channels_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                           const int64_t *grid, int64_t P, int64_t B, int64_t C);
+size_t dpr_workspace_bytes_channels_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                           const int64_t *grid, int64_t P, int64_t B, int64_t C);
+int dpr_raster_channels_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                               const int64_t *grid, int64_t P, int64_t B, int64_t C, float *out,
+                               const float *points, const float *rotation, const float *translation,
+                               const float *background, const float *out_weight,
+                               const float *point_weight, void *workspace, size_t workspace_bytes);
+int dpr_raster_channels_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                               const int64_t *grid, int64_t P, int64_t B, int64_t C, double *out,
+                               const double *points, const double *rotation,
+                               const double *translation, const double *background,
+                               const double *out_weight, const double *point_weight, void *workspace,
+                               size_t workspace_bytes);
+int dpr_raster_pullback_channels_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                        const int64_t *grid, int64_t P, int64_t B, int64_t C,
+                                        const float *ds_dout, const float *points,
+                                        const float *rotation, const float *translation,
+                                        const float *out_weight, const float *point_weight,
+                                        float *ds_dpoints, float *ds_drotation,
+                                        float *ds_dtranslation, float *ds_dbackground,
+                                        float *ds_dout_weight, float *ds_dpoint_weight,
+                                        void *workspace, size_t workspace_bytes);
+int dpr_raster_pullback_channels_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                        const int64_t *grid, int64_t P, int64_t B, int64_t C,
+                                        const double *ds_dout, const double *points,
+                                        const double *rotation, const double *translation,
+                                        const double *out_weight, const double *point_weight,
+                                        double *ds_dpoints, double *ds_drotation,
                                         double *ds_dtranslation, double *ds_dbackground,
                                         double *ds_dout_weight, double *ds_dpoint_weight,
                                         void *workspace, size_t workspace_bytes);
