@@ -13,6 +13,8 @@ from .timing import stage_times
 from .autograd import raster_ad
 from .channels import (empty_channel_grid, raster_channels, raster_channels_, raster_channels_ad,
                        raster_pullback_channels_, resolve_algo_channels, workspace_bytes_channels)
+from .sample import (SamplePullbackResult, resolve_algo_sample, sample, sample_, sample_ad, sample_pullback_,
+                     workspace_bytes_sample)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -24,4 +26,6 @@ __all__ = [
     "raster_point_sharded", "raster_pullback_point_sharded_",
     "raster_channels", "raster_channels_", "raster_pullback_channels_", "raster_channels_ad", "empty_channel_grid",
     "resolve_algo_channels", "workspace_bytes_channels",
+    "sample", "sample_", "sample_pullback_", "sample_ad", "SamplePullbackResult", "resolve_algo_sample",
+    "workspace_bytes_sample",
 ]

@@ -55,6 +55,8 @@ EXPORTS = [
     "dpr_resolve_algo_channels", "dpr_workspace_bytes_channels_ex_f32", "dpr_workspace_bytes_channels_ex_f64",
     "dpr_raster_channels_ex_f32", "dpr_raster_channels_ex_f64",
     "dpr_raster_pullback_channels_ex_f32", "dpr_raster_pullback_channels_ex_f64",
+    "dpr_resolve_algo_sample", "dpr_workspace_bytes_sample_ex_f32", "dpr_workspace_bytes_sample_ex_f64",
+    "dpr_sample_ex_f32", "dpr_sample_ex_f64", "dpr_sample_pullback_ex_f32", "dpr_sample_pullback_ex_f64",
 ]
 
 _lib = None
@@ -154,6 +156,20 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, f"dpr_raster_pullback_channels_ex_{suf}")
         f.restype = i
         f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 12 + [vp, sz]
+    L.dpr_resolve_algo_sample.restype = i
+    L.dpr_resolve_algo_sample.argtypes = [i, i, i, vp, i64, i64]
+    for suf in ("f32", "f64"):
+        f = getattr(L, f"dpr_workspace_bytes_sample_ex_{suf}")
+        f.restype = sz
+        f.argtypes = [i, i, ctypes.c_uint, i, i, vp, i64, i64]
+        # stream, algo, flags, n_in, n_out, grid, P, B, values, image, points, rot, trans, ws, ws_bytes
+        f = getattr(L, f"dpr_sample_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64] + [vp] * 5 + [vp, sz]
+        # ..., ds_dvalues, image, points, rot, trans, ds_dimage, ds_dpoints, ds_drot, ds_dtrans, ws, ws_bytes
+        f = getattr(L, f"dpr_sample_pullback_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64] + [vp] * 9 + [vp, sz]
     L.dpr_comm_unique_id.restype = i
     L.dpr_comm_unique_id.argtypes = [vp, sz]
     L.dpr_comm_init.restype = i

@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define DPR_VERSION 106 /* 0.1.6: + multi-channel entry points (dpr_raster_channels_ex_*, dpr_raster_pullback_channels_ex_*) */
+#define DPR_VERSION 107 /* 0.1.7: + point sampling (dpr_sample_ex_*, dpr_sample_pullback_ex_*) */
 
 /* status codes */
 #define DPR_OK 0
@@ -130,7 +130,9 @@ extern "C" {
                               Correct for any point order.
    The multi-channel entry points (MULTI-CHANNEL below) run DPR_ALGO_ATOMIC or, for the forward,
    DPR_ALGO_TILED: AUTO takes DPR_ALGO_TILED where the single-channel rule above prefers it for the shape
-   and the grid is one slab, DPR_ALGO_ATOMIC otherwise (always for the pullback). */
+   and the grid is one slab, DPR_ALGO_ATOMIC otherwise (always for the pullback).
+   The sampling entry points (SAMPLING below) run DPR_ALGO_ATOMIC for the forward; their pullback takes
+   DPR_ALGO_TILED where the single-pose forward of the shape would, DPR_ALGO_ATOMIC otherwise. */
 
 /* SUMMATION ORDER.  The reference promises none for its float atomics (src/raster.jl:64) and sums
  * serially per pose on the CPU (src/raster_pullback.jl:39-72).  Here, per algorithm and output:
@@ -479,6 +481,75 @@ int dpr_raster_pullback_channels_ex_f64(void *stream, int algo, unsigned flags, 
                                         double *ds_dtranslation, double *ds_dbackground,
                                         double *ds_dout_weight, double *ds_dpoint_weight,
                                         void *workspace, size_t workspace_bytes);
+
+/* ---- SAMPLING: N-linear interpolation of images at the transformed points ---------------------
+ * The transpose of dpr_raster_* with respect to the point weights.  For pose b (R_b, t_b):
+ *     values[p, b] = sum over the 2^N neighbours s that lie in the grid of
+ *                    voxel_weight(deltas(R_b p + t_b), s) * image[ref(p, b) + shift_s, b]
+ *     values[p, b] = 0 where the point is rejected (an axis with no in-range neighbour, NaN / Inf)
+ * with exactly the cell choice, deltas, neighbour weights and drop rules of dpr_raster_* (the reference's
+ * src/raster.jl:53-64, 85-108).  So
+ *     sum_v (raster(pw) - background)[v, b] * image[v, b] = out_weight[b] * sum_p pw[p] * values[p, b]
+ * and for B = 1 `values` is the ds_dpoint_weight of dpr_raster_pullback_* with ds_dout = image, out_weight = 1
+ * and point_weight = 1.
+ * The pullback takes ds_dvalues (P x B) and writes
+ *   ds_dimage[.., b]     dpr_raster_* of pose b with point_weight = ds_dvalues[:, b], background 0, out_weight 1
+ *   ds_dpoints           sum over b of the reference's point gradient (src/raster_pullback.jl:46-70) with
+ *                        ds_dout = image_b, out_weight = 1, point_weight = ds_dvalues[:, b]
+ *   ds_drotation[b], ds_dtranslation[b]   the per-pose sums of that same formula
+ * (the reference's piecewise derivative of the interpolant, the one its pullback uses).
+ * Layouts: values, ds_dvalues   P x B, point index fastest (pose b is the contiguous column at b * P);
+ *          image, ds_dimage     (n_1, .., n_N, B) as `out` of dpr_raster_ex_*;
+ *          everything else      as for dpr_raster_ex_* / dpr_raster_pullback_ex_*.
+ * op: DPR_OP_RASTER (the forward) or DPR_OP_PULLBACK.  All 16 (n_in, n_out) with 1 <= n_in, n_out <= 4.
+ * Outputs are overwritten, not accumulated.  Any pullback output may be NULL (not wanted); at least one must be
+ * given; `image` may be NULL when only ds_dimage is wanted.
+ * Algorithms.  Forward: DPR_ALGO_ATOMIC (= AUTO): one thread per point, the point in registers across a slice of
+ * the poses, all 2^N gathers issued before the first use, the value stored coalesced, no atomics; workspace 0.
+ * Pullback DPR_ALGO_ATOMIC: one fused kernel per (point, pose slice) forms from the same gathers the point
+ * gradient, g * voxel_weight into ds_dimage (global float atomics) and the per-pose sums (wave -> block -> one
+ * atomic per scalar per block); workspace 0.  Pullback DPR_ALGO_TILED, for (2,2), (3,3), (3,2): the same kernel
+ * without the image atomics, then ds_dimage pose by pose from the tiled forward with B = 1, point_weight =
+ * ds_dvalues[:, b], background and out_weight NULL -- each plane is what dpr_raster_ex_*(DPR_ALGO_TILED) returns
+ * for those weights, and exactly as reproducible as that call (fp32: bit-identical where it sums exactly --
+ * fixed point within its range guard, 3-D grids -- and at rounding level where it does not); workspace: that of
+ * dpr_raster_ex_*(DPR_ALGO_TILED) for (grid, P, B = 1).  DPR_FLAG_COHERENT_POINTS is passed on to that forward;
+ * the other flags except KEEP / REUSE are ignored.  AUTO (dpr_resolve_algo_sample): the pullback takes
+ * DPR_ALGO_TILED where dpr_resolve_algo(DPR_OP_RASTER, .., P, 1) returns DPR_ALGO_TILED and the pair has it,
+ * DPR_ALGO_ATOMIC otherwise.
+ * Summation order.  values: over the neighbours s = 0 .. 2^N - 1 in order, as in dpr_raster_pullback_*.  Point
+ * gradients: per pose in point_backward's order, summed over the poses of a slice in pose order, slices added
+ * atomically.  Per-pose sums and the ATOMIC ds_dimage: global atomics, unordered.
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): dimensions outside 1..4
+ * DPR_ERR_UNSUPPORTED_DIMS; a bad op, a NULL required pointer or all outputs NULL DPR_ERR_INVALID_ARG;
+ * DPR_ALGO_TILED for the forward or for another pair, DPR_ALGO_CHUNKED and the KEEP / REUSE flags
+ * DPR_ERR_UNSUPPORTED_ALGO; a workspace smaller than dpr_workspace_bytes_sample_ex_* DPR_ERR_WORKSPACE.
+ * dpr_workspace_bytes_sample_ex_* returns (size_t)-1 on invalid arguments. */
+int dpr_resolve_algo_sample(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_sample_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                         const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_sample_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                         const int64_t *grid, int64_t P, int64_t B);
+int dpr_sample_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                      int64_t P, int64_t B, float *values, const float *image, const float *points,
+                      const float *rotation, const float *translation, void *workspace,
+                      size_t workspace_bytes);
+int dpr_sample_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                      int64_t P, int64_t B, double *values, const double *image, const double *points,
+                      const double *rotation, const double *translation, void *workspace,
+                      size_t workspace_bytes);
+int dpr_sample_pullback_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                               const int64_t *grid, int64_t P, int64_t B, const float *ds_dvalues,
+                               const float *image, const float *points, const float *rotation,
+                               const float *translation, float *ds_dimage, float *ds_dpoints,
+                               float *ds_drotation, float *ds_dtranslation, void *workspace,
+                               size_t workspace_bytes);
+int dpr_sample_pullback_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                               const int64_t *grid, int64_t P, int64_t B, const double *ds_dvalues,
+                               const double *image, const double *points, const double *rotation,
+                               const double *translation, double *ds_dimage, double *ds_dpoints,
+                               double *ds_drotation, double *ds_dtranslation, void *workspace,
+                               size_t workspace_bytes);
 
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
