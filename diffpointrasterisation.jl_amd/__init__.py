@@ -15,6 +15,7 @@ from .channels import (empty_channel_grid, raster_channels, raster_channels_, ra
                        raster_pullback_channels_, resolve_algo_channels, workspace_bytes_channels)
 from .sample import (SamplePullbackResult, resolve_algo_sample, sample, sample_, sample_ad, sample_pullback_,
                      workspace_bytes_sample)
+from .jvp import raster_jvp, raster_jvp_, resolve_algo_jvp, workspace_bytes_jvp
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -28,4 +29,5 @@ __all__ = [
     "resolve_algo_channels", "workspace_bytes_channels",
     "sample", "sample_", "sample_pullback_", "sample_ad", "SamplePullbackResult", "resolve_algo_sample",
     "workspace_bytes_sample",
+    "raster_jvp", "raster_jvp_", "resolve_algo_jvp", "workspace_bytes_jvp",
 ]

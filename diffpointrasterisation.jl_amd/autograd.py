@@ -15,11 +15,16 @@ where DPR_ALGO_AUTO keeps every pose's binning -- keeps the forward's binning (o
 in a private workspace and the first backward pass reuses it (DPR_FLAG_KEEP_BINNING /
 DPR_FLAG_REUSE_BINNING); it is consumed by that pass, any further backward pass through the same
 node re-bins.
+
+Forward mode (torch.autograd.forward_ad dual tensors) goes through `jvp`: `raster_jvp` with one tangent, on the
+caller's algorithm where the JVP has it (atomic, tiled) and on AUTO otherwise.  It does not touch the forward's
+workspace, so the reverse mode is unchanged.
 """
 from __future__ import annotations
 
 import torch
 
+from .jvp import raster_jvp, workspace_bytes_jvp
 from .interface import (empty_grid, raster_, raster_pullback_, resolve_algo, sharing_effective,
                         workspace_bytes)
 
@@ -29,6 +34,7 @@ class _RasterFn(torch.autograd.Function):
     def forward(ctx, grid_size, algo, points, rotation, translation, background, out_weight,
                 point_weight):
         grid_size = tuple(int(g) for g in grid_size)
+        algo_in = algo
         single = rotation.ndim == 2
         batch = None if single else rotation.shape[0]
         dtype = torch.promote_types(points.dtype, torch.promote_types(rotation.dtype,
@@ -67,9 +73,11 @@ class _RasterFn(torch.autograd.Function):
                 algo = f
         raster_(out, points, rotation, translation, background, out_weight, point_weight,
                 algo=algo, workspace=ws, keep_binning=ws is not None)
-        ctx.save_for_backward(points, rotation, translation,
-                              *[t for t in (background, out_weight, point_weight)
-                                if isinstance(t, torch.Tensor)])
+        saved = (points, rotation, translation,
+                 *[t for t in (background, out_weight, point_weight) if isinstance(t, torch.Tensor)])
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        ctx.grid_size, ctx.caller_algo = grid_size, algo_in
         ctx.opt = tuple(t if not isinstance(t, torch.Tensor) else None
                         for t in (background, out_weight, point_weight))
         ctx.opt_is_tensor = tuple(isinstance(t, torch.Tensor)
@@ -110,10 +118,30 @@ class _RasterFn(torch.autograd.Function):
         return tuple(grads)
 
 
+    @staticmethod
+    def jvp(ctx, _grid_t, _algo_t, points_t, rotation_t, translation_t, background_t, out_weight_t,
+            point_weight_t):
+        saved = list(ctx.saved_tensors)
+        points, rotation, translation = saved[:3]
+        rest = saved[3:]
+        opt = [rest.pop(0) if ctx.opt_is_tensor[k] else ctx.opt[k] for k in range(3)]
+        P, n_in = points.shape
+        B = 1 if rotation.ndim == 2 else rotation.shape[0]
+        algo = ctx.caller_algo if ctx.caller_algo in ("atomic", "tiled") else "auto"
+        if algo == "tiled":
+            try:
+                workspace_bytes_jvp(ctx.grid_size, P, B, n_in, 1, points.dtype, "tiled")
+            except Exception:  # (a shape the tiled JVP does not cover: AUTO picks for it)
+                algo = "auto"
+        return raster_jvp(ctx.grid_size, points, rotation, translation, *opt, points_dot=points_t,
+                          rotation_dot=rotation_t, translation_dot=translation_t, background_dot=background_t,
+                          out_weight_dot=out_weight_t, point_weight_dot=point_weight_t, algo=algo)
+
+
 def raster_ad(grid_size, points, rotation, translation, background=None, out_weight=None,
               point_weight=None, *, algo: str = "auto") -> torch.Tensor:
-    """Differentiable `raster` (torch autograd).  Tensor arguments may require grad; Python
-    scalars / None for the optional arguments are constants, as FillArrays defaults are for
-    the rrule.  Same shapes and errors as `raster`."""
+    """Differentiable `raster` (torch autograd, reverse and forward mode).  Tensor arguments may
+    require grad or carry a forward-mode tangent; Python scalars / None for the optional arguments
+    are constants, as FillArrays defaults are for the rrule.  Same shapes and errors as `raster`."""
     return _RasterFn.apply(tuple(grid_size), algo, points, rotation, translation, background,
                            out_weight, point_weight)

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "dpr_device.h"
+#include "dpr_jvp.h"
 
 namespace dpr {
 
@@ -41,6 +42,13 @@ template <typename T, int NI, int NO>
 int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C, T* out,
                           const T* points, const T* rot, const T* trans, const T* bg, const T* ow,
                           const T* pw, void* ws, size_t ws_bytes);
+
+// forward-mode derivative on DPR_ALGO_TILED (the channel forward's per-pose binning; dpr_tiled.hip)
+size_t tiled_jvp_workspace_bytes(size_t elem, int n_in, int n_out, const int64_t* grid, int64_t P);
+template <typename T, int NI, int NO>
+int raster_tiled_jvp(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
+                     const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan,
+                     const T* bg_dot, void* ws, size_t ws_bytes);
 
 // DPR_ALGO_CHUNKED on 2-D grids: chunk-owned LDS tiles, pose loop inside (dpr_chunkown.hip)
 size_t chunkown_workspace_bytes(size_t elem, int op, unsigned flags, int n_in, int64_t P,

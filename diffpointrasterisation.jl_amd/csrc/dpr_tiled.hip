@@ -41,6 +41,7 @@
 
 #include "../../include/dpr.h"
 #include "dpr_device.h"
+#include "dpr_jvp.h"
 #include "dpr_tiled.h"
 
 namespace dpr {
@@ -1660,6 +1661,55 @@ __device__ __forceinline__ void splat_record(const R& rc, bool active, const Pos
     }
 }
 
+// One record of the forward-mode derivative (raster_tiled_jvp): splat_record with cf = {a, b_0, .., b_{N-1}} of
+// the record's (point, pose, tangent) in place of the weight, the contributions dpr_jvp.h's deposits.  (A copy of
+// splat_record's cell logic: sharing it through a value functor cost the existing instantiations a register.)
+template <bool FIX, typename T, int NI, int NO, typename R>
+__device__ __forceinline__ void splat_record_jvp(const R& rc, const Rec4<T>& cf, bool active,
+                                                 const Pose<T, NI, NO>& ps, const GridDesc<NO>& gd,
+                                                 const int (&x0)[NO], double* __restrict__ acc, const FixScale& fs) {
+    T pt[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) pt[j] = rc.v[j];
+    int ref0[NO];
+    T dlo[NO];
+    ref_and_deltas<T, NI, NO>(pt, ps, gd, ref0, dlo);  // in range by construction
+    T bc[NO];
+#pragma unroll
+    for (int n = 0; n < NO; ++n) bc[n] = cf.v[1 + n];
+    int lb[NO];
+    bool low_ok[NO];
+#pragma unroll
+    for (int d = 0; d < NO; ++d) {
+        lb[d] = ref0[d] - x0[d];
+        lb[d] = lb[d] < -1 ? -1 : (lb[d] > TileDims<NO>::T[d] - 1 ? TileDims<NO>::T[d] - 1 : lb[d]);
+        low_ok[d] = lb[d] >= 0;
+    }
+    bool interior = true;
+#pragma unroll
+    for (int d = 0; d < NO; ++d) interior = interior && low_ok[d];
+    if (active && interior) {
+        double* base = &acc[lds_index<NO>(lb)];
+#pragma unroll
+        for (int s = 0; s < (1 << NO); ++s)
+            cell_add<FIX, T>(base + nbr_lds_offset<NO>(s), jvp_deposit<T, NO>(cf.v[0], bc, dlo, s), fs);
+    } else if (active) {  // a lower neighbour at -1: only at the low faces of the grid
+#pragma unroll
+        for (int s = 0; s < (1 << NO); ++s) {
+            int l[NO];
+            bool ok = true;
+#pragma unroll
+            for (int d = 0; d < NO; ++d) {
+                const int sd = (s >> d) & 1;
+                ok = ok && (sd || low_ok[d]);
+                l[d] = (sd || low_ok[d]) ? lb[d] + sd : 0;
+            }
+            const T v = jvp_deposit<T, NO>(cf.v[0], bc, dlo, s);
+            cell_add<FIX, T>(&acc[lds_index<NO>(l)], ok ? v : T(0), fs);
+        }
+    }
+}
+
 // Flush of a forward tile kernel's LDS tile, one row (TX + 1 cells along x) per wave pass: the row's y / z
 // coordinates, bounds and base offsets are wave-uniform, a lane only adds its x.  Owned rows leave as
 // out = background + acc (plain non-temporal stores of TX contiguous values); the rows of the upper y / z
@@ -1724,7 +1774,10 @@ __device__ __forceinline__ void flush_tile(const double* __restrict__ acc, const
 // WPL (multi-channel forward, raster_tiled_channels): the records carry no weight (4-word records
 // with the index), the weight of record r is wplane[r] -- one channel's plane of the weights in
 // binned order -- and maxpw points at that channel's max / min |weight| words.
-template <typename T, int NI, int NO, bool HAS_PW, bool W3, bool WPL = false>
+// JVP (forward-mode derivative, raster_tiled_jvp): wplane holds one coefficient record {a, b_0, .., b_{N-1}}
+// (Rec4<T>) per binned record of one tangent, the contributions are dpr_jvp.h's deposits, and maxpw points at
+// the max / min of their bounds |a| + sum |b_n|; out_weight is not passed (1).
+template <typename T, int NI, int NO, bool HAS_PW, bool W3, bool WPL = false, bool JVP = false>
 __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
     GridDesc<NO> gd, TileGeom<NO> tg, const RecT<T, W3>* __restrict__ rec,
     const WorkItem* __restrict__ items, const uint32_t* __restrict__ n_items,
@@ -1733,6 +1786,7 @@ __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
     T* __restrict__ out, T* __restrict__ halo, T* __restrict__ ovf, int blocked,
     const uint32_t* __restrict__ maxpw, int fixed, const T* __restrict__ wplane) {
     static_assert(!WPL || (HAS_PW && !W3), "weight planes go with 4-word records and point weights");
+    static_assert(!JVP || (HAS_PW && !W3 && !WPL), "coefficient records go with 4-word records");
     constexpr int NVH = tile_voxels_halo<NO>();
     __shared__ double acc[NVH];
     // Everything the block needs from memory before it can touch its records is requested at
@@ -1778,12 +1832,15 @@ __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
     constexpr int kPF = 2;
     RecT<T, W3> nxt[kPF];
     T nxt_w[WPL ? kPF : 1];
+    Rec4<T> nxt_c[JVP ? kPF : 1];
+    const Rec4<T>* const coef = (const Rec4<T>*)wplane;
 #pragma unroll
     for (int u = 0; u < kPF; ++u) {
         const uint32_t ru = r + u * step;
         const uint32_t rl = ru < r1 ? ru : (r1 > item.begin ? r1 - 1 : item.begin);
         nxt[u] = rec[rl];
         if constexpr (WPL) nxt_w[u] = wplane[rl];
+        if constexpr (JVP) nxt_c[u] = coef[rl];
     }
     lds_barrier();  // LDS phases only: prefetched records stay in flight
     // fp32 data: exact 64-bit fixed-point sums (see FixScale); fp64 data and non-finite weights: f64
@@ -1799,6 +1856,11 @@ __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
 #pragma unroll
                 for (int u = 0; u < kPF; ++u) cur[u].v[3] = nxt_w[u];  // (the index slot: unused here)
             }
+            Rec4<T> cur_c[JVP ? kPF : 1];
+            if constexpr (JVP) {
+#pragma unroll
+                for (int u = 0; u < kPF; ++u) cur_c[u] = nxt_c[u];
+            }
             const uint32_t r_cur = r;
             r += kPF * step;
 #pragma unroll
@@ -1806,10 +1868,15 @@ __global__ __launch_bounds__(kSplatThreads) void k_tile_splat(
                 const uint32_t ru = r + u * step;
                 nxt[u] = rec[ru < r1 ? ru : r1 - 1];  // clamped prefetch (branch-free loop body)
                 if constexpr (WPL) nxt_w[u] = wplane[ru < r1 ? ru : r1 - 1];
+                if constexpr (JVP) nxt_c[u] = coef[ru < r1 ? ru : r1 - 1];
             }
 #pragma unroll
-            for (int u = 0; u < kPF; ++u)
-                splat_record<FIX, T, NI, NO, HAS_PW>(cur[u], r_cur + u * step < r1, ps, gd, x0, acc, fs);
+            for (int u = 0; u < kPF; ++u) {
+                if constexpr (JVP)
+                    splat_record_jvp<FIX, T, NI, NO>(cur[u], cur_c[u], r_cur + u * step < r1, ps, gd, x0, acc, fs);
+                else
+                    splat_record<FIX, T, NI, NO, HAS_PW>(cur[u], r_cur + u * step < r1, ps, gd, x0, acc, fs);
+            }
         }
     };
     if (fs.mul != 0.0) record_loop(std::true_type{});  // (uniform)
@@ -4197,6 +4264,124 @@ int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_
     return DPR_OK;
 }
 
+// dpr_raster_jvp_ex_* on DPR_ALGO_TILED: every pose is binned ONCE as for the channel forward (the one-pose plan,
+// 4-word records with the point index), then per tangent k
+//   k_jvp_coeffs   one pass in binned order: the coefficient record {a, b_0, .., b_{N-1}} of every binned record
+//                  (dpr_jvp.h) and the max / min non-zero bound |a| + sum |b_n| of the tangent's records
+//   k_tile_splat   (JVP) the deposits into the LDS tiles: exact fixed-point sums for fp32 with the scale and the
+//                  2^10 range guard taken from those bounds (f64 atomics where the guard trips), the background tangent in the flush
+//   k_halo_gather  the halos, the background tangent again for the low-face cells
+// into plane (b, k) of out_dot.
+//   jvp part of the workspace: coef[P + 1] (Rec4<T>) | keys[2]
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(256) void k_jvp_coeffs(GridDesc<NO> gd, int64_t P, const Rec4<T>* __restrict__ rec,
+                                                    const uint32_t* __restrict__ n_rec, const T* __restrict__ rot_b,
+                                                    const T* __restrict__ trans_b, const T* __restrict__ ow_b,
+                                                    const T* __restrict__ pw, JvpTangents<T> tk,
+                                                    const T* __restrict__ rot_dot_kb, const T* __restrict__ trans_dot_kb,
+                                                    const T* __restrict__ ow_dot_kb, Rec4<T>* __restrict__ coef,
+                                                    uint32_t* __restrict__ keys) {
+    const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot_b, trans_b, ow_b, 0);
+    const JvpPose<T, NI, NO> tp = load_jvp_pose<T, NI, NO>(rot_dot_kb, trans_dot_kb, ow_dot_kb, 0);
+    uint32_t key = 0;
+    const int64_t n = *n_rec;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        const Rec4<T> rc = rec[r];
+        uint32_t idx = slot_to_idx(rc.v[3]);
+        idx = idx < (uint64_t)P ? idx : 0u;  // (records of a complete binning always hold a point index)
+        T pt[NI];
+#pragma unroll
+        for (int j = 0; j < NI; ++j) pt[j] = rc.v[j];
+        const T pwv = pw ? pw[idx] : T(1);
+        T pd[NI], pwd;
+        load_jvp_point<T, NI>(tk.points, tk.pw, idx, pd, pwd);
+        T a, bc[NO];
+        jvp_coeffs<T, NI, NO>(pt, pwv, pd, pwd, ps, tp, gd, a, bc);
+        Rec4<T> c;
+        c.v[0] = a;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) c.v[1 + d] = d < NO ? bc[d < NO ? d : 0] : T(0);
+        coef[r] = c;
+        key = wrange_merge(key, abs_key(jvp_bound<T, NO>(a, bc)));
+    }
+    publish_max_abs(keys, key);  // (every lane gets here)
+}
+
+static size_t jvp_part_bytes(size_t elem, int64_t P) {
+    return align_up((size_t)(P + 1) * 4 * elem) + align_up(2 * 4);
+}
+
+size_t tiled_jvp_workspace_bytes(size_t elem, int n_in, int n_out, const int64_t* grid, int64_t P) {
+    if (!tiled_channels_supported(n_out, grid, P)) return (size_t)-1;
+    SlabCut sc;
+    (void)grid_cut(n_out, grid, &sc);
+    return align_up(channel_plan(elem, n_in, n_out, sc, P).total) + jvp_part_bytes(elem, P);
+}
+
+template <typename T, int NI, int NO>
+int raster_tiled_jvp(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
+                     const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan,
+                     const T* bg_dot, void* ws_, size_t ws_bytes) {
+    if (!tiled_channels_supported(NO, grid, P))
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "DPR_ALGO_TILED JVP: per-pose binning of a grid of at most %d tiles and P < 2^32 only", kMaxTiles);
+    SlabCut sc;
+    (void)make_slab_cut<NO>(grid, &sc);
+    const Plan pl = channel_plan(sizeof(T), NI, NO, sc, P);
+    const size_t need = tiled_jvp_workspace_bytes(sizeof(T), NI, NO, grid, P);
+    if (!ws_ || ws_bytes < need)
+        return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_TILED JVP needs %zu workspace bytes, got %zu", need,
+                    ws_ ? ws_bytes : (size_t)0);
+    char* ws = (char*)ws_;
+    const size_t off_jvp = need - jvp_part_bytes(sizeof(T), P);
+    Rec4<T>* coef = (Rec4<T>*)(ws + off_jvp);
+    uint32_t* keys = (uint32_t*)(ws + off_jvp + align_up((size_t)(P + 1) * 4 * sizeof(T)));
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    const TileGeom<NO> tg = slab_geom<NO>(grid, sc, 0, true);
+    T* halo = (T*)(ws + pl.off_aux);
+    T* ovf = (T*)(ws + pl.off_aux + align_up((size_t)tg.NT * halo_count<NO>() * sizeof(T)));
+    int64_t blocks = (P + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    for (int64_t b = 0; b < B; ++b) {
+        // the binning ignores the weights (4-word records carry the point index)
+        if (int rc = bin_points<T, NI, NO>(st, gd, tg, pl, ws, P, points, (const T*)nullptr, rot, trans, b, 1,
+                                           true, false, points, pw))
+            return rc;
+        const T* rot_b = rot + b * (NO * NI);
+        const T* trans_b = trans + b * NO;
+        const T* ow_b = ow ? ow + b : nullptr;
+        for (int k = 0; k < K; ++k) {
+            const int64_t kb = (int64_t)k * B + b;
+            JvpTangents<T> tk = tan;
+            tk.points = tan.points ? tan.points + (int64_t)k * P * NI : nullptr;
+            tk.pw = tan.pw ? tan.pw + (int64_t)k * P : nullptr;
+            DPR_HIP(hipMemsetAsync(keys, 0, 2 * 4, st));
+            hipLaunchKernelGGL((k_jvp_coeffs<T, NI, NO>), dim3((unsigned)blocks), dim3(256), 0, st, gd, P,
+                               (const Rec4<T>*)(ws + pl.off_rec), (const uint32_t*)(ws + pl.off_tile_start) + tg.NT,
+                               rot_b, trans_b, ow_b, pw, tk, tan.rot ? tan.rot + kb * (NO * NI) : nullptr,
+                               tan.trans ? tan.trans + kb * NO : nullptr, tan.ow ? tan.ow + kb : nullptr, coef, keys);
+            stage_mark(st);
+            // the pose's parameters, the background tangent and the plane are passed as pose 0
+            const T* bg_kb = bg_dot ? bg_dot + kb : nullptr;
+            T* out_kb = out_dot + (b * K + k) * G;
+            hipLaunchKernelGGL((k_tile_splat<T, NI, NO, true, false, false, true>), dim3(pl.max_items),
+                               dim3(kSplatThreads), 0, st, gd, tg, (const Rec4<T>*)(ws + pl.off_rec),
+                               (const WorkItem*)(ws + pl.off_items), (const uint32_t*)(ws + pl.off_nitems),
+                               (const uint32_t*)(ws + pl.off_tslab), rot_b, trans_b, (const T*)nullptr, bg_kb,
+                               (int64_t)0, out_kb, halo, ovf, 2, (const uint32_t*)keys, 1, (const T*)coef);
+            stage_mark(st);
+            hipLaunchKernelGGL((k_halo_gather<T, NO>), dim3(tg.NT + kSplitGrid), dim3(256), 0, st, gd, tg,
+                               (const T*)halo, (const T*)ovf, (const uint32_t*)(ws + pl.off_tparts),
+                               (const uint32_t*)(ws + pl.off_tslab), (const uint32_t*)(ws + pl.off_split) + 1,
+                               (const uint32_t*)(ws + pl.off_split), bg_kb, (int64_t)0, 1, out_kb);
+            stage_mark(st);
+        }
+    }
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
 #define DPR_INST(T, NI, NO)                                                                       \
     template int raster_tiled<T, NI, NO>(hipStream_t, unsigned, const int64_t*, int64_t, int64_t, \
                                          int64_t, T*, const T*, const T*, const T*, const T*,     \
@@ -4207,7 +4392,10 @@ int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_
                                            void*, size_t, Residual<T>);                           \
     template int raster_tiled_channels<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t,         \
                                                   int64_t, int, T*, const T*, const T*, const T*,        \
-                                                  const T*, const T*, const T*, void*, size_t);
+                                                  const T*, const T*, const T*, void*, size_t);                \
+    template int raster_tiled_jvp<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, int, T*,   \
+                                             const T*, const T*, const T*, const T*, const T*, JvpTangents<T>,  \
+                                             const T*, void*, size_t);
 DPR_INST(float, 2, 2)
 DPR_INST(float, 3, 3)
 DPR_INST(float, 3, 2)

@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define DPR_VERSION 107 /* 0.1.7: + point sampling (dpr_sample_ex_*, dpr_sample_pullback_ex_*) */
+#define DPR_VERSION 108 /* 0.1.8: + forward-mode derivative of raster (dpr_raster_jvp_ex_*) */
 
 /* status codes */
 #define DPR_OK 0
@@ -550,6 +550,68 @@ int dpr_sample_pullback_ex_f64(void *stream, int algo, unsigned flags, int n_in,
                                const double *translation, double *ds_dimage, double *ds_dpoints,
                                double *ds_drotation, double *ds_dtranslation, void *workspace,
                                size_t workspace_bytes);
+
+/* ---- FORWARD-MODE DERIVATIVE: out_dot = J . v of dpr_raster_* for K = 1..16 tangents ------------------
+ * For tangent k, pose b and point p, with coord = (R_b p + 1 + t_b) * n / 2 and (ref0, dlo) the cell and deltas
+ * of dpr_raster_* (held FIXED: the one-sided derivative dpr_raster_pullback_* uses, so that J . v is the exact
+ * transpose of the pullback for every input, points on cell faces included):
+ *     cdot_n    = n_n / 2 * (sum_j Rdot_{k,b}[n, j] p_j + sum_j R_b[n, j] pdot_{k,p}[j] + tdot_{k,b}[n])
+ *     a         = owdot_{k,b} * pw_p + ow_b * pwdot_{k,p}
+ *     b_n       = ow_b * pw_p * cdot_n
+ *     deposit_s = a * voxel_weight(dlo, s) + sum_n b_n * interp_weight(n, dlo, s)
+ *     out_dot[cell, k, b] = bgdot_{k,b} + sum over (p, s) -> cell of deposit_s
+ * interp_weight is the reference's piecewise derivative of the interpolant (src/raster_pullback.jl:150-160).
+ * The drop rules are those of dpr_raster_*: a rejected point deposits nothing whatever its tangents hold (they
+ * are not read), an out-of-range neighbour is dropped on its own.  out_weight / point_weight NULL = 1; the primal
+ * background does not enter.
+ * Layouts.  Every tangent holds K copies of its primal's layout, tangent k at k * (primal size): points_dot
+ * K x P x n_in, rotation_dot K x B x (n_out x n_in column-major), translation_dot K x B x n_out,
+ * point_weight_dot K x P; background_dot and out_weight_dot K x B (tangent k a contiguous run of B).  out_dot is
+ * the channel layout with C = K: plane (k, b) at (b * K + k) * G.  Any tangent may be NULL (= zero; a NULL
+ * tangent and a zero one give the same bits); with all of them NULL out_dot is zero-filled.  out_dot is
+ * overwritten.  All 16 (n_in, n_out).
+ * Algorithms.  DPR_ALGO_ATOMIC: background tangent fill, then one thread per point over a slice of the poses:
+ * the cell, the 2^N voxel weights and the N * 2^N interpolation weights once per (point, pose), the K tangents a
+ * run-time loop of 2^N global float atomics each; workspace 0.  DPR_ALGO_TILED, for (2,2), (3,3), (3,2) on grids
+ * of one tile slab (at most 32768 tiles) and P < 2^32: each pose binned once (the per-pose binning of the
+ * tiled channel forward), then per tangent one pass in binned order that writes the coefficients (a, b_n) of every
+ * record, one LDS tile splat of the deposits and one halo pass with the background tangent fused into the
+ * flush; workspace dpr_workspace_bytes_jvp_ex_* (independent of B and K).  AUTO (dpr_resolve_algo_jvp):
+ * DPR_ALGO_TILED where the pair and the grid have it and dpr_resolve_algo(DPR_OP_RASTER, .., P, 1) returns
+ * DPR_ALGO_TILED (the rule of the channel forward), DPR_ALGO_ATOMIC otherwise.  There is no DPR_ALGO_CHUNKED JVP.
+ * Summation order and reproducibility.  ATOMIC: global float atomics, unordered (rounding level run to run).
+ * TILED, fp32: 64-bit fixed-point sums per tile, exact, as the tiled forward -- a plane is bit-reproducible, and
+ * the plane of tangent k of a K-tangent call is bit-identical to the K = 1 call on tangent k, except for tiles
+ * split into parts (> max(4096, P / 256) records of one pose), whose parts add in fp32 and vary at rounding
+ * level.  TILED, fp64: f64 LDS atomics, rounding level.  TILED and ATOMIC agree at rounding level.
+ * Fixed-point guard.  |voxel_weight| <= 1 and |interp_weight| <= 1, so |deposit_s| <= m_p = |a| + sum_n |b_n|.
+ * The scale and the 2^10 range guard of the tiled forward (PRECISION OF THE FIXED-POINT SUMS above) are taken per
+ * scope -- one (pose, tangent) -- from the max / min non-zero m_p of its binned points; a scope whose m_p span
+ * more than 2^10, or hold NaN / Inf, accumulates with f64 LDS atomics instead.
+ * Errors (status, dpr_last_error text, nothing launched, out_dot untouched): dimensions outside 1..4
+ * DPR_ERR_UNSUPPORTED_DIMS; K outside 1..16, a bad grid, NULL out_dot or a NULL primal (points with P > 0,
+ * rotation, translation) DPR_ERR_INVALID_ARG; DPR_ALGO_TILED for another pair or an unsupported grid,
+ * DPR_ALGO_CHUNKED and the KEEP / REUSE flags DPR_ERR_UNSUPPORTED_ALGO; a workspace smaller than
+ * dpr_workspace_bytes_jvp_ex_* DPR_ERR_WORKSPACE.  The other flags are ignored.
+ * dpr_workspace_bytes_jvp_ex_* returns (size_t)-1 on invalid arguments; dpr_resolve_algo_jvp a negative status. */
+int dpr_resolve_algo_jvp(int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B, int64_t K);
+size_t dpr_workspace_bytes_jvp_ex_f32(int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                                      int64_t P, int64_t B, int64_t K);
+size_t dpr_workspace_bytes_jvp_ex_f64(int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                                      int64_t P, int64_t B, int64_t K);
+int dpr_raster_jvp_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                          int64_t P, int64_t B, int64_t K, float *out_dot, const float *points,
+                          const float *rotation, const float *translation, const float *out_weight,
+                          const float *point_weight, const float *points_dot, const float *rotation_dot,
+                          const float *translation_dot, const float *background_dot, const float *out_weight_dot,
+                          const float *point_weight_dot, void *workspace, size_t workspace_bytes);
+int dpr_raster_jvp_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                          int64_t P, int64_t B, int64_t K, double *out_dot, const double *points,
+                          const double *rotation, const double *translation, const double *out_weight,
+                          const double *point_weight, const double *points_dot, const double *rotation_dot,
+                          const double *translation_dot, const double *background_dot,
+                          const double *out_weight_dot, const double *point_weight_dot, void *workspace,
+                          size_t workspace_bytes);
 
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
