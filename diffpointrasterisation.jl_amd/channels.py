@@ -24,8 +24,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from .interface import (ColumnMajorRotation, DimensionMismatch, PullbackResult, _SUFFIX, _as, _canonicalise,
-                        _device_of, _is_grid_layout, _promote, _ptr, _stream_ptr, empty_grid, to_grid_layout)
+from .interface import (_REFUSED, ColumnMajorRotation, DimensionMismatch, PullbackResult, _SUFFIX, _algo_name,
+                        _allocate, _as, _canonicalise, _device_of, _grid_arr, _is_grid_layout, _promote, _ptr,
+                        _stream_ptr, empty_grid, to_grid_layout)
 
 MAX_CHANNELS = 16
 
@@ -35,12 +36,6 @@ def empty_channel_grid(grid_size: Sequence[int], channels: int, batch: Optional[
     """Allocate an `out` / `ds_dout` of the channel entry points: a view of logical shape
     grid_size + (C,) (+ (B,)) whose memory is a contiguous (B, C, n_N, .., n_1) tensor."""
     return empty_grid(tuple(int(n) for n in grid_size) + (int(channels),), batch, dtype, device)
-
-
-def _grid_arr(grid):
-    import numpy as np
-
-    return np.asarray(tuple(int(n) for n in grid), dtype=np.int64)
 
 
 def _check_channels(C):
@@ -54,9 +49,7 @@ def resolve_algo_channels(op: str, grid_size, n_points: int, batch: int, n_in: i
     opc = {"raster": _lib.OP_RASTER, "pullback": _lib.OP_PULLBACK}[op]
     rc = _lib.lib().dpr_resolve_algo_channels(opc, n_in, len(grid_size), g.ctypes.data_as(ctypes.c_void_p),
                                              n_points, batch, channels)
-    if rc < 0:
-        _lib.check(rc)
-    return {v: k for k, v in _lib.ALGOS.items()}[rc]
+    return _algo_name(rc)
 
 
 def workspace_bytes_channels(op: str, grid_size, n_points: int, batch: int, n_in: int, channels: int,
@@ -67,7 +60,7 @@ def workspace_bytes_channels(op: str, grid_size, n_points: int, batch: int, n_in
     need = getattr(_lib.lib(), f"dpr_workspace_bytes_channels_ex_{_SUFFIX[dtype]}")(
         opc, _lib.ALGOS[algo], 0, n_in, len(grid_size), g.ctypes.data_as(ctypes.c_void_p), n_points, batch,
         channels)
-    if need == ctypes.c_size_t(-1).value:
+    if need == _REFUSED:
         raise _lib.DprError(_lib.ERR_INVALID_ARG, _lib.last_error())
     return int(need)
 
@@ -76,14 +69,8 @@ def _workspace(op, algo_c, suf, n_in, grid, P, B, C, device, workspace, flags):
     g = _grid_arr(grid)
     need = getattr(_lib.lib(), f"dpr_workspace_bytes_channels_ex_{suf}")(
         op, algo_c, flags, n_in, len(grid), g.ctypes.data_as(ctypes.c_void_p), P, B, C)
-    if need == ctypes.c_size_t(-1).value or need == 0:
-        # (a refused query: the entry point itself reports the status, before any launch)
-        return None, 0
-    if workspace is not None:
-        if workspace.device != device or workspace.numel() * workspace.element_size() < need:
-            raise ValueError(f"workspace too small: need {need} bytes")
-        return workspace, workspace.numel() * workspace.element_size()
-    return torch.empty(need, dtype=torch.uint8, device=device), need
+    # (a refused query: the entry point itself reports the status, before any launch)
+    return _allocate(0 if need == _REFUSED else need, device, workspace)
 
 
 def _canonicalise_channels(points, rotation, translation, background, out_weight, point_weight, extra=()):

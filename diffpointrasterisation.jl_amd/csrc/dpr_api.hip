@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 
 #include "../../include/dpr.h"
 #include "dpr_kernels_atomic.h"
@@ -30,13 +31,6 @@ int fail(int code, const char* fmt, ...) {
     g_last_error = buf;
     return code;
 }
-
-#define DPR_HIP(expr)                                                                  \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess)                                                          \
-            return fail(DPR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
 
 // AUTO and DPR_ALGO_CHUNKED on 2-D grids: a small cost model (ms on one MI355X) instead of fixed
 // thresholds, because the crossover moves with three things at once -- the poses that share the
@@ -203,8 +197,31 @@ constexpr int kMaxDim = 4;
 static bool dims_supported(int n_in, int n_out) {
     return n_out >= 1 && n_out <= kMaxDim && n_in >= 1 && n_in <= kMaxDim;
 }
-static bool dims_have_all_algos(int n_in, int n_out) {
+// (constexpr: `if constexpr` keeps the other algorithms' templates to these three pairs)
+static constexpr bool dims_have_all_algos(int n_in, int n_out) {
     return (n_in == 2 && n_out == 2) || (n_in == 3 && n_out == 3) || (n_in == 3 && n_out == 2);
+}
+
+// f(std::integral_constant<int, NI>{}, std::integral_constant<int, NO>{}) for the runtime pair: the one place
+// that maps (n_in, n_out) to template arguments.  Callers have passed check_common, so the pair is supported.
+template <int NI, class F> static int with_out_dim(int n_out, F& f) {
+    using NIc = std::integral_constant<int, NI>;
+    switch (n_out) {
+        case 1: return f(NIc{}, std::integral_constant<int, 1>{});
+        case 2: return f(NIc{}, std::integral_constant<int, 2>{});
+        case 3: return f(NIc{}, std::integral_constant<int, 3>{});
+        case 4: return f(NIc{}, std::integral_constant<int, 4>{});
+    }
+    return fail(DPR_ERR_UNSUPPORTED_DIMS, "unsupported (n_in, n_out) = (%d, %d)", NI, n_out);
+}
+template <class F> static int with_dims(int n_in, int n_out, F&& f) {
+    switch (n_in) {
+        case 1: return with_out_dim<1>(n_out, f);
+        case 2: return with_out_dim<2>(n_out, f);
+        case 3: return with_out_dim<3>(n_out, f);
+        case 4: return with_out_dim<4>(n_out, f);
+    }
+    return fail(DPR_ERR_UNSUPPORTED_DIMS, "unsupported (n_in, n_out) = (%d, %d)", n_in, n_out);
 }
 
 static int check_common(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
@@ -227,13 +244,6 @@ static int check_common(int n_in, int n_out, const int64_t* grid, int64_t P, int
         return fail(DPR_ERR_INVALID_ARG, "voxels per pose (%lld) exceed 2^31-1", (long long)G);
     *G_out = G;
     return DPR_OK;
-}
-
-template <int NO> static GridDesc<NO> make_grid(const int64_t* grid, int64_t G) {
-    GridDesc<NO> gd;
-    for (int d = 0; d < NO; ++d) gd.n[d] = (int)grid[d];
-    gd.G = G;
-    return gd;
 }
 
 // DPR_ALGO_AUTO.  `flags` (in/out): a KEEP_BINNING / REUSE_BINNING call pair must run the SAME
@@ -322,23 +332,54 @@ void stage_mark(hipStream_t st) {
         (void)hipEventRecord(g_stage_events[g_stage_n++], st);
 }
 
+// ---------------------------------------------------------------- launch helpers
+// Pose slices (grid.y) of the per-point kernels: enough blocks to fill 256 CUs x 8 when P is small.
+// Returns the poses per slice; *slices_out: the slices that cover the B poses.
+static int pose_slices(int64_t P, int64_t B, int64_t* slices_out) {
+    const int64_t pblocks = (P + kBlock - 1) / kBlock;
+    int64_t slices = 1;
+    if (pblocks < 2048 && B > 1) {
+        slices = (2048 + pblocks - 1) / pblocks;
+        if (slices > B) slices = B;
+        if (slices > 65535) slices = 65535;
+    }
+    const int64_t pps = (B + slices - 1) / slices;
+    *slices_out = (B + pps - 1) / pps;
+    return (int)pps;
+}
+
+// k_fill_background: plane k of `out` (G voxels each) = bg[k] (0 without bg), in launches of at most 65535 planes
+template <typename T>
+static void fill_background(hipStream_t st, T* out, int64_t G, int64_t planes, const T* bg) {
+    const int64_t want = (G + kBlock - 1) / kBlock;
+    dim3 g((unsigned)(want < 4096 ? want : 4096), 1);
+    for (int64_t k0 = 0; k0 < planes; k0 += 65535) {
+        const int64_t nk = (planes - k0 < 65535) ? planes - k0 : 65535;
+        g.y = (unsigned)nk;
+        hipLaunchKernelGGL(k_fill_background<T>, g, dim3(kBlock), 0, st, out + k0 * G, G, bg ? bg + k0 : nullptr);
+    }
+}
+
+// k_grid_sum: d_bg[k] = the sum of plane k of `g` (the residual's planes alike), in launches of at most 65535 planes
+template <typename T>
+static void grid_sum(hipStream_t st, const T* g, int64_t G, int64_t planes, T* d_bg, Residual<T> rs) {
+    for (int64_t k0 = 0; k0 < planes; k0 += 65535) {
+        const int64_t nk = (planes - k0 < 65535) ? planes - k0 : 65535;
+        Residual<T> rk = rs;
+        if (rk.target) rk.target += k0 * G;
+        if (rk.loss) rk.loss += k0;
+        hipLaunchKernelGGL(k_grid_sum<T>, dim3((unsigned)grid_sum_blocks(G, nk), (unsigned)nk), dim3(kBlock), 0, st,
+                           g + k0 * G, G, d_bg + k0, rk);
+    }
+}
+
 // ---------------------------------------------------------------- forward
 template <typename T, int NI, int NO>
 static int raster_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B,
                          T* out, const T* points, const T* rot, const T* trans, const T* bg,
                          const T* ow, const T* pw) {
-    const GridDesc<NO> gd = make_grid<NO>(grid, G);
-    {
-        const int64_t want = (G + kBlock - 1) / kBlock;
-        dim3 g((unsigned)(want < 4096 ? want : 4096), (unsigned)(B < 65535 ? B : 65535));
-        // B > 65535 poses: loop on the host in slabs of 65535
-        for (int64_t b0 = 0; b0 < B; b0 += 65535) {
-            const int64_t nb = (B - b0 < 65535) ? B - b0 : 65535;
-            g.y = (unsigned)nb;
-            hipLaunchKernelGGL(k_fill_background<T>, g, dim3(kBlock), 0, st, out + b0 * G, G,
-                               bg ? bg + b0 : nullptr);
-        }
-    }
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    fill_background(st, out, G, B, bg);
     stage_mark(st);
     if (P > 0) {
         dim3 g((unsigned)((P + kBlock - 1) / kBlock), (unsigned)(B < 65535 ? B : 65535));
@@ -379,46 +420,35 @@ static int raster_impl(void* stream, int algo, unsigned flags, int n_in, int n_o
     hipStream_t st = (hipStream_t)stream;
     algo = resolve_algo(algo, DPR_OP_RASTER, n_in, n_out, grid, P, B, G, &flags);
     stage_mark(st);
-#define DPR_CASE(NI, NO)                                                                       \
-    if (n_in == NI && n_out == NO) {                                                           \
-        if (algo == DPR_ALGO_ATOMIC && !(flags & 3u))                                           \
-            return raster_atomic<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, bg, ow, \
-                                            pw);                                               \
-        if (algo == DPR_ALGO_TILED)                                                            \
-            return raster_tiled<T, NI, NO>(st, flags, grid, G, P, B, out, points, rot, trans, bg, ow,  \
-                                           pw, ws, ws_bytes);                                  \
-        if (algo == DPR_ALGO_CHUNKED) {                                                        \
-            if constexpr (NO == 2)                                                             \
-                return raster_chunkown<T, NI>(st, flags, grid, G, P, B, out, points, rot, trans, \
-                                              bg, ow, pw, ws, ws_bytes);                       \
-            else if (P > 0 && raster3d_sorts(flags, grid, G, P, B))                           \
-                return raster_owner_sorted<T>(st, flags, grid, G, P, B, out, points, rot,      \
-                                              trans, bg, ow, pw, ws, ws_bytes);                \
-            else if (chunked3d_lists(grid, G, P, B))                                           \
-                return raster_chunked<T, NI, NO>(st, flags, grid, G, P, B, out, points, rot,   \
-                                                 trans, bg, ow, pw, ws, ws_bytes);             \
-            else                                                                               \
-                return raster_owner<T>(st, flags, grid, G, P, B, out, points, rot, trans, bg,  \
-                                       ow, pw, ws, ws_bytes);                                  \
-        }                                                                                      \
-    }
-    DPR_CASE(2, 2)
-    DPR_CASE(3, 3)
-    DPR_CASE(3, 2)
-#undef DPR_CASE
-#define DPR_CASE_DIRECT(NI, NO)                                                                 \
-    if (n_in == NI && n_out == NO && algo == DPR_ALGO_ATOMIC && !(flags & 3u))                  \
-        return raster_atomic<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, bg, ow, pw);
-    DPR_CASE_DIRECT(1, 1) DPR_CASE_DIRECT(2, 1) DPR_CASE_DIRECT(3, 1) DPR_CASE_DIRECT(4, 1)
-    DPR_CASE_DIRECT(1, 2) DPR_CASE_DIRECT(4, 2)
-    DPR_CASE_DIRECT(1, 3) DPR_CASE_DIRECT(2, 3) DPR_CASE_DIRECT(4, 3)
-    DPR_CASE_DIRECT(1, 4) DPR_CASE_DIRECT(2, 4) DPR_CASE_DIRECT(3, 4) DPR_CASE_DIRECT(4, 4)
-#undef DPR_CASE_DIRECT
-    if (!dims_have_all_algos(n_in, n_out))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only (no flags)", n_in, n_out);
-    return fail(DPR_ERR_UNSUPPORTED_ALGO, "unknown algorithm %d (flags %u need DPR_ALGO_TILED)", algo,
-                flags);
+    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        if (algo == DPR_ALGO_ATOMIC && !(flags & 3u))
+            return raster_atomic<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, bg, ow, pw);
+        if constexpr (!dims_have_all_algos(NI, NO)) {
+            return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                        "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only (no flags)", n_in, n_out);
+        } else {
+            if (algo == DPR_ALGO_TILED)
+                return raster_tiled<T, NI, NO>(st, flags, grid, G, P, B, out, points, rot, trans, bg, ow, pw, ws,
+                                               ws_bytes);
+            if (algo == DPR_ALGO_CHUNKED) {
+                if constexpr (NO == 2)
+                    return raster_chunkown<T, NI>(st, flags, grid, G, P, B, out, points, rot, trans, bg, ow, pw, ws,
+                                                  ws_bytes);
+                else if (P > 0 && raster3d_sorts(flags, grid, G, P, B))
+                    return raster_owner_sorted<T>(st, flags, grid, G, P, B, out, points, rot, trans, bg, ow, pw, ws,
+                                                  ws_bytes);
+                else if (chunked3d_lists(grid, G, P, B))
+                    return raster_chunked<T, NI, NO>(st, flags, grid, G, P, B, out, points, rot, trans, bg, ow, pw,
+                                                     ws, ws_bytes);
+                else
+                    return raster_owner<T>(st, flags, grid, G, P, B, out, points, rot, trans, bg, ow, pw, ws,
+                                           ws_bytes);
+            }
+            return fail(DPR_ERR_UNSUPPORTED_ALGO, "unknown algorithm %d (flags %u need DPR_ALGO_TILED)", algo,
+                        flags);
+        }
+    });
 }
 
 // ---------------------------------------------------------------- pullback
@@ -427,33 +457,18 @@ static int pullback_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64
                            const T* g, const T* points, const T* rot, const T* trans, const T* ow,
                            const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow,
                            T* d_pw, Residual<T> rs) {
-    const GridDesc<NO> gd = make_grid<NO>(grid, G);
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     if (rs.target && rs.loss) DPR_HIP(hipMemsetAsync(rs.loss, 0, sizeof(T) * (size_t)B, st));
     DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * NO * NI), st));
     DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * NO), st));
     DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
     DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {
-        const int64_t nb = (B - b0 < 65535) ? B - b0 : 65535;
-        const int64_t want = grid_sum_blocks(G, nb);
-        dim3 gg((unsigned)want, (unsigned)nb);
-        Residual<T> rb = rs;
-        if (rb.target) rb.target += b0 * G;
-        if (rb.loss) rb.loss += b0;
-        hipLaunchKernelGGL(k_grid_sum<T>, gg, dim3(kBlock), 0, st, g + b0 * G, G, d_bg + b0, rb);
-    }
+    grid_sum(st, g, G, B, d_bg, rs);
     stage_mark(st);
     if (P > 0) {
         const int64_t pblocks = (P + kBlock - 1) / kBlock;
-        // enough blocks to fill 256 CUs x 8: split poses into slices when P is small
         int64_t slices = 1;
-        if (pblocks < 2048 && B > 1) {
-            slices = (2048 + pblocks - 1) / pblocks;
-            if (slices > B) slices = B;
-            if (slices > 65535) slices = 65535;
-        }
-        const int poses_per_slice = (int)((B + slices - 1) / slices);
-        slices = (B + poses_per_slice - 1) / poses_per_slice;
+        const int poses_per_slice = pose_slices(P, B, &slices);
         const int accumulate = slices > 1;
         if (accumulate) {
             DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
@@ -480,20 +495,19 @@ static bool pullback3d_sorts(unsigned flags, const int64_t* grid, int64_t P, int
 struct Sorted3dPlan {
     size_t off_pts, off_pw, off_inv, off_perm, off_g, off_gw, off_sort, off_own, own_bytes, total;
 };
-static size_t s3_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static Sorted3dPlan sorted3d_plan(size_t elem, const int64_t* grid, int64_t P, int64_t B) {
     Sorted3dPlan pl;
     size_t o = 0;
-    pl.off_pts = o;  o += s3_align((size_t)P * 3 * elem);
-    pl.off_pw = o;   o += s3_align((size_t)P * elem);
-    pl.off_inv = o;  o += s3_align((size_t)P * 4);
-    pl.off_perm = o; o += s3_align((size_t)P * 4);
-    pl.off_g = o;    o += s3_align((size_t)P * 3 * elem);
-    pl.off_gw = o;   o += s3_align((size_t)P * elem);
-    pl.off_sort = o; o += s3_align(sort_workspace_bytes(P));
+    pl.off_pts = o;  o += align_up((size_t)P * 3 * elem);
+    pl.off_pw = o;   o += align_up((size_t)P * elem);
+    pl.off_inv = o;  o += align_up((size_t)P * 4);
+    pl.off_perm = o; o += align_up((size_t)P * 4);
+    pl.off_g = o;    o += align_up((size_t)P * 3 * elem);
+    pl.off_gw = o;   o += align_up((size_t)P * elem);
+    pl.off_sort = o; o += align_up(sort_workspace_bytes(P));
     pl.off_own = o;
     pl.own_bytes = owner_workspace_bytes(DPR_OP_PULLBACK, grid, P, B);
-    o += s3_align(pl.own_bytes == (size_t)-1 ? 0 : pl.own_bytes);
+    o += align_up(pl.own_bytes == (size_t)-1 ? 0 : pl.own_bytes);
     pl.total = o;
     return pl;
 }
@@ -522,15 +536,15 @@ struct SortedFwdPlan {
 static SortedFwdPlan sorted_fwd_plan(size_t elem, const int64_t* grid, int64_t P, int64_t B) {
     SortedFwdPlan pl;
     size_t o = 0;
-    pl.off_pts = o;  o += s3_align((size_t)P * 3 * elem);
-    pl.off_pw = o;   o += s3_align((size_t)P * elem);
-    pl.off_perm = o; o += s3_align((size_t)P * 4);
-    pl.off_sort = o; o += s3_align(sort_workspace_bytes(P));
+    pl.off_pts = o;  o += align_up((size_t)P * 3 * elem);
+    pl.off_pw = o;   o += align_up((size_t)P * elem);
+    pl.off_perm = o; o += align_up((size_t)P * 4);
+    pl.off_sort = o; o += align_up(sort_workspace_bytes(P));
     pl.off_own = o;
     int64_t G = grid[0] * grid[1] * grid[2];
     pl.own_bytes = chunked3d_lists(grid, G, P, B) ? chunked_workspace_bytes(3, grid, P, B)
                                                   : owner_workspace_bytes(DPR_OP_RASTER, grid, P, B);
-    o += s3_align(pl.own_bytes == (size_t)-1 ? 0 : pl.own_bytes);
+    o += align_up(pl.own_bytes == (size_t)-1 ? 0 : pl.own_bytes);
     pl.total = o;
     return pl;
 }
@@ -623,55 +637,39 @@ static int pullback_impl(void* stream, int algo, unsigned flags, int n_in, int n
     algo = resolve_algo(algo, rs.target ? DPR_OP_RESIDUAL_PULLBACK : DPR_OP_PULLBACK, n_in, n_out, grid, P, B, G,
                         &flags);
     stage_mark(st);
-#define DPR_CASE(NI, NO)                                                                         \
-    if (n_in == NI && n_out == NO) {                                                             \
-        if (algo == DPR_ALGO_ATOMIC && !(flags & 3u))                                             \
-            return pullback_atomic<T, NI, NO>(st, grid, G, P, B, g, points, rot, trans, ow, pw,   \
-                                              d_pts, d_rot, d_trans, d_bg, d_ow, d_pw, rs);      \
-        if (algo == DPR_ALGO_TILED)                                                              \
-            return pullback_tiled<T, NI, NO>(st, flags, grid, G, P, B, g, points, rot, trans, ow, pw,    \
-                                             d_pts, d_rot, d_trans, d_bg, d_ow, d_pw, ws,        \
-                                             ws_bytes, rs);                                      \
-        if (algo == DPR_ALGO_CHUNKED) {                                                          \
-            if constexpr (NO == 2) {                                                             \
-                return pullback_chunkown<T, NI>(st, flags, grid, G, P, B, g, points, rot, trans, \
-                                                ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw, \
-                                                ws, ws_bytes, rs);                               \
-            } else {                                                                             \
-                if (rs.target)                                                                   \
-                    return fail(DPR_ERR_UNSUPPORTED_ALGO,                                        \
-                                "the residual pullback has no 3-D DPR_ALGO_CHUNKED variant");    \
-                if (grid[0] < 2) /* (its x-pair gathers need two cells per row) */               \
-                    return pullback_atomic<T, NI, NO>(st, grid, G, P, B, g, points, rot, trans,  \
-                                                      ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, \
-                                                      d_pw, rs);                                 \
-                if (P > 0 && pullback3d_sorts(flags, grid, P, B))                               \
-                    return pullback_owner_sorted<T>(st, flags, grid, G, P, B, g, points, rot,    \
-                                                    trans, ow, pw, d_pts, d_rot, d_trans, d_bg,  \
-                                                    d_ow, d_pw, ws, ws_bytes);                   \
-                return pullback_owner<T>(st, flags, grid, G, P, B, g, points, rot, trans, ow,    \
-                                         pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw, ws,        \
-                                         ws_bytes);                                              \
-            }                                                                                    \
-        }                                                                                        \
-    }
-    DPR_CASE(2, 2)
-    DPR_CASE(3, 3)
-    DPR_CASE(3, 2)
-#undef DPR_CASE
-#define DPR_CASE_DIRECT(NI, NO)                                                                   \
-    if (n_in == NI && n_out == NO && algo == DPR_ALGO_ATOMIC && !(flags & 3u))                    \
-        return pullback_atomic<T, NI, NO>(st, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, \
-                                          d_rot, d_trans, d_bg, d_ow, d_pw, rs);
-    DPR_CASE_DIRECT(1, 1) DPR_CASE_DIRECT(2, 1) DPR_CASE_DIRECT(3, 1) DPR_CASE_DIRECT(4, 1)
-    DPR_CASE_DIRECT(1, 2) DPR_CASE_DIRECT(4, 2)
-    DPR_CASE_DIRECT(1, 3) DPR_CASE_DIRECT(2, 3) DPR_CASE_DIRECT(4, 3)
-    DPR_CASE_DIRECT(1, 4) DPR_CASE_DIRECT(2, 4) DPR_CASE_DIRECT(3, 4) DPR_CASE_DIRECT(4, 4)
-#undef DPR_CASE_DIRECT
-    if (!dims_have_all_algos(n_in, n_out))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only (no flags)", n_in, n_out);
-    return fail(DPR_ERR_UNSUPPORTED_ALGO, "unknown algorithm %d", algo);
+    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        if (algo == DPR_ALGO_ATOMIC && !(flags & 3u))
+            return pullback_atomic<T, NI, NO>(st, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans,
+                                              d_bg, d_ow, d_pw, rs);
+        if constexpr (!dims_have_all_algos(NI, NO)) {
+            return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                        "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only (no flags)", n_in, n_out);
+        } else {
+            if (algo == DPR_ALGO_TILED)
+                return pullback_tiled<T, NI, NO>(st, flags, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts,
+                                                 d_rot, d_trans, d_bg, d_ow, d_pw, ws, ws_bytes, rs);
+            if (algo == DPR_ALGO_CHUNKED) {
+                if constexpr (NO == 2) {
+                    return pullback_chunkown<T, NI>(st, flags, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts,
+                                                    d_rot, d_trans, d_bg, d_ow, d_pw, ws, ws_bytes, rs);
+                } else {
+                    if (rs.target)
+                        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                                    "the residual pullback has no 3-D DPR_ALGO_CHUNKED variant");
+                    if (grid[0] < 2)  // (its x-pair gathers need two cells per row)
+                        return pullback_atomic<T, NI, NO>(st, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts,
+                                                          d_rot, d_trans, d_bg, d_ow, d_pw, rs);
+                    if (P > 0 && pullback3d_sorts(flags, grid, P, B))
+                        return pullback_owner_sorted<T>(st, flags, grid, G, P, B, g, points, rot, trans, ow, pw,
+                                                        d_pts, d_rot, d_trans, d_bg, d_ow, d_pw, ws, ws_bytes);
+                    return pullback_owner<T>(st, flags, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot,
+                                             d_trans, d_bg, d_ow, d_pw, ws, ws_bytes);
+                }
+            }
+            return fail(DPR_ERR_UNSUPPORTED_ALGO, "unknown algorithm %d", algo);
+        }
+    });
 }
 
 template <typename T>
@@ -754,19 +752,9 @@ template <typename T, int NI, int NO>
 static int raster_atomic_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C,
                                   T* out, const T* points, const T* rot, const T* trans, const T* bg,
                                   const T* ow, const T* pw) {
-    const GridDesc<NO> gd = make_grid<NO>(grid, G);
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     // B * C planes, plane k = b * C + c, background[k] (C x B, channel fastest)
-    const int64_t planes = B * C;
-    {
-        const int64_t want = (G + kBlock - 1) / kBlock;
-        dim3 g((unsigned)(want < 4096 ? want : 4096), 1);
-        for (int64_t k0 = 0; k0 < planes; k0 += 65535) {
-            const int64_t nk = (planes - k0 < 65535) ? planes - k0 : 65535;
-            g.y = (unsigned)nk;
-            hipLaunchKernelGGL(k_fill_background<T>, g, dim3(kBlock), 0, st, out + k0 * G, G,
-                               bg ? bg + k0 : nullptr);
-        }
-    }
+    fill_background(st, out, G, B * C, bg);
     stage_mark(st);
     if (P > 0) {
         dim3 g((unsigned)((P + kBlock - 1) / kBlock), (unsigned)(B < 65535 ? B : 65535));
@@ -811,51 +799,35 @@ static int raster_channels_impl(void* stream, int algo, unsigned flags, int n_in
                                               "(algorithm %d)", algo);
     stage_mark(st);
     const int c = (int)C;
-#define DPR_CASE_CH(NI, NO)                                                                                 \
-    if (n_in == NI && n_out == NO) {                                                                        \
-        if (algo == DPR_ALGO_ATOMIC)                                                                        \
-            return raster_atomic_channels<T, NI, NO>(st, grid, G, P, B, c, out, points, rot, trans, bg, ow, \
-                                                     pw);                                                   \
-        if constexpr ((NI == 2 && NO == 2) || (NI == 3 && NO == 3) || (NI == 3 && NO == 2))                 \
-            return raster_tiled_channels<T, NI, NO>(st, grid, G, P, B, c, out, points, rot, trans, bg, ow,  \
-                                                    pw, ws, ws_bytes);                                      \
-    }
-    DPR_CASE_CH(1, 1) DPR_CASE_CH(2, 1) DPR_CASE_CH(3, 1) DPR_CASE_CH(4, 1)
-    DPR_CASE_CH(1, 2) DPR_CASE_CH(2, 2) DPR_CASE_CH(3, 2) DPR_CASE_CH(4, 2)
-    DPR_CASE_CH(1, 3) DPR_CASE_CH(2, 3) DPR_CASE_CH(3, 3) DPR_CASE_CH(4, 3)
-    DPR_CASE_CH(1, 4) DPR_CASE_CH(2, 4) DPR_CASE_CH(3, 4) DPR_CASE_CH(4, 4)
-#undef DPR_CASE_CH
-    return fail(DPR_ERR_UNSUPPORTED_ALGO, "unknown algorithm %d", algo);
+    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        // (algo is ATOMIC, or TILED on a pair that has it)
+        if constexpr (dims_have_all_algos(NI, NO)) {
+            if (algo == DPR_ALGO_TILED)
+                return raster_tiled_channels<T, NI, NO>(st, grid, G, P, B, c, out, points, rot, trans, bg, ow, pw,
+                                                        ws, ws_bytes);
+        }
+        return raster_atomic_channels<T, NI, NO>(st, grid, G, P, B, c, out, points, rot, trans, bg, ow, pw);
+    });
 }
 
 template <typename T, int NI, int NO>
 static int pullback_atomic_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C,
                                     const T* g, const T* points, const T* rot, const T* trans, const T* ow,
                                     const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw) {
-    const GridDesc<NO> gd = make_grid<NO>(grid, G);
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     const int64_t planes = B * C;
     DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * NO * NI), st));
     DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * NO), st));
     DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
     DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)planes, st));
     // ds_dbackground[c, b] = sum of plane b * C + c: the single-channel grid sum over B * C planes
-    for (int64_t k0 = 0; k0 < planes; k0 += 65535) {
-        const int64_t nk = (planes - k0 < 65535) ? planes - k0 : 65535;
-        dim3 gg((unsigned)grid_sum_blocks(G, nk), (unsigned)nk);
-        hipLaunchKernelGGL(k_grid_sum<T>, gg, dim3(kBlock), 0, st, g + k0 * G, G, d_bg + k0,
-                           Residual<T>{nullptr, T(0), nullptr});
-    }
+    grid_sum(st, g, G, planes, d_bg, Residual<T>{nullptr, T(0), nullptr});
     stage_mark(st);
     if (P > 0) {
         const int64_t pblocks = (P + kBlock - 1) / kBlock;
-        int64_t slices = 1;  // (as pullback_atomic: fill the chip when P is small)
-        if (pblocks < 2048 && B > 1) {
-            slices = (2048 + pblocks - 1) / pblocks;
-            if (slices > B) slices = B;
-            if (slices > 65535) slices = 65535;
-        }
-        const int poses_per_slice = (int)((B + slices - 1) / slices);
-        slices = (B + poses_per_slice - 1) / poses_per_slice;
+        int64_t slices = 1;
+        const int poses_per_slice = pose_slices(P, B, &slices);
         const int accumulate = slices > 1;
         if (accumulate) {
             DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
@@ -910,16 +882,10 @@ static int pullback_channels_impl(void* stream, int algo, unsigned flags, int n_
         return rc;
     stage_mark(st);
     const int c = (int)C;
-#define DPR_CASE_CH(NI, NO)                                                                                  \
-    if (n_in == NI && n_out == NO)                                                                           \
-        return pullback_atomic_channels<T, NI, NO>(st, grid, G, P, B, c, g, points, rot, trans, ow, pw, d_pts, \
-                                                   d_rot, d_trans, d_bg, d_ow, d_pw);
-    DPR_CASE_CH(1, 1) DPR_CASE_CH(2, 1) DPR_CASE_CH(3, 1) DPR_CASE_CH(4, 1)
-    DPR_CASE_CH(1, 2) DPR_CASE_CH(2, 2) DPR_CASE_CH(3, 2) DPR_CASE_CH(4, 2)
-    DPR_CASE_CH(1, 3) DPR_CASE_CH(2, 3) DPR_CASE_CH(3, 3) DPR_CASE_CH(4, 3)
-    DPR_CASE_CH(1, 4) DPR_CASE_CH(2, 4) DPR_CASE_CH(3, 4) DPR_CASE_CH(4, 4)
-#undef DPR_CASE_CH
-    return fail(DPR_ERR_UNSUPPORTED_DIMS, "unsupported (n_in, n_out)");
+    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        return pullback_atomic_channels<T, decltype(ni)::value, decltype(no)::value>(
+            st, grid, G, P, B, c, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw);
+    });
 }
 
 template <typename T>
@@ -979,20 +945,6 @@ static size_t sample_tiled_workspace_bytes(size_t elem, unsigned flags, int n_in
     return tiled_workspace_bytes(elem, DPR_OP_RASTER, flags & DPR_FLAG_COHERENT_POINTS, n_in, n_out, grid, P, 1);
 }
 
-// pose slices of the sampling kernels: enough blocks to fill the chip when P is small (as pullback_atomic)
-static int sample_poses_per_slice(int64_t P, int64_t B, int64_t* slices_out) {
-    const int64_t pblocks = (P + kBlock - 1) / kBlock;
-    int64_t slices = 1;
-    if (pblocks < 2048 && B > 1) {
-        slices = (2048 + pblocks - 1) / pblocks;
-        if (slices > B) slices = B;
-        if (slices > 65535) slices = 65535;
-    }
-    const int64_t pps = (B + slices - 1) / slices;
-    *slices_out = (B + pps - 1) / pps;
-    return (int)pps;
-}
-
 static int check_sample_sizes(int64_t P, int64_t B, int64_t G) {
     if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
     if (B > 0 && (P > ((int64_t)1 << 62) / B || G > ((int64_t)1 << 62) / B))
@@ -1004,9 +956,9 @@ static int check_sample_sizes(int64_t P, int64_t B, int64_t G) {
 template <typename T, int NI, int NO>
 static int sample_direct(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* values,
                          const T* image, const T* points, const T* rot, const T* trans) {
-    const GridDesc<NO> gd = make_grid<NO>(grid, G);
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     int64_t slices = 1;
-    const int pps = sample_poses_per_slice(P, B, &slices);
+    const int pps = pose_slices(P, B, &slices);
     dim3 gg((unsigned)((P + kBlock - 1) / kBlock), (unsigned)slices);
     hipLaunchKernelGGL((k_sample_fwd<T, NI, NO>), gg, dim3(kBlock), 0, st, gd, P, B, values, image, points, rot,
                        trans, pps);
@@ -1036,14 +988,10 @@ static int sample_impl(void* stream, int algo, unsigned flags, int n_in, int n_o
     if (int rc = check_alignment<T>(ws, {values, image, points, rot, trans})) return rc;
     hipStream_t st = (hipStream_t)stream;
     stage_mark(st);
-#define DPR_CASE_S(NI, NO)                                                                                   \
-    if (n_in == NI && n_out == NO) return sample_direct<T, NI, NO>(st, grid, G, P, B, values, image, points, rot, trans);
-    DPR_CASE_S(1, 1) DPR_CASE_S(2, 1) DPR_CASE_S(3, 1) DPR_CASE_S(4, 1)
-    DPR_CASE_S(1, 2) DPR_CASE_S(2, 2) DPR_CASE_S(3, 2) DPR_CASE_S(4, 2)
-    DPR_CASE_S(1, 3) DPR_CASE_S(2, 3) DPR_CASE_S(3, 3) DPR_CASE_S(4, 3)
-    DPR_CASE_S(1, 4) DPR_CASE_S(2, 4) DPR_CASE_S(3, 4) DPR_CASE_S(4, 4)
-#undef DPR_CASE_S
-    return fail(DPR_ERR_UNSUPPORTED_DIMS, "unsupported (n_in, n_out)");
+    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        return sample_direct<T, decltype(ni)::value, decltype(no)::value>(st, grid, G, P, B, values, image, points,
+                                                                          rot, trans);
+    });
 }
 
 template <typename T, int NI, int NO>
@@ -1051,7 +999,7 @@ static int sample_pullback_run(hipStream_t st, int algo, unsigned flags, const i
                                int64_t B, const T* dv, const T* image, const T* points, const T* rot,
                                const T* trans, T* d_img, T* d_pts, T* d_rot, T* d_trans, void* ws,
                                size_t ws_bytes) {
-    const GridDesc<NO> gd = make_grid<NO>(grid, G);
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     const bool tiled = algo == DPR_ALGO_TILED;
     if (d_rot) DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * NO * NI), st));
     if (d_trans) DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * NO), st));
@@ -1061,7 +1009,7 @@ static int sample_pullback_run(hipStream_t st, int algo, unsigned flags, const i
     T* const kernel_img = tiled ? nullptr : d_img;
     if (kernel_img || d_pts || d_rot || d_trans) {
         int64_t slices = 1;
-        const int pps = sample_poses_per_slice(P, B, &slices);
+        const int pps = pose_slices(P, B, &slices);
         const int accumulate = slices > 1;
         if (accumulate && d_pts) DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
         dim3 gg((unsigned)((P + kBlock - 1) / kBlock), (unsigned)slices);
@@ -1071,7 +1019,7 @@ static int sample_pullback_run(hipStream_t st, int algo, unsigned flags, const i
     }
     stage_mark(st);
     if (tiled && d_img) {
-        if constexpr ((NI == 2 && NO == 2) || (NI == 3 && NO == 3) || (NI == 3 && NO == 2)) {
+        if constexpr (dims_have_all_algos(NI, NO)) {
             // pose b: the single-pose tiled forward of weights ds_dvalues[:, b] (a contiguous column),
             // background 0, out_weight 1 -- plane b is what dpr_raster_ex_*(DPR_ALGO_TILED) returns for them
             for (int64_t b = 0; b < B; ++b)
@@ -1122,16 +1070,10 @@ static int sample_pullback_impl(void* stream, int algo, unsigned flags, int n_in
     if (int rc = check_alignment<T>(ws, {dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans})) return rc;
     hipStream_t st = (hipStream_t)stream;
     stage_mark(st);
-#define DPR_CASE_S(NI, NO)                                                                                   \
-    if (n_in == NI && n_out == NO)                                                                           \
-        return sample_pullback_run<T, NI, NO>(st, algo, flags, grid, G, P, B, dv, image, points, rot, trans, \
-                                              d_img, d_pts, d_rot, d_trans, ws, ws_bytes);
-    DPR_CASE_S(1, 1) DPR_CASE_S(2, 1) DPR_CASE_S(3, 1) DPR_CASE_S(4, 1)
-    DPR_CASE_S(1, 2) DPR_CASE_S(2, 2) DPR_CASE_S(3, 2) DPR_CASE_S(4, 2)
-    DPR_CASE_S(1, 3) DPR_CASE_S(2, 3) DPR_CASE_S(3, 3) DPR_CASE_S(4, 3)
-    DPR_CASE_S(1, 4) DPR_CASE_S(2, 4) DPR_CASE_S(3, 4) DPR_CASE_S(4, 4)
-#undef DPR_CASE_S
-    return fail(DPR_ERR_UNSUPPORTED_DIMS, "unsupported (n_in, n_out)");
+    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        return sample_pullback_run<T, decltype(ni)::value, decltype(no)::value>(
+            st, algo, flags, grid, G, P, B, dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans, ws, ws_bytes);
+    });
 }
 
 template <typename T>
@@ -1200,7 +1142,7 @@ static int raster_jvp_run(hipStream_t st, int algo, const int64_t* grid, int64_t
                           JvpTangents<T> tan, const T* bg_dot, void* ws, size_t ws_bytes) {
     const bool any = tan.points || tan.rot || tan.trans || tan.ow || tan.pw;
     if (algo == DPR_ALGO_TILED && P > 0 && any) {
-        if constexpr ((NI == 2 && NO == 2) || (NI == 3 && NO == 3) || (NI == 3 && NO == 2))
+        if constexpr (dims_have_all_algos(NI, NO))
             return raster_tiled_jvp<T, NI, NO>(st, grid, G, P, B, K, out_dot, points, rot, trans, ow, pw, tan,
                                                bg_dot, ws, ws_bytes);
         return fail(DPR_ERR_UNSUPPORTED_ALGO, "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only", NI, NO);
@@ -1216,9 +1158,9 @@ static int raster_jvp_run(hipStream_t st, int algo, const int64_t* grid, int64_t
     }
     stage_mark(st);
     if (P > 0 && any) {
-        const GridDesc<NO> gd = make_grid<NO>(grid, G);
+        const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
         int64_t slices = 1;
-        const int pps = sample_poses_per_slice(P, B, &slices);
+        const int pps = pose_slices(P, B, &slices);
         dim3 gg((unsigned)((P + kBlock - 1) / kBlock), (unsigned)slices);
         hipLaunchKernelGGL((k_jvp_atomic<T, NI, NO>), gg, dim3(kBlock), 0, st, gd, P, B, K, out_dot, points, rot,
                            trans, ow, pw, tan, pps);
@@ -1254,16 +1196,11 @@ static int raster_jvp_impl(void* stream, int algo, unsigned flags, int n_in, int
     hipStream_t st = (hipStream_t)stream;
     stage_mark(st);
     const int k = (int)K;
-#define DPR_CASE_J(NI, NO)                                                                                      \
-    if (n_in == NI && n_out == NO)                                                                              \
-        return raster_jvp_run<T, NI, NO>(st, algo, grid, G, P, B, k, out_dot, points, rot, trans, ow, pw, tan, \
-                                         bg_dot, ws, ws_bytes);
-    DPR_CASE_J(1, 1) DPR_CASE_J(2, 1) DPR_CASE_J(3, 1) DPR_CASE_J(4, 1)
-    DPR_CASE_J(1, 2) DPR_CASE_J(2, 2) DPR_CASE_J(3, 2) DPR_CASE_J(4, 2)
-    DPR_CASE_J(1, 3) DPR_CASE_J(2, 3) DPR_CASE_J(3, 3) DPR_CASE_J(4, 3)
-    DPR_CASE_J(1, 4) DPR_CASE_J(2, 4) DPR_CASE_J(3, 4) DPR_CASE_J(4, 4)
-#undef DPR_CASE_J
-    return fail(DPR_ERR_UNSUPPORTED_DIMS, "unsupported (n_in, n_out)");
+    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        return raster_jvp_run<T, decltype(ni)::value, decltype(no)::value>(st, algo, grid, G, P, B, k, out_dot, points,
+                                                                           rot, trans, ow, pw, tan, bg_dot, ws,
+                                                                           ws_bytes);
+    });
 }
 
 template <typename T>

@@ -358,8 +358,6 @@ __global__ __launch_bounds__(256) void k_chunk_divert_fwd(
 }
 
 // ------------------------------------------------------------------ host side
-static size_t calign(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct CPlan {
     int64_t n_chunks, cap, Bw;  // Bw = poses held in the workspace at once
     size_t off_sets, off_nset, off_count, off_start, off_order, off_list, total;
@@ -375,17 +373,17 @@ static CPlan make_cplan(int NT, int64_t P, int64_t B) {
     if (pl.Bw > 16) pl.Bw = 16;
     size_t o = 0;
     pl.off_sets = o;
-    o += calign((size_t)pl.Bw * pl.n_chunks * kSetMax * 2);
+    o += align_up((size_t)pl.Bw * pl.n_chunks * kSetMax * 2);
     pl.off_nset = o;
-    o += calign((size_t)pl.Bw * pl.n_chunks);
+    o += align_up((size_t)pl.Bw * pl.n_chunks);
     pl.off_count = o;
-    o += calign((size_t)pl.Bw * NT * 4);
+    o += align_up((size_t)pl.Bw * NT * 4);
     pl.off_start = o;
-    o += calign((size_t)pl.Bw * (NT + 1) * 4);
+    o += align_up((size_t)pl.Bw * (NT + 1) * 4);
     pl.off_order = o;
-    o += calign((size_t)pl.Bw * NT * 4);
+    o += align_up((size_t)pl.Bw * NT * 4);
     pl.off_list = o;
-    o += calign((size_t)pl.Bw * pl.cap * 4);
+    o += align_up((size_t)pl.Bw * pl.cap * 4);
     pl.total = o;
     return pl;
 }
@@ -411,20 +409,6 @@ size_t chunked_workspace_bytes(int n_out, const int64_t* grid, int64_t P, int64_
         NT = tg.NT;
     }
     return make_cplan(NT, P, B).total;
-}
-
-#define DPR_HIP(expr)                                                                \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess)                                                        \
-            return fail(DPR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-template <int NO> static GridDesc<NO> cgrid_desc(const int64_t* grid, int64_t G) {
-    GridDesc<NO> gd;
-    for (int d = 0; d < NO; ++d) gd.n[d] = (int)grid[d];
-    gd.G = G;
-    return gd;
 }
 
 // tile sets + lists for poses [b0, b0 + nb)
@@ -466,7 +450,7 @@ int raster_chunked(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
         return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_CHUNKED raster needs %zu workspace bytes, got %zu",
                     pl.total, ws_ ? ws_bytes : (size_t)0);
     char* ws = (char*)ws_;
-    const GridDesc<NO> gd = cgrid_desc<NO>(grid, G);
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     for (int64_t b0 = 0; b0 < B; b0 += pl.Bw) {
         const int64_t nb = (B - b0 < pl.Bw) ? B - b0 : pl.Bw;
         if (int rc = build_lists<T, NI, NO>(st, gd, tg, pl, ws, P, points, rot, trans, b0, nb))

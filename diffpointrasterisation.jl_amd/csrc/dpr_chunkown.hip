@@ -892,8 +892,6 @@ __global__ __launch_bounds__(256) void k_co_unsort(int64_t P, const uint32_t* __
 }
 
 // ------------------------------------------------------------------ host side
-static size_t co_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct COPlan {
     int64_t nblk;
     int slices, poses_per_slice;
@@ -924,23 +922,23 @@ static COPlan co_plan(size_t elem, int op, unsigned flags, int n_in, int64_t P, 
     const bool sort = !(flags & DPR_FLAG_COHERENT_POINTS);
     size_t o = 0;
     pl.off_hdr = o;
-    o += co_align(sizeof(SortHeader));
+    o += align_up(sizeof(SortHeader));
     pl.off_pts = o;
-    if (sort) o += co_align((size_t)P * n_in * elem);
+    if (sort) o += align_up((size_t)P * n_in * elem);
     pl.off_pw = o;
-    if (sort) o += co_align((size_t)P * elem);
+    if (sort) o += align_up((size_t)P * elem);
     pl.off_perm = o;
-    if (sort) o += co_align((size_t)P * 4);
+    if (sort) o += align_up((size_t)P * 4);
     pl.off_grad = o;
-    if (sort && op == DPR_OP_PULLBACK) o += co_align((size_t)P * n_in * elem);
+    if (sort && op == DPR_OP_PULLBACK) o += align_up((size_t)P * n_in * elem);
     pl.off_gradw = o;
-    if (sort && op == DPR_OP_PULLBACK) o += co_align((size_t)P * elem);
+    if (sort && op == DPR_OP_PULLBACK) o += align_up((size_t)P * elem);
     pl.off_part = o;
-    if (op == DPR_OP_PULLBACK) o += co_align((size_t)(2 * n_in + 3) * (size_t)(B > 0 ? B : 1) * pl.nblk * 8);
+    if (op == DPR_OP_PULLBACK) o += align_up((size_t)(2 * n_in + 3) * (size_t)(B > 0 ? B : 1) * pl.nblk * 8);
     pl.off_sort = o;
     if (sort) {
         const size_t a = sort_workspace_bytes(P), c = coarse_sort_scratch_bytes(elem, P);
-        o += co_align(a > c ? a : c);
+        o += align_up(a > c ? a : c);
     }
     pl.total = o > 0 ? o : 256;
     return pl;
@@ -970,13 +968,6 @@ size_t chunkown_workspace_bytes(size_t elem, int op, unsigned flags, int n_in, i
     return co_plan(elem, op, flags, n_in, P, B).total;
 }
 
-#define DPR_HIP(expr)                                                                \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess)                                                        \
-            return fail(DPR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 template <typename T, int NI>
 int raster_chunkown(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G, int64_t P,
                     int64_t B, T* out, const T* points, const T* rot, const T* trans, const T* bg,
@@ -992,10 +983,7 @@ int raster_chunkown(hipStream_t st, unsigned flags, const int64_t* grid, int64_t
         return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_CHUNKED raster needs %zu workspace bytes, got %zu",
                     pl.total, ws_ ? ws_bytes : (size_t)0);
     char* ws = (char*)ws_;
-    GridDesc<2> gd;
-    gd.n[0] = (int)grid[0];
-    gd.n[1] = (int)grid[1];
-    gd.G = G;
+    const GridDesc<2> gd = make_grid_desc<2>(grid, G);
     const T* pts = points;
     const T* pws = pw;
     // list of the (chunk, group of <= 8 poses) items left to k_co_splat_wide: a counter + at most
@@ -1071,10 +1059,7 @@ int pullback_chunkown(hipStream_t st, unsigned flags, const int64_t* grid, int64
                     ws_ ? ws_bytes : (size_t)0);
     const bool sort = !(flags & DPR_FLAG_COHERENT_POINTS);
     char* ws = (char*)ws_;
-    GridDesc<2> gd;
-    gd.n[0] = (int)grid[0];
-    gd.n[1] = (int)grid[1];
-    gd.G = G;
+    const GridDesc<2> gd = make_grid_desc<2>(grid, G);
     const T* pts = points;
     const T* pws = pw;
     T* gp = d_pts;

@@ -223,7 +223,7 @@ static size_t coarse_workspace_bytes(size_t elem, int64_t P) {
     int nblk;
     int64_t chunk;
     coarse_slices(elem, P < 1 ? 1 : P, &nblk, &chunk);
-    return ((size_t)nblk * kCells * 4 + 255) / 256 * 256 + 2 * (size_t)kCells * 4;
+    return align_up((size_t)nblk * kCells * 4) + 2 * (size_t)kCells * 4;
 }
 
 template <typename T, int NI>
@@ -235,7 +235,7 @@ static int coarse_sort_points(hipStream_t st, int64_t P, const T* points, const 
     int64_t chunk;
     coarse_slices(sizeof(T), P, &nblk, &chunk);
     uint32_t* counts = (uint32_t*)ws;
-    uint32_t* totals = (uint32_t*)(ws + ((size_t)nblk * kCells * 4 + 255) / 256 * 256);
+    uint32_t* totals = (uint32_t*)(ws + align_up((size_t)nblk * kCells * 4));
     uint32_t* cell_start = totals + kCells;
     hipLaunchKernelGGL((k_cell_count<T, NI>), dim3(nblk), dim3(kCellThreads), 0, st, P, chunk, points,
                        counts);

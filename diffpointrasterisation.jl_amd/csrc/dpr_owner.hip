@@ -1371,8 +1371,6 @@ __global__ __launch_bounds__(1024) void k_own_reduce(const double* __restrict__ 
 }
 
 // ---------------------------------------------------------------- host side
-static size_t oalign(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct OwnPlan {
     int64_t nSC, nL1, nL2, Bw;
     uint32_t list_cap, cap;
@@ -1402,31 +1400,31 @@ static OwnPlan make_oplan(int op, const OGeom& tg, int64_t P, int64_t B) {
     pl.list_cap = (uint32_t)lc;
     size_t o = 0;
     pl.off_ctl = o;
-    o += oalign((size_t)pl.Bw * kCtlWords * 4);
+    o += align_up((size_t)pl.Bw * kCtlWords * 4);
     pl.off_b0 = o;
-    o += oalign((size_t)(pl.nSC + 1) * sizeof(IBox) * pl.Bw);
+    o += align_up((size_t)(pl.nSC + 1) * sizeof(IBox) * pl.Bw);
     pl.off_b1 = o;
-    o += oalign((size_t)(pl.nL1 + 1) * sizeof(IBox) * pl.Bw);
+    o += align_up((size_t)(pl.nL1 + 1) * sizeof(IBox) * pl.Bw);
     pl.off_b2 = o;
-    o += oalign((size_t)(pl.nL2 + 1) * sizeof(IBox) * pl.Bw);
+    o += align_up((size_t)(pl.nL2 + 1) * sizeof(IBox) * pl.Bw);
     pl.off_mw1 = o;  // max | min non-zero, per chunk
-    o += oalign((size_t)(pl.nL1 + 1) * 4 * 2);
+    o += align_up((size_t)(pl.nL1 + 1) * 4 * 2);
     pl.off_mw2 = o;
-    o += oalign((size_t)(pl.nL2 + 1) * 4);
-    pl.rec_stride = oalign((size_t)tg.NT * sizeof(TileRec));
+    o += align_up((size_t)(pl.nL2 + 1) * 4);
+    pl.rec_stride = align_up((size_t)tg.NT * sizeof(TileRec));
     pl.off_rec = o;
     o += pl.rec_stride * pl.Bw;
-    pl.list_stride = oalign((size_t)pl.list_cap * 4 * tg.NT);
+    pl.list_stride = align_up((size_t)pl.list_cap * 4 * tg.NT);
     pl.off_list = o;
     o += pl.list_stride * pl.Bw;
-    pl.items_stride = oalign((size_t)kBuckets * pl.max_items * sizeof(OwnItem));
+    pl.items_stride = align_up((size_t)kBuckets * pl.max_items * sizeof(OwnItem));
     pl.off_items = o;
     o += pl.items_stride * pl.Bw;
-    pl.split_stride = oalign((size_t)pl.max_split * 4);
+    pl.split_stride = align_up((size_t)pl.max_split * 4);
     pl.off_split = o;
     o += pl.split_stride * pl.Bw;
     pl.off_slabs = o;
-    o += oalign((size_t)pl.max_slabs * kCells * 8);
+    o += align_up((size_t)pl.max_slabs * kCells * 8);
     pl.total = o;
     return pl;
 }
@@ -1445,22 +1443,8 @@ size_t owner_workspace_bytes(int op, const int64_t* grid, int64_t P, int64_t B) 
     OGeom tg;
     if (!make_ogeom(grid, &tg) || P >= ((int64_t)1 << 32)) return (size_t)-1;
     // pullback: per-block partial sums only (at most 8192 blocks, up to 64 poses per launch)
-    if (op == DPR_OP_PULLBACK) return oalign((size_t)8192 * kNVal * 8 * (size_t)(B < 1 ? 1 : (B < 64 ? B : 64)));
+    if (op == DPR_OP_PULLBACK) return align_up((size_t)8192 * kNVal * 8 * (size_t)(B < 1 ? 1 : (B < 64 ? B : 64)));
     return make_oplan(DPR_OP_RASTER, tg, P, B).total;
-}
-
-#define DPR_HIP(expr)                                                                \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess)                                                        \
-            return fail(DPR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-static GridDesc<3> ogrid_desc(const int64_t* grid, int64_t G) {
-    GridDesc<3> gd;
-    for (int d = 0; d < 3; ++d) gd.n[d] = (int)grid[d];
-    gd.G = G;
-    return gd;
 }
 
 static OwnPlanArgs plan_args(const OwnPlan& pl, char* ws) {
@@ -1564,7 +1548,7 @@ int raster_owner(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G,
         return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_CHUNKED raster needs %zu workspace bytes, got %zu", need,
                     ws_ ? ws_bytes : (size_t)0);
     char* ws = (char*)ws_;
-    const GridDesc<3> gd = ogrid_desc(grid, G);
+    const GridDesc<3> gd = make_grid_desc<3>(grid, G);
     const OwnPlan pl = make_oplan(DPR_OP_RASTER, tg, P, B);
     const size_t lds = sizeof(OwnWalkLds) + (size_t)kPCells * 8;
     if (pw) {
@@ -1623,7 +1607,7 @@ int pullback_owner(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
     if (!ws_ || ws_bytes < need)
         return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_CHUNKED pullback needs %zu workspace bytes, got %zu", need,
                     ws_ ? ws_bytes : (size_t)0);
-    const GridDesc<3> gd = ogrid_desc(grid, G);
+    const GridDesc<3> gd = make_grid_desc<3>(grid, G);
     const int nblocks = own_pullback_blocks(P, G);
     int64_t per_block = ((P + nblocks - 1) / nblocks + kDT - 1) / kDT * kDT;
     if (per_block < kDT) per_block = kDT;

@@ -95,8 +95,6 @@ __global__ __launch_bounds__(256) void k_gather_points(int64_t P, const uint32_t
     }
 }
 
-static size_t salign(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static size_t radix_temp_bytes(int64_t P) {
     size_t temp = 0;
     uint32_t* nul = nullptr;
@@ -107,7 +105,7 @@ static size_t radix_temp_bytes(int64_t P) {
 
 size_t sort_workspace_bytes(int64_t P) {
     if (P < 1) P = 1;
-    return salign((size_t)P * 4) * 3 + salign(radix_temp_bytes(P));  // keys in/out, idx in, temp
+    return align_up((size_t)P * 4) * 3 + align_up(radix_temp_bytes(P));  // keys in/out, idx in, temp
 }
 
 template <typename T>
@@ -134,9 +132,9 @@ int sort_points_impl(void* stream, int n_in, int64_t P, const T* points, T* poin
     char* ws = (char*)ws_;
     // workspace: keys_in | keys_out | idx_in | rocPRIM temporary storage
     uint32_t* keys_in = (uint32_t*)ws;
-    uint32_t* keys_out = (uint32_t*)(ws + salign((size_t)P * 4));
-    uint32_t* idx_in = (uint32_t*)(ws + 2 * salign((size_t)P * 4));
-    void* temp = ws + 3 * salign((size_t)P * 4);
+    uint32_t* keys_out = (uint32_t*)(ws + align_up((size_t)P * 4));
+    uint32_t* idx_in = (uint32_t*)(ws + 2 * align_up((size_t)P * 4));
+    void* temp = ws + 3 * align_up((size_t)P * 4);
     size_t temp_bytes = radix_temp_bytes(P);
     const dim3 grid((unsigned)((P + 255) / 256));
     if (n_in == 3 && fine)

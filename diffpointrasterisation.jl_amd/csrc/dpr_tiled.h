@@ -12,6 +12,24 @@ namespace dpr {
 
 int fail(int code, const char* fmt, ...);
 
+// returns DPR_ERR_HIP (message recorded) from the calling function if a HIP call fails
+#define DPR_HIP(expr)                                                                \
+    do {                                                                             \
+        hipError_t e_ = (expr);                                                      \
+        if (e_ != hipSuccess)                                                        \
+            return fail(DPR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// workspace pieces start on 256-byte boundaries
+inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+template <int NO> GridDesc<NO> make_grid_desc(const int64_t* grid, int64_t G) {
+    GridDesc<NO> gd;
+    for (int d = 0; d < NO; ++d) gd.n[d] = (int)grid[d];
+    gd.G = G;
+    return gd;
+}
+
 // records hipEvent k (if stage timing is armed, see dpr_stage_timing_begin) on `st`
 void stage_mark(hipStream_t st);
 

@@ -3229,8 +3229,6 @@ __global__ __launch_bounds__(256) void k_unsort(int64_t P, const uint32_t* __res
 }
 
 // ------------------------------------------------------------------ host side
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // compute units of the current device (cached)
 static int cu_count() {
     static std::mutex mu;
@@ -3568,13 +3566,6 @@ size_t tiled_workspace_bytes(size_t elem, int op, unsigned flags, int n_in, int 
         .total;
 }
 
-#define DPR_HIP(expr)                                                                \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess)                                                        \
-            return fail(DPR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 // Dynamic LDS above 48 KiB has to be allowed per kernel (and per device): done once for the
 // maximum the kernel can ask for (128 KiB of cursors at kMaxTiles), not per call.
 template <typename K> static int allow_big_lds(K kernel, size_t bytes) {
@@ -3822,13 +3813,6 @@ static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGe
                        pl.off_dcursor, pl.off_sdesc, pl.nsub, pl.sub, fused ? 1 : 0, ra);
     stage_mark(st);
     return DPR_OK;
-}
-
-template <int NO> static GridDesc<NO> make_grid_desc(const int64_t* grid, int64_t G) {
-    GridDesc<NO> gd;
-    for (int d = 0; d < NO; ++d) gd.n[d] = (int)grid[d];
-    gd.G = G;
-    return gd;
 }
 
 template <typename T, int NI, int NO>
@@ -4181,6 +4165,57 @@ bool tiled_channels_supported(int n_out, const int64_t* grid, int64_t P) {
     return P < ((int64_t)1 << 32) && grid_cut(n_out, grid, &sc) && sc.nslab == 1;
 }
 
+// What the channel forward and the JVP share on DPR_ALGO_TILED: the one-pose plan of a single-slab grid, every pose
+// binned once (the binning ignores the weights: 4-word records carry the point index), and the halo pass of each
+// plane the caller's splat wrote.  The caller's own part of the workspace follows the plan's.
+template <typename T, int NI, int NO>
+struct PoseBinning {
+    Plan pl;
+    GridDesc<NO> gd;
+    TileGeom<NO> tg;
+    char* ws;
+    T* halo;
+    T* ovf;
+    unsigned pass_blocks;  // of the caller's one pass over the binned records
+
+    // the support and workspace checks (`path` and `call` name the caller in the messages), the plan
+    int init(const int64_t* grid, int64_t G, int64_t P, size_t need, void* ws_, size_t ws_bytes, const char* path,
+             const char* call) {
+        if (!tiled_channels_supported(NO, grid, P))
+            return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                        "%s: per-pose binning of a grid of at most %d tiles and P < 2^32 only", path, kMaxTiles);
+        SlabCut sc;
+        (void)make_slab_cut<NO>(grid, &sc);
+        pl = channel_plan(sizeof(T), NI, NO, sc, P);
+        if (!ws_ || ws_bytes < need)
+            return fail(DPR_ERR_WORKSPACE, "%s needs %zu workspace bytes, got %zu", call, need,
+                        ws_ ? ws_bytes : (size_t)0);
+        ws = (char*)ws_;
+        gd = make_grid_desc<NO>(grid, G);
+        tg = slab_geom<NO>(grid, sc, 0, true);
+        halo = (T*)(ws + pl.off_aux);
+        ovf = (T*)(ws + pl.off_aux + align_up((size_t)tg.NT * halo_count<NO>() * sizeof(T)));
+        int64_t blocks = (P + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        if (blocks < 1) blocks = 1;
+        pass_blocks = (unsigned)blocks;
+        return DPR_OK;
+    }
+    int bin(hipStream_t st, int64_t P, const T* points, const T* rot, const T* trans, const T* pw, int64_t b) const {
+        return bin_points<T, NI, NO>(st, gd, tg, pl, ws, P, points, (const T*)nullptr, rot, trans, b, 1, true, false,
+                                     points, pw);
+    }
+    const Rec4<T>* rec() const { return (const Rec4<T>*)(ws + pl.off_rec); }
+    const uint32_t* n_rec() const { return (const uint32_t*)(ws + pl.off_tile_start) + tg.NT; }
+    // the halos of the plane `out` (background bg[0] for the low-face cells)
+    void halo_gather(hipStream_t st, const T* bg, T* out) const {
+        hipLaunchKernelGGL((k_halo_gather<T, NO>), dim3(tg.NT + kSplitGrid), dim3(256), 0, st, gd, tg, (const T*)halo,
+                           (const T*)ovf, (const uint32_t*)(ws + pl.off_tparts), (const uint32_t*)(ws + pl.off_tslab),
+                           (const uint32_t*)(ws + pl.off_split) + 1, (const uint32_t*)(ws + pl.off_split), bg,
+                           (int64_t)0, 1, out);
+    }
+};
+
 size_t tiled_channels_workspace_bytes(size_t elem, int n_in, int n_out, const int64_t* grid, int64_t P,
                                       int64_t B, int C) {
     if (!tiled_channels_supported(n_out, grid, P)) return (size_t)-1;
@@ -4198,38 +4233,22 @@ template <typename T, int NI, int NO>
 int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C, T* out,
                           const T* points, const T* rot, const T* trans, const T* bg, const T* ow,
                           const T* pw, void* ws_, size_t ws_bytes) {
-    if (!tiled_channels_supported(NO, grid, P))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "DPR_ALGO_TILED with channels: per-pose binning of a grid of at most %d tiles and P < 2^32 "
-                    "only", kMaxTiles);
-    SlabCut sc;
-    (void)make_slab_cut<NO>(grid, &sc);
-    const Plan pl = channel_plan(sizeof(T), NI, NO, sc, P);
     const size_t need = tiled_channels_workspace_bytes(sizeof(T), NI, NO, grid, P, B, C);
-    if (!ws_ || ws_bytes < need)
-        return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_TILED channel raster needs %zu workspace bytes, got %zu", need,
-                    ws_ ? ws_bytes : (size_t)0);
-    char* ws = (char*)ws_;
+    PoseBinning<T, NI, NO> pb;
+    if (int rc = pb.init(grid, G, P, need, ws_, ws_bytes, "DPR_ALGO_TILED with channels",
+                         "DPR_ALGO_TILED channel raster"))
+        return rc;
+    const Plan& pl = pb.pl;
+    char* const ws = pb.ws;
     const size_t off_ch = need - channel_part_bytes(sizeof(T), P, C);
     T* w_sorted = (T*)(ws + off_ch);
     uint32_t* keys = (uint32_t*)(ws + off_ch + align_up((size_t)C * (size_t)(P + 1) * sizeof(T)));
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    const TileGeom<NO> tg = slab_geom<NO>(grid, sc, 0, true);
-    T* halo = (T*)(ws + pl.off_aux);
-    T* ovf = (T*)(ws + pl.off_aux + align_up((size_t)tg.NT * halo_count<NO>() * sizeof(T)));
     for (int64_t b = 0; b < B; ++b) {
-        // the binning ignores the weights (4-word records carry the point index)
-        if (int rc = bin_points<T, NI, NO>(st, gd, tg, pl, ws, P, points, (const T*)nullptr, rot, trans, b, 1,
-                                           true, false, points, pw))
-            return rc;
+        if (int rc = pb.bin(st, P, points, rot, trans, pw, b)) return rc;
         if (pw) {
             DPR_HIP(hipMemsetAsync(keys, 0, (size_t)C * 2 * 4, st));
-            int64_t blocks = (P + 255) / 256;
-            if (blocks > 4096) blocks = 4096;
-            if (blocks < 1) blocks = 1;
-            hipLaunchKernelGGL(k_channel_weights<T>, dim3((unsigned)blocks), dim3(256), 0, st, P, C, pw,
-                               (const Rec4<T>*)(ws + pl.off_rec), (const uint32_t*)(ws + pl.off_tile_start) + tg.NT,
-                               w_sorted, P + 1, keys);
+            hipLaunchKernelGGL(k_channel_weights<T>, dim3(pb.pass_blocks), dim3(256), 0, st, P, C, pw, pb.rec(),
+                               pb.n_rec(), w_sorted, P + 1, keys);
         }
         // one pass per channel; the pose's parameters, background and plane are passed as pose 0
         const T* rot_b = rot + b * (NO * NI);
@@ -4240,23 +4259,20 @@ int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_
             T* out_c = out + (b * C + c) * G;
             if (pw)
                 hipLaunchKernelGGL((k_tile_splat<T, NI, NO, true, false, true>), dim3(pl.max_items),
-                                   dim3(kSplatThreads), 0, st, gd, tg, (const Rec4<T>*)(ws + pl.off_rec),
+                                   dim3(kSplatThreads), 0, st, pb.gd, pb.tg, pb.rec(),
                                    (const WorkItem*)(ws + pl.off_items), (const uint32_t*)(ws + pl.off_nitems),
                                    (const uint32_t*)(ws + pl.off_tslab), rot_b, trans_b, ow_b, bg_c, (int64_t)0,
-                                   out_c, halo, ovf, 2, (const uint32_t*)(keys + 2 * c), 1,
+                                   out_c, pb.halo, pb.ovf, 2, (const uint32_t*)(keys + 2 * c), 1,
                                    (const T*)(w_sorted + (int64_t)c * (P + 1)));
             else
                 hipLaunchKernelGGL((k_tile_splat<T, NI, NO, false, false>), dim3(pl.max_items),
-                                   dim3(kSplatThreads), 0, st, gd, tg, (const Rec4<T>*)(ws + pl.off_rec),
+                                   dim3(kSplatThreads), 0, st, pb.gd, pb.tg, pb.rec(),
                                    (const WorkItem*)(ws + pl.off_items), (const uint32_t*)(ws + pl.off_nitems),
                                    (const uint32_t*)(ws + pl.off_tslab), rot_b, trans_b, ow_b, bg_c, (int64_t)0,
-                                   out_c, halo, ovf, 2, (const uint32_t*)(ws + pl.off_nitems) + 2, 1,
+                                   out_c, pb.halo, pb.ovf, 2, (const uint32_t*)(ws + pl.off_nitems) + 2, 1,
                                    (const T*)nullptr);
             stage_mark(st);
-            hipLaunchKernelGGL((k_halo_gather<T, NO>), dim3(tg.NT + kSplitGrid), dim3(256), 0, st, gd, tg,
-                               (const T*)halo, (const T*)ovf, (const uint32_t*)(ws + pl.off_tparts),
-                               (const uint32_t*)(ws + pl.off_tslab), (const uint32_t*)(ws + pl.off_split) + 1,
-                               (const uint32_t*)(ws + pl.off_split), bg_c, (int64_t)0, 1, out_c);
+            pb.halo_gather(st, bg_c, out_c);
             stage_mark(st);
         }
     }
@@ -4322,32 +4338,16 @@ template <typename T, int NI, int NO>
 int raster_tiled_jvp(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
                      const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan,
                      const T* bg_dot, void* ws_, size_t ws_bytes) {
-    if (!tiled_channels_supported(NO, grid, P))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "DPR_ALGO_TILED JVP: per-pose binning of a grid of at most %d tiles and P < 2^32 only", kMaxTiles);
-    SlabCut sc;
-    (void)make_slab_cut<NO>(grid, &sc);
-    const Plan pl = channel_plan(sizeof(T), NI, NO, sc, P);
     const size_t need = tiled_jvp_workspace_bytes(sizeof(T), NI, NO, grid, P);
-    if (!ws_ || ws_bytes < need)
-        return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_TILED JVP needs %zu workspace bytes, got %zu", need,
-                    ws_ ? ws_bytes : (size_t)0);
-    char* ws = (char*)ws_;
+    PoseBinning<T, NI, NO> pb;
+    if (int rc = pb.init(grid, G, P, need, ws_, ws_bytes, "DPR_ALGO_TILED JVP", "DPR_ALGO_TILED JVP")) return rc;
+    const Plan& pl = pb.pl;
+    char* const ws = pb.ws;
     const size_t off_jvp = need - jvp_part_bytes(sizeof(T), P);
     Rec4<T>* coef = (Rec4<T>*)(ws + off_jvp);
     uint32_t* keys = (uint32_t*)(ws + off_jvp + align_up((size_t)(P + 1) * 4 * sizeof(T)));
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    const TileGeom<NO> tg = slab_geom<NO>(grid, sc, 0, true);
-    T* halo = (T*)(ws + pl.off_aux);
-    T* ovf = (T*)(ws + pl.off_aux + align_up((size_t)tg.NT * halo_count<NO>() * sizeof(T)));
-    int64_t blocks = (P + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
     for (int64_t b = 0; b < B; ++b) {
-        // the binning ignores the weights (4-word records carry the point index)
-        if (int rc = bin_points<T, NI, NO>(st, gd, tg, pl, ws, P, points, (const T*)nullptr, rot, trans, b, 1,
-                                           true, false, points, pw))
-            return rc;
+        if (int rc = pb.bin(st, P, points, rot, trans, pw, b)) return rc;
         const T* rot_b = rot + b * (NO * NI);
         const T* trans_b = trans + b * NO;
         const T* ow_b = ow ? ow + b : nullptr;
@@ -4357,24 +4357,20 @@ int raster_tiled_jvp(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, 
             tk.points = tan.points ? tan.points + (int64_t)k * P * NI : nullptr;
             tk.pw = tan.pw ? tan.pw + (int64_t)k * P : nullptr;
             DPR_HIP(hipMemsetAsync(keys, 0, 2 * 4, st));
-            hipLaunchKernelGGL((k_jvp_coeffs<T, NI, NO>), dim3((unsigned)blocks), dim3(256), 0, st, gd, P,
-                               (const Rec4<T>*)(ws + pl.off_rec), (const uint32_t*)(ws + pl.off_tile_start) + tg.NT,
-                               rot_b, trans_b, ow_b, pw, tk, tan.rot ? tan.rot + kb * (NO * NI) : nullptr,
+            hipLaunchKernelGGL((k_jvp_coeffs<T, NI, NO>), dim3(pb.pass_blocks), dim3(256), 0, st, pb.gd, P, pb.rec(),
+                               pb.n_rec(), rot_b, trans_b, ow_b, pw, tk, tan.rot ? tan.rot + kb * (NO * NI) : nullptr,
                                tan.trans ? tan.trans + kb * NO : nullptr, tan.ow ? tan.ow + kb : nullptr, coef, keys);
             stage_mark(st);
             // the pose's parameters, the background tangent and the plane are passed as pose 0
             const T* bg_kb = bg_dot ? bg_dot + kb : nullptr;
             T* out_kb = out_dot + (b * K + k) * G;
             hipLaunchKernelGGL((k_tile_splat<T, NI, NO, true, false, false, true>), dim3(pl.max_items),
-                               dim3(kSplatThreads), 0, st, gd, tg, (const Rec4<T>*)(ws + pl.off_rec),
+                               dim3(kSplatThreads), 0, st, pb.gd, pb.tg, pb.rec(),
                                (const WorkItem*)(ws + pl.off_items), (const uint32_t*)(ws + pl.off_nitems),
                                (const uint32_t*)(ws + pl.off_tslab), rot_b, trans_b, (const T*)nullptr, bg_kb,
-                               (int64_t)0, out_kb, halo, ovf, 2, (const uint32_t*)keys, 1, (const T*)coef);
+                               (int64_t)0, out_kb, pb.halo, pb.ovf, 2, (const uint32_t*)keys, 1, (const T*)coef);
             stage_mark(st);
-            hipLaunchKernelGGL((k_halo_gather<T, NO>), dim3(tg.NT + kSplitGrid), dim3(256), 0, st, gd, tg,
-                               (const T*)halo, (const T*)ovf, (const uint32_t*)(ws + pl.off_tparts),
-                               (const uint32_t*)(ws + pl.off_tslab), (const uint32_t*)(ws + pl.off_split) + 1,
-                               (const uint32_t*)(ws + pl.off_split), bg_kb, (int64_t)0, 1, out_kb);
+            pb.halo_gather(st, bg_kb, out_kb);
             stage_mark(st);
         }
     }
@@ -4406,12 +4402,12 @@ DPR_INST(double, 3, 2)
 // permutation sorted position -> original index.  `scratch`: coarse_sort_scratch_bytes(sizeof(T), P) bytes
 // (slice histograms | inverse permutation, which this caller does not use).
 size_t coarse_sort_scratch_bytes(size_t elem, int64_t P) {
-    return (coarse_workspace_bytes(elem, P) + 255) / 256 * 256 + (size_t)(P < 1 ? 1 : P) * 4;
+    return align_up(coarse_workspace_bytes(elem, P)) + (size_t)(P < 1 ? 1 : P) * 4;
 }
 template <typename T>
 int coarse_sort_with_perm(hipStream_t st, int n_in, int64_t P, const T* points, const T* pw, T* points_sorted,
                           T* pw_sorted, uint32_t* perm, char* scratch) {
-    uint32_t* inv = (uint32_t*)(scratch + (coarse_workspace_bytes(sizeof(T), P) + 255) / 256 * 256);
+    uint32_t* inv = (uint32_t*)(scratch + align_up(coarse_workspace_bytes(sizeof(T), P)));
     if (n_in == 3) return coarse_sort_points<T, 3>(st, P, points, pw, points_sorted, pw_sorted, inv, scratch, perm);
     if (n_in == 2) return coarse_sort_points<T, 2>(st, P, points, pw, points_sorted, pw_sorted, inv, scratch, perm);
     return fail(DPR_ERR_UNSUPPORTED_DIMS, "coarse cell sort: n_in = %d", n_in);

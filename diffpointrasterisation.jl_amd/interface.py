@@ -117,19 +117,42 @@ def _stream_ptr(device) -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-def _workspace(op, algo, suf, n_in, n_out, grid_arr, P, B, device, workspace, flags=0):
-    need = getattr(_lib.lib(), f"dpr_workspace_bytes_ex_{suf}")(
-        op, algo, flags, n_in, n_out, grid_arr.ctypes.data_as(ctypes.c_void_p), P, B)
-    if need == ctypes.c_size_t(-1).value:
-        raise _lib.DprError(_lib.ERR_INVALID_ARG, _lib.last_error())
+def _grid_arr(grid):
+    """The grid sizes as the int64 array the C ABI reads."""
+    import numpy as np
+
+    return np.asarray(tuple(int(n) for n in grid), dtype=np.int64)
+
+
+def _algo_name(rc: int) -> str:
+    """Name of a resolved DPR_ALGO_* value; an error status raises."""
+    if rc < 0:
+        _lib.check(rc)
+    return {v: k for k, v in _lib.ALGOS.items()}[rc]
+
+
+# what a workspace query returns when it refuses the call (SIZE_MAX)
+_REFUSED = ctypes.c_size_t(-1).value
+
+
+def _allocate(need, device, workspace):
+    """(workspace, bytes) for a queried `need`: none for 0, else the caller's buffer if it holds `need` bytes on
+    `device`, or a new one."""
     if need == 0:
         return None, 0
     if workspace is not None:
         if workspace.device != device or workspace.numel() * workspace.element_size() < need:
             raise ValueError(f"workspace too small: need {need} bytes")
         return workspace, workspace.numel() * workspace.element_size()
-    ws = torch.empty(need, dtype=torch.uint8, device=device)
-    return ws, need
+    return torch.empty(need, dtype=torch.uint8, device=device), need
+
+
+def _workspace(op, algo, suf, n_in, n_out, grid_arr, P, B, device, workspace, flags=0):
+    need = getattr(_lib.lib(), f"dpr_workspace_bytes_ex_{suf}")(
+        op, algo, flags, n_in, n_out, grid_arr.ctypes.data_as(ctypes.c_void_p), P, B)
+    if need == _REFUSED:
+        raise _lib.DprError(_lib.ERR_INVALID_ARG, _lib.last_error())
+    return _allocate(need, device, workspace)
 
 
 def workspace_bytes(op: str, grid_size, n_points: int, batch: int, n_in: int, dtype=torch.float32,
@@ -139,9 +162,7 @@ def workspace_bytes(op: str, grid_size, n_points: int, batch: int, n_in: int, dt
     bounds how many poses of a batch the tiled path bins together -- the speed / memory trade of
     DPR_FLAG_MAX_POSE_GROUP (include/dpr.h).  `sharing`: the calls will carry keep_binning /
     reuse_binning (`algo="auto"` then sizes for the algorithm the pair runs)."""
-    import numpy as np
-
-    grid_arr = np.asarray(grid_size, dtype=np.int64)
+    grid_arr = _grid_arr(grid_size)
     opc = {"raster": _lib.OP_RASTER, "pullback": _lib.OP_PULLBACK,
            "residual_pullback": _lib.OP_RESIDUAL_PULLBACK}[op]
     need = getattr(_lib.lib(), f"dpr_workspace_bytes_ex_{_SUFFIX[dtype]}")(
@@ -149,7 +170,7 @@ def workspace_bytes(op: str, grid_size, n_points: int, batch: int, n_in: int, dt
         | (_lib.FLAG_COHERENT_POINTS if coherent_points else 0)
         | (_lib.FLAG_KEEP_BINNING if sharing else 0), n_in, len(grid_size),
         grid_arr.ctypes.data_as(ctypes.c_void_p), n_points, batch)
-    if need == ctypes.c_size_t(-1).value:
+    if need == _REFUSED:
         raise _lib.DprError(_lib.ERR_INVALID_ARG, _lib.last_error())
     return int(need)
 
@@ -159,26 +180,20 @@ def resolve_algo(op: str, grid_size, n_points: int, batch: int, n_in: int, *,
     """Name of the algorithm `algo="auto"` picks for this problem.  `sharing`: the call carries
     keep_binning / reuse_binning (the choice is then made for the raster + pullback pair, see
     include/dpr.h)."""
-    import numpy as np
-
-    grid_arr = np.asarray(grid_size, dtype=np.int64)
+    grid_arr = _grid_arr(grid_size)
     opc = {"raster": _lib.OP_RASTER, "pullback": _lib.OP_PULLBACK,
            "residual_pullback": _lib.OP_RESIDUAL_PULLBACK}[op]
     flags = (_lib.FLAG_KEEP_BINNING if sharing else 0) | (_lib.FLAG_COHERENT_POINTS if coherent_points else 0)
     rc = _lib.lib().dpr_resolve_algo_ex(opc, flags, n_in, len(grid_size),
                                         grid_arr.ctypes.data_as(ctypes.c_void_p), n_points, batch)
-    if rc < 0:
-        _lib.check(rc)
-    return {v: k for k, v in _lib.ALGOS.items()}[rc]
+    return _algo_name(rc)
 
 
 def sharing_effective(grid_size, n_points: int, batch: int, n_in: int, *,
                       coherent_points: bool = False) -> bool:
     """Will `algo="auto"` honour keep_binning / reuse_binning for this problem
     (dpr_resolve_flags_ex)?  False where the pair's algorithm has nothing to share."""
-    import numpy as np
-
-    grid_arr = np.asarray(grid_size, dtype=np.int64)
+    grid_arr = _grid_arr(grid_size)
     flags = _lib.FLAG_KEEP_BINNING | (_lib.FLAG_COHERENT_POINTS if coherent_points else 0)
     rc = _lib.lib().dpr_resolve_flags_ex(_lib.OP_RASTER, flags, n_in, len(grid_size),
                                          grid_arr.ctypes.data_as(ctypes.c_void_p), n_points, batch)
@@ -313,8 +328,6 @@ def raster_(out, points, rotation, translation, background=None, out_weight=None
     `keep_binning=True` (explicit `workspace`, sized with `sharing=True`) leaves the binning of
     every pose (tiled algorithm) or the sorted copy of the cloud (chunk-owner algorithm) in
     `workspace` for `raster_pullback_(..., reuse_binning=True)` with the same arguments."""
-    import numpy as np
-
     c = _canonicalise(points, rotation, translation, background, out_weight, point_weight)
     if not isinstance(out, torch.Tensor) or out.device != c["device"]:
         raise RuntimeError("out must be a tensor on the same HIP device as points")
@@ -329,7 +342,7 @@ def raster_(out, points, rotation, translation, background=None, out_weight=None
     if not _is_grid_layout(out):
         raise ValueError("out must have the reference memory order (use empty_grid/to_grid_layout)")
     grid = tuple(out.shape[: c["n_out"]])
-    grid_arr = np.asarray(grid, dtype=np.int64)
+    grid_arr = _grid_arr(grid)
     suf = _SUFFIX[c["dtype"]]
     algo_c = _lib.ALGOS[algo]
     with torch.cuda.device(c["device"]):
@@ -401,8 +414,6 @@ def _pullback(ds_dout, residual, points, rotation, translation, background, out_
               point_weight, ds_dpoints, ds_drotation, ds_dtranslation, ds_dbackground,
               ds_dout_weight, ds_dpoint_weight, algo, workspace, reuse_binning,
               max_pose_group=0, coherent_points=False, point_weight_grad=True):
-    import numpy as np
-
     c = _canonicalise(points, rotation, translation, background, out_weight, point_weight,
                       extra=(ds_dout,))
     dev, dtype, P, B, n_in, n_out = c["device"], c["dtype"], c["P"], c["B"], c["n_in"], c["n_out"]
@@ -417,7 +428,7 @@ def _pullback(ds_dout, residual, points, rotation, translation, background, out_
     if not _is_grid_layout(g):
         g = to_grid_layout(g)
     grid = tuple(g.shape[:n_out])
-    grid_arr = np.asarray(grid, dtype=np.int64)
+    grid_arr = _grid_arr(grid)
     tgt = None
     if residual is not None:
         target, res_scale, loss = residual

@@ -27,17 +27,11 @@ import torch
 
 from . import _lib
 from .channels import empty_channel_grid
-from .interface import (DimensionMismatch, _SUFFIX, _canonicalise, _is_grid_layout, _ptr, _stream_ptr,
-                        empty_grid)
+from .interface import (_REFUSED, DimensionMismatch, _SUFFIX, _algo_name, _allocate, _canonicalise, _grid_arr,
+                        _is_grid_layout, _ptr, _stream_ptr, empty_grid)
 
 MAX_TANGENTS = 16
 _NAMES = ("points_dot", "rotation_dot", "translation_dot", "background_dot", "out_weight_dot", "point_weight_dot")
-
-
-def _grid_arr(grid):
-    import numpy as np
-
-    return np.asarray(tuple(int(n) for n in grid), dtype=np.int64)
 
 
 def _n_tangents(tangents):
@@ -53,9 +47,7 @@ def resolve_algo_jvp(grid_size, n_points: int, batch: int, n_in: int, tangents: 
     g = _grid_arr(grid_size)
     rc = _lib.lib().dpr_resolve_algo_jvp(n_in, len(grid_size), g.ctypes.data_as(ctypes.c_void_p), n_points, batch,
                                          tangents)
-    if rc < 0:
-        _lib.check(rc)
-    return {v: k for k, v in _lib.ALGOS.items()}[rc]
+    return _algo_name(rc)
 
 
 def workspace_bytes_jvp(grid_size, n_points: int, batch: int, n_in: int, tangents: int = 1, dtype=torch.float32,
@@ -64,7 +56,7 @@ def workspace_bytes_jvp(grid_size, n_points: int, batch: int, n_in: int, tangent
     g = _grid_arr(grid_size)
     need = getattr(_lib.lib(), f"dpr_workspace_bytes_jvp_ex_{_SUFFIX[dtype]}")(
         _lib.ALGOS[algo], 0, n_in, len(grid_size), g.ctypes.data_as(ctypes.c_void_p), n_points, batch, tangents)
-    if need == ctypes.c_size_t(-1).value:
+    if need == _REFUSED:
         raise _lib.DprError(_lib.ERR_INVALID_ARG, _lib.last_error())
     return int(need)
 
@@ -129,14 +121,8 @@ def raster_jvp_(out_dot, points, rotation, translation, background=None, out_wei
     with torch.cuda.device(dev):
         need = getattr(_lib.lib(), f"dpr_workspace_bytes_jvp_ex_{suf}")(
             algo_c, 0, n_in, n_out, g.ctypes.data_as(ctypes.c_void_p), P, B, K)
-        ws, ws_bytes = None, 0
-        if need not in (0, ctypes.c_size_t(-1).value):  # (a refused query: the entry point reports the status)
-            if workspace is not None:
-                if workspace.device != dev or workspace.numel() * workspace.element_size() < need:
-                    raise ValueError(f"workspace too small: need {need} bytes")
-                ws, ws_bytes = workspace, workspace.numel() * workspace.element_size()
-            else:
-                ws, ws_bytes = torch.empty(need, dtype=torch.uint8, device=dev), need
+        # (a refused query: the entry point itself reports the status, before any launch)
+        ws, ws_bytes = _allocate(0 if need == _REFUSED else need, dev, workspace)
         fn = getattr(_lib.lib(), f"dpr_raster_jvp_ex_{suf}")
         _lib.check(fn(_stream_ptr(dev), algo_c, 0, n_in, n_out, g.ctypes.data_as(ctypes.c_void_p), P, B, K,
                       _ptr(out_dot), _ptr(c["points"]), _ptr(c["rot"]), _ptr(c["trans"]), _ptr(c["ow"]),

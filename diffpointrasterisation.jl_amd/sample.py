@@ -25,18 +25,12 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from .interface import (DimensionMismatch, _SUFFIX, _canonicalise, _is_grid_layout, _ptr, _stream_ptr,
-                        empty_grid, to_grid_layout)
+from .interface import (_REFUSED, DimensionMismatch, _SUFFIX, _algo_name, _allocate, _canonicalise, _grid_arr,
+                        _is_grid_layout, _ptr, _stream_ptr, empty_grid, to_grid_layout)
 
 SamplePullbackResult = namedtuple("SamplePullbackResult", ["image", "points", "rotation", "translation"])
 _NAMES = SamplePullbackResult._fields
 _OPS = {"raster": _lib.OP_RASTER, "sample": _lib.OP_RASTER, "pullback": _lib.OP_PULLBACK}
-
-
-def _grid_arr(grid):
-    import numpy as np
-
-    return np.asarray(tuple(int(n) for n in grid), dtype=np.int64)
 
 
 def resolve_algo_sample(op: str, grid_size, n_points: int, batch: int, n_in: int) -> str:
@@ -45,9 +39,7 @@ def resolve_algo_sample(op: str, grid_size, n_points: int, batch: int, n_in: int
     g = _grid_arr(grid_size)
     rc = _lib.lib().dpr_resolve_algo_sample(_OPS[op], n_in, len(grid_size), g.ctypes.data_as(ctypes.c_void_p),
                                             n_points, batch)
-    if rc < 0:
-        _lib.check(rc)
-    return {v: k for k, v in _lib.ALGOS.items()}[rc]
+    return _algo_name(rc)
 
 
 def workspace_bytes_sample(op: str, grid_size, n_points: int, batch: int, n_in: int, dtype=torch.float32,
@@ -56,7 +48,7 @@ def workspace_bytes_sample(op: str, grid_size, n_points: int, batch: int, n_in: 
     g = _grid_arr(grid_size)
     need = getattr(_lib.lib(), f"dpr_workspace_bytes_sample_ex_{_SUFFIX[dtype]}")(
         _OPS[op], _lib.ALGOS[algo], 0, n_in, len(grid_size), g.ctypes.data_as(ctypes.c_void_p), n_points, batch)
-    if need == ctypes.c_size_t(-1).value:
+    if need == _REFUSED:
         raise _lib.DprError(_lib.ERR_INVALID_ARG, _lib.last_error())
     return int(need)
 
@@ -65,14 +57,8 @@ def _workspace(op, algo_c, suf, n_in, grid, P, B, device, workspace):
     g = _grid_arr(grid)
     need = getattr(_lib.lib(), f"dpr_workspace_bytes_sample_ex_{suf}")(
         op, algo_c, 0, n_in, len(grid), g.ctypes.data_as(ctypes.c_void_p), P, B)
-    if need == ctypes.c_size_t(-1).value or need == 0:
-        # (a refused query: the entry point itself reports the status, before any launch)
-        return None, 0
-    if workspace is not None:
-        if workspace.device != device or workspace.numel() * workspace.element_size() < need:
-            raise ValueError(f"workspace too small: need {need} bytes")
-        return workspace, workspace.numel() * workspace.element_size()
-    return torch.empty(need, dtype=torch.uint8, device=device), need
+    # (a refused query: the entry point itself reports the status, before any launch)
+    return _allocate(0 if need == _REFUSED else need, device, workspace)
 
 
 def _image(image, c):
