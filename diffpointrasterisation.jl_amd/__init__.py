@@ -16,6 +16,8 @@ from .channels import (empty_channel_grid, raster_channels, raster_channels_, ra
 from .sample import (SamplePullbackResult, resolve_algo_sample, sample, sample_, sample_ad, sample_pullback_,
                      workspace_bytes_sample)
 from .jvp import raster_jvp, raster_jvp_, resolve_algo_jvp, workspace_bytes_jvp
+from .clouds import (raster_clouds, raster_clouds_, raster_clouds_ad, raster_pullback_clouds_, resolve_algo_clouds,
+                     workspace_bytes_clouds)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -30,4 +32,6 @@ __all__ = [
     "sample", "sample_", "sample_pullback_", "sample_ad", "SamplePullbackResult", "resolve_algo_sample",
     "workspace_bytes_sample",
     "raster_jvp", "raster_jvp_", "resolve_algo_jvp", "workspace_bytes_jvp",
+    "raster_clouds", "raster_clouds_", "raster_pullback_clouds_", "raster_clouds_ad", "resolve_algo_clouds",
+    "workspace_bytes_clouds",
 ]

@@ -59,6 +59,9 @@ EXPORTS = [
     "dpr_sample_ex_f32", "dpr_sample_ex_f64", "dpr_sample_pullback_ex_f32", "dpr_sample_pullback_ex_f64",
     "dpr_resolve_algo_jvp", "dpr_workspace_bytes_jvp_ex_f32", "dpr_workspace_bytes_jvp_ex_f64",
     "dpr_raster_jvp_ex_f32", "dpr_raster_jvp_ex_f64",
+    "dpr_resolve_algo_clouds", "dpr_workspace_bytes_clouds_ex_f32", "dpr_workspace_bytes_clouds_ex_f64",
+    "dpr_raster_clouds_ex_f32", "dpr_raster_clouds_ex_f64",
+    "dpr_raster_pullback_clouds_ex_f32", "dpr_raster_pullback_clouds_ex_f64",
 ]
 
 _lib = None
@@ -183,6 +186,19 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, f"dpr_raster_jvp_ex_{suf}")
         f.restype = i
         f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 12 + [vp, sz]
+    L.dpr_resolve_algo_clouds.restype = i
+    L.dpr_resolve_algo_clouds.argtypes = [i, i, i, vp, i64, i64]
+    for suf in ("f32", "f64"):
+        f = getattr(L, f"dpr_workspace_bytes_clouds_ex_{suf}")
+        f.restype = sz
+        f.argtypes = [i, i, ctypes.c_uint, i, i, vp, i64, i64]
+        # the argument lists of dpr_raster_ex_* / dpr_raster_pullback_ex_*
+        f = getattr(L, f"dpr_raster_clouds_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64] + [vp] * 7 + [vp, sz]
+        f = getattr(L, f"dpr_raster_pullback_clouds_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64] + [vp] * 12 + [vp, sz]
     L.dpr_comm_unique_id.restype = i
     L.dpr_comm_unique_id.argtypes = [vp, sz]
     L.dpr_comm_init.restype = i

@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define DPR_VERSION 108 /* 0.1.8: + forward-mode derivative of raster (dpr_raster_jvp_ex_*) */
+#define DPR_VERSION 109 /* 0.1.9: + per-pose point clouds (dpr_raster_clouds_ex_*) */
 
 /* status codes */
 #define DPR_OK 0
@@ -132,7 +132,9 @@ extern "C" {
    DPR_ALGO_TILED: AUTO takes DPR_ALGO_TILED where the single-channel rule above prefers it for the shape
    and the grid is one slab, DPR_ALGO_ATOMIC otherwise (always for the pullback).
    The sampling entry points (SAMPLING below) run DPR_ALGO_ATOMIC for the forward; their pullback takes
-   DPR_ALGO_TILED where the single-pose forward of the shape would, DPR_ALGO_ATOMIC otherwise. */
+   DPR_ALGO_TILED where the single-pose forward of the shape would, DPR_ALGO_ATOMIC otherwise.
+   The per-pose cloud entry points (PER-POSE CLOUDS below) run DPR_ALGO_ATOMIC, DPR_ALGO_TILED (the single-pose
+   tiled calls, pose by pose) or DPR_ALGO_CHUNKED (pose-owned LDS tiles). */
 
 /* SUMMATION ORDER.  The reference promises none for its float atomics (src/raster.jl:64) and sums
  * serially per pose on the CPU (src/raster_pullback.jl:39-72).  Here, per algorithm and output:
@@ -180,6 +182,19 @@ extern "C" {
  *   DPR_ALGO_ATOMIC      global float atomics, each contribution     one thread per point, poses in index   as DPR_ALGO_ATOMIC; the channels are
  *                        the single-channel value: rounding level    order, channels folded per gather:     folded per gather before the sums:
  *                                                                    bit-reproducible                       rounding level
+ *
+ *   per-pose clouds (dpr_raster_clouds_ex_* / dpr_raster_pullback_clouds_ex_*, see PER-POSE CLOUDS below):
+ *   DPR_ALGO_ATOMIC      global float atomics: rounding level        one thread per (point, pose), one      wave -> block -> one float atomic per block:
+ *                                                                    plain store: bit-reproducible; B = 1   rounding level
+ *                                                                    = dpr_raster_pullback_ex_* ATOMIC
+ *   DPR_ALGO_TILED       plane b = dpr_raster_ex_*(DPR_ALGO_TILED)   ds_dpoints[b] = dpr_raster_pullback_   those of the single-pose tiled pullback of
+ *                        of (cloud b, pose b), bit for bit           ex_*(DPR_ALGO_TILED) of pose b         pose b
+ *   DPR_ALGO_CHUNKED     fp32, one slice per (pose, tile): 64-bit    the owner tile of a (point, pose)      per-thread sums in T over a fixed set of
+ *                        fixed point per pose, EXACT -- the same     stores it once: bit-reproducible       points, f64 across waves, one partial per
+ *                        bits for any order of the cloud; several                                           workgroup, partials summed in f64 in a fixed
+ *                        slices: float atomics across slices,                                               order: bit-reproducible run to run
+ *                        rounding level; fp64 / guard tripped:                                              (ds_dbackground: k_grid_sum's block atomics,
+ *                        f64 LDS atomics, rounding level                                                    rounding level on grids of several blocks)
  *
  * "Rounding level" = the differences any two summation orders of the same terms show in the
  * accumulation type; no output depends on the order beyond that.  The contributions themselves
@@ -612,6 +627,76 @@ int dpr_raster_jvp_ex_f64(void *stream, int algo, unsigned flags, int n_in, int 
                           const double *translation_dot, const double *background_dot,
                           const double *out_weight_dot, const double *point_weight_dot, void *workspace,
                           size_t workspace_bytes);
+
+/* ---- PER-POSE CLOUDS: a different point cloud for every pose -------------------------------------------------
+ * For pose b, with its own cloud points[b]:
+ *     out[i.., b] = background[b] + out_weight[b] * sum_p point_weight[b, p] * voxel_weight(i..; R_b points[b, p] + t_b)
+ * Plane b is exactly dpr_raster_* of (grid, points[b], R_b, t_b, background[b], out_weight[b], point_weight[b]):
+ * the same cell choice, weights and drop rules.  The pullback decomposes the same way: ds_dpoints[b] and
+ * ds_dpoint_weight[b] are the single-pose gradients of pose b -- disjoint across poses, no sum over poses -- and
+ * the per-pose sums (ds_drotation, ds_dtranslation, ds_dbackground, ds_dout_weight) the single-pose ones.
+ * Layouts (column-major like the rest of this header):
+ *   points, ds_dpoints                 n_in x P x B: cloud b at b * P * n_in (a contiguous (B, P, n_in) tensor)
+ *   point_weight, ds_dpoint_weight     P x B: cloud b's weights at b * P; point_weight NULL => 1
+ *   everything else                    as for dpr_raster_ex_* / dpr_raster_pullback_ex_*
+ * Clouds of different sizes: pad them to a common P with point_weight = 0.  A zero-weight point deposits nothing
+ * and its ds_dpoints come back as 0 (its ds_dpoint_weight is the sensitivity of that weight, which a caller of
+ * padded clouds drops); a point outside the grid gets 0 in both.  All six pullback outputs and `out` are overwritten.
+ * op: DPR_OP_RASTER or DPR_OP_PULLBACK.  Flags: DPR_FLAG_NO_POINT_WEIGHT_GRAD keeps its meaning (ds_dpoint_weight
+ * may then be NULL); DPR_FLAG_COHERENT_POINTS and DPR_FLAG_MAX_POSE_GROUP are accepted and ignored.
+ * Algorithms.  DPR_ALGO_ATOMIC, all 16 (n_in, n_out): one thread per (point, pose) with global float atomics
+ * (forward) or gathers (pullback; point gradients one plain store each, per-pose sums wave -> block -> one atomic
+ * per block); workspace 0.  DPR_ALGO_TILED, (2,2), (3,3), (3,2): dpr_raster_ex_* / dpr_raster_pullback_ex_* with
+ * DPR_ALGO_TILED and B = 1 on (cloud b, pose b), pose after pose on the stream; workspace: the single-pose tiled
+ * one of (grid, P, 1), reused from pose to pose.  DPR_ALGO_CHUNKED, (2,2), (3,3), (3,2): pose-owned LDS tiles
+ * (2-D 128 x 78 cells, 3-D 32 x 16 x 16); a workgroup owns (pose, tile, slice of consecutive points of the
+ * pose's cloud), with as many slices as fill the device.  The forward deposits into its own tile only (fp32:
+ * 64-bit fixed point with the scale and the 2^10 range guard of PRECISION OF THE FIXED-POINT SUMS taken per pose
+ * from |out_weight[b]| * max |point_weight[b, :]|; fp64 and guarded poses: f64 LDS atomics) and flushes with
+ * plain stores (one slice per (pose, tile)) or with float atomics onto the background (several); workspace
+ * (fp32) 4 bytes per pose.  The pullback stages its tile of ds_dout (+ one halo cell on the high side); the tile
+ * that holds a point's reference cell (-1 clamped to 0; tile 0 for a dropped point) writes its gradients;
+ * per-pose sums go to one f64 partial per workgroup, reduced in a fixed order (ds_dbackground: k_grid_sum, one
+ * float atomic per block); workspace 8 * (n_out * n_in + n_out + 1) * B * workgroups per pose bytes.  Every tile
+ * re-reads its slices of the cloud.
+ * AUTO (dpr_resolve_algo_clouds), from the shape alone: DPR_ALGO_CHUNKED where a pose's grid is at most 32 tiles
+ * of DPR_ALGO_CHUNKED -- for the pullback only on 2-D grids of fp32 data; DPR_ALGO_TILED where
+ * dpr_resolve_algo(op, .., P, 1) would choose it for one pose of the shape; DPR_ALGO_ATOMIC otherwise and for
+ * every other pair.  dpr_resolve_algo_clouds answers for fp32 data: an fp64 pullback takes DPR_ALGO_ATOMIC where
+ * it answers DPR_ALGO_CHUNKED.
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): dimensions outside 1..4
+ * DPR_ERR_UNSUPPORTED_DIMS; a bad op, negative P / B, a bad grid, a NULL required pointer, B * P * n_in beyond 2^60
+ * DPR_ERR_INVALID_ARG; DPR_ALGO_TILED / DPR_ALGO_CHUNKED for another pair (or a grid the tiled path refuses), the
+ * KEEP / REUSE flags and DPR_OP_RESIDUAL_PULLBACK DPR_ERR_UNSUPPORTED_ALGO; a workspace smaller than
+ * dpr_workspace_bytes_clouds_ex_* DPR_ERR_WORKSPACE.  dpr_workspace_bytes_clouds_ex_* returns (size_t)-1 on
+ * invalid arguments (0 for DPR_ALGO_ATOMIC); dpr_resolve_algo_clouds a negative status. */
+int dpr_resolve_algo_clouds(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_clouds_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                         const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_clouds_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                         const int64_t *grid, int64_t P, int64_t B);
+int dpr_raster_clouds_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                             int64_t P, int64_t B, float *out, const float *points, const float *rotation,
+                             const float *translation, const float *background, const float *out_weight,
+                             const float *point_weight, void *workspace, size_t workspace_bytes);
+int dpr_raster_clouds_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                             int64_t P, int64_t B, double *out, const double *points, const double *rotation,
+                             const double *translation, const double *background, const double *out_weight,
+                             const double *point_weight, void *workspace, size_t workspace_bytes);
+int dpr_raster_pullback_clouds_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, const float *ds_dout,
+                                      const float *points, const float *rotation, const float *translation,
+                                      const float *out_weight, const float *point_weight, float *ds_dpoints,
+                                      float *ds_drotation, float *ds_dtranslation, float *ds_dbackground,
+                                      float *ds_dout_weight, float *ds_dpoint_weight, void *workspace,
+                                      size_t workspace_bytes);
+int dpr_raster_pullback_clouds_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, const double *ds_dout,
+                                      const double *points, const double *rotation, const double *translation,
+                                      const double *out_weight, const double *point_weight, double *ds_dpoints,
+                                      double *ds_drotation, double *ds_dtranslation, double *ds_dbackground,
+                                      double *ds_dout_weight, double *ds_dpoint_weight, void *workspace,
+                                      size_t workspace_bytes);
 
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
