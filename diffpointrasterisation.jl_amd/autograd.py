@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import torch
 
+from ._args import _Like, _cast_grads, _restore, _save
 from .jvp import raster_jvp, workspace_bytes_jvp
 from .interface import (empty_grid, raster_, raster_pullback_, resolve_algo, sharing_effective,
                         workspace_bytes)
@@ -73,28 +74,18 @@ class _RasterFn(torch.autograd.Function):
                 algo = f
         raster_(out, points, rotation, translation, background, out_weight, point_weight,
                 algo=algo, workspace=ws, keep_binning=ws is not None)
-        saved = (points, rotation, translation,
-                 *[t for t in (background, out_weight, point_weight) if isinstance(t, torch.Tensor)])
-        ctx.save_for_backward(*saved)
+        saved = _save(ctx, (points, rotation, translation), (background, out_weight, point_weight))
         ctx.save_for_forward(*saved)
         ctx.grid_size, ctx.caller_algo = grid_size, algo_in
-        ctx.opt = tuple(t if not isinstance(t, torch.Tensor) else None
-                        for t in (background, out_weight, point_weight))
-        ctx.opt_is_tensor = tuple(isinstance(t, torch.Tensor)
-                                  for t in (background, out_weight, point_weight))
         ctx.algo, ctx.ws = algo, ws
-        ctx.points_dtype = points_in.dtype
-        ctx.pw_like = (pw_in.shape, pw_in.dtype) if isinstance(pw_in, torch.Tensor) else None
+        # (the saved points / point_weight are the canonical copies: gradients go back as the arguments were)
+        ctx.points_like = _Like(points.shape, points_in.dtype)
+        ctx.pw_like = _Like(pw_in.shape, pw_in.dtype) if isinstance(pw_in, torch.Tensor) else None
         return out
 
     @staticmethod
     def backward(ctx, ds_dout):
-        saved = list(ctx.saved_tensors)
-        points, rotation, translation = saved[:3]
-        rest = saved[3:]
-        opt = []
-        for k in range(3):
-            opt.append(rest.pop(0) if ctx.opt_is_tensor[k] else ctx.opt[k])
+        (points, rotation, translation), opt = _restore(ctx, 3)
         ws, ctx.ws = ctx.ws, None  # the binning is consumed by the pass that reuses it
         need = ctx.needs_input_grad  # (grid_size, algo, points, rotation, translation, bg, ow, pw)
         # the rrule drops the point_weight tangent when that argument was defaulted
@@ -102,29 +93,13 @@ class _RasterFn(torch.autograd.Function):
         pb = raster_pullback_(ds_dout.detach(), points, rotation, translation, *opt,
                               algo=ctx.algo, workspace=ws, reuse_binning=ws is not None,
                               point_weight_grad=bool(ctx.opt_is_tensor[2] and need[7]))
-        grads = [None, None,
-                 pb.points.to(ctx.points_dtype) if need[2] else None,
-                 pb.rotation.to(rotation.dtype) if need[3] else None,
-                 pb.translation.to(translation.dtype) if need[4] else None]
-        for k, g in enumerate((pb.background, pb.out_weight, pb.point_weight)):
-            given = ctx.opt_is_tensor[k] and need[5 + k]
-            if given and k == 2:  # (the saved point_weight is the canonical copy)
-                grads.append(g.reshape(ctx.pw_like[0]).to(ctx.pw_like[1]))
-            elif given:
-                ref = saved[3 + sum(ctx.opt_is_tensor[:k])]
-                grads.append(g.reshape(ref.shape).to(ref.dtype))
-            else:
-                grads.append(None)
-        return tuple(grads)
-
+        like = (ctx.points_like, rotation, translation, opt[0], opt[1], ctx.pw_like)
+        return (None, None, *_cast_grads(need[2:], pb, like))
 
     @staticmethod
     def jvp(ctx, _grid_t, _algo_t, points_t, rotation_t, translation_t, background_t, out_weight_t,
             point_weight_t):
-        saved = list(ctx.saved_tensors)
-        points, rotation, translation = saved[:3]
-        rest = saved[3:]
-        opt = [rest.pop(0) if ctx.opt_is_tensor[k] else ctx.opt[k] for k in range(3)]
+        (points, rotation, translation), opt = _restore(ctx, 3)
         P, n_in = points.shape
         B = 1 if rotation.ndim == 2 else rotation.shape[0]
         algo = ctx.caller_algo if ctx.caller_algo in ("atomic", "tiled") else "auto"

@@ -18,17 +18,18 @@ point_weight (P, C) and background (C,) / (B, C) are per channel.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional, Sequence
 
 import torch
 
 from . import _lib
-from .interface import (_REFUSED, ColumnMajorRotation, DimensionMismatch, PullbackResult, _SUFFIX, _algo_name,
-                        _allocate, _as, _canonicalise, _device_of, _grid_arr, _is_grid_layout, _promote, _ptr,
-                        _stream_ptr, empty_grid, to_grid_layout)
+from ._args import (DimensionMismatch, _alloc_like, _as, _canonicalise, _cast_grads, _detach, _image, _launch,
+                    _op_code, _out_buf, _per_pose, _resolve, _restore, _rotation_buf, _save, _workspace_bytes,
+                    empty_grid)
+from .interface import PullbackResult
 
 MAX_CHANNELS = 16
+_ACCEPTED_OPS = ("raster", "pullback")
 
 
 def empty_channel_grid(grid_size: Sequence[int], channels: int, batch: Optional[int], dtype,
@@ -45,36 +46,19 @@ def _check_channels(C):
 
 def resolve_algo_channels(op: str, grid_size, n_points: int, batch: int, n_in: int, channels: int) -> str:
     """Name of the algorithm `algo="auto"` picks for a channel call (dpr_resolve_algo_channels)."""
-    g = _grid_arr(grid_size)
-    opc = {"raster": _lib.OP_RASTER, "pullback": _lib.OP_PULLBACK}[op]
-    rc = _lib.lib().dpr_resolve_algo_channels(opc, n_in, len(grid_size), g.ctypes.data_as(ctypes.c_void_p),
-                                             n_points, batch, channels)
-    return _algo_name(rc)
+    return _resolve("dpr_resolve_algo_channels", (_op_code(op, _ACCEPTED_OPS),), grid_size, n_points, batch, n_in,
+                    channels)
 
 
 def workspace_bytes_channels(op: str, grid_size, n_points: int, batch: int, n_in: int, channels: int,
                              dtype=torch.float32, algo: str = "auto") -> int:
     """dpr_workspace_bytes_channels_ex_*: device bytes a channel call needs."""
-    g = _grid_arr(grid_size)
-    opc = {"raster": _lib.OP_RASTER, "pullback": _lib.OP_PULLBACK}[op]
-    need = getattr(_lib.lib(), f"dpr_workspace_bytes_channels_ex_{_SUFFIX[dtype]}")(
-        opc, _lib.ALGOS[algo], 0, n_in, len(grid_size), g.ctypes.data_as(ctypes.c_void_p), n_points, batch,
-        channels)
-    if need == _REFUSED:
-        raise _lib.DprError(_lib.ERR_INVALID_ARG, _lib.last_error())
-    return int(need)
-
-
-def _workspace(op, algo_c, suf, n_in, grid, P, B, C, device, workspace, flags):
-    g = _grid_arr(grid)
-    need = getattr(_lib.lib(), f"dpr_workspace_bytes_channels_ex_{suf}")(
-        op, algo_c, flags, n_in, len(grid), g.ctypes.data_as(ctypes.c_void_p), P, B, C)
-    # (a refused query: the entry point itself reports the status, before any launch)
-    return _allocate(0 if need == _REFUSED else need, device, workspace)
+    return _workspace_bytes("_channels", (_op_code(op, _ACCEPTED_OPS), _lib.ALGOS[algo], 0), dtype, grid_size,
+                            n_points, batch, n_in, channels)
 
 
 def _canonicalise_channels(points, rotation, translation, background, out_weight, point_weight, extra=()):
-    """_canonicalise of interface.py plus the channel arguments: point_weight (P, C) -> C x P,
+    """_canonicalise plus the channel arguments: point_weight (P, C) -> C x P,
     background (C,) / (B, C) -> C x B.  Returns the dict of _canonicalise with C, bg, pw set."""
     c = _canonicalise(points, rotation, translation, None, out_weight, None,
                       extra=(background, point_weight) + tuple(extra))
@@ -114,12 +98,7 @@ def _infer_channels(point_weight):
 def raster_channels(grid_size, points, rotation, translation, point_weight, background=None, out_weight=None,
                     *, algo: str = "auto", workspace=None) -> torch.Tensor:
     """Allocating multi-channel forward: returns out[i_1..i_N, c] (single pose) or out[i_1..i_N, c, b]."""
-    device = _device_of(points)
-    rot_like = isinstance(rotation, (torch.Tensor, ColumnMajorRotation))
-    rot_nd = rotation.ndim if rot_like else torch.as_tensor(rotation).ndim
-    dtype = _promote(points, rotation.cm if isinstance(rotation, ColumnMajorRotation) else rotation,
-                     translation, background, out_weight, point_weight)
-    batch = None if rot_nd == 2 else (rotation.shape[0] if rot_like else len(rotation))
+    device, dtype, batch = _alloc_like(points, rotation, translation, background, out_weight, point_weight)
     C = _infer_channels(point_weight)
     _check_channels(C)
     out = empty_channel_grid(tuple(grid_size), C, batch, dtype, device)
@@ -132,32 +111,9 @@ def raster_channels_(out, points, rotation, translation, point_weight, backgroun
     """In-place multi-channel forward: `out` (grid_size + (C,) [+ (B,)], `empty_channel_grid` memory order)
     is fully overwritten and returned.  Enqueued on torch's current stream; not synchronised."""
     c = _canonicalise_channels(points, rotation, translation, background, out_weight, point_weight)
-    if not isinstance(out, torch.Tensor) or out.device != c["device"]:
-        raise RuntimeError("out must be a tensor on the same HIP device as points")
-    n_out, C, B = c["n_out"], c["C"], c["B"]
-    expect_ndim = n_out + 1 + (0 if c["single"] else 1)
-    if out.ndim != expect_ndim:
-        raise DimensionMismatch(
-            f"out has {out.ndim} dims, expected {expect_ndim} for N_out={n_out} and a channel axis")
-    if out.shape[n_out] != C:
-        raise DimensionMismatch(f"out channel dim {out.shape[n_out]} != number of channels {C}")
-    if not c["single"] and out.shape[-1] != B:
-        raise DimensionMismatch(f"out batch dim {out.shape[-1]} != number of poses {B}")
-    if out.dtype != c["dtype"]:
-        raise TypeError(f"out dtype {out.dtype} != promoted argument dtype {c['dtype']}")
-    if not _is_grid_layout(out):
-        raise ValueError("out must have the reference memory order (use empty_channel_grid)")
-    grid = tuple(out.shape[:n_out])
-    g = _grid_arr(grid)
-    suf = _SUFFIX[c["dtype"]]
-    algo_c = _lib.ALGOS[algo]
-    with torch.cuda.device(c["device"]):
-        ws, ws_bytes = _workspace(_lib.OP_RASTER, algo_c, suf, c["n_in"], grid, c["P"], B, C, c["device"],
-                                  workspace, 0)
-        fn = getattr(_lib.lib(), f"dpr_raster_channels_ex_{suf}")
-        _lib.check(fn(_stream_ptr(c["device"]), algo_c, 0, c["n_in"], n_out, g.ctypes.data_as(ctypes.c_void_p),
-                      c["P"], B, C, _ptr(out), _ptr(c["points"]), _ptr(c["rot"]), _ptr(c["trans"]),
-                      _ptr(c["bg"]), _ptr(c["ow"]), _ptr(c["pw"]), _ptr(ws), ws_bytes))
+    _image(out, "out", c, (("channels", c["C"]),), out=True)
+    _launch("_channels", "dpr_raster_channels_ex", _lib.OP_RASTER, c, out.shape[: c["n_out"]], algo, 0, workspace,
+            out, c["points"], c["rot"], c["trans"], c["bg"], c["ow"], c["pw"], tail=(c["C"],))
     return out
 
 
@@ -170,103 +126,43 @@ def raster_pullback_channels_(ds_dout, points, rotation, translation, point_weig
     point_weight (P, C) (None with point_weight_grad=False) and background (C,) or (B, C)."""
     c = _canonicalise_channels(points, rotation, translation, background, out_weight, point_weight,
                                extra=(ds_dout,))
-    dev, dtype, P, B, C = c["device"], c["dtype"], c["P"], c["B"], c["C"]
-    n_in, n_out = c["n_in"], c["n_out"]
-    if not isinstance(ds_dout, torch.Tensor) or ds_dout.device != dev:
-        raise RuntimeError("ds_dout must be a tensor on the same HIP device as points")
-    expect_ndim = n_out + 1 + (0 if c["single"] else 1)
-    if ds_dout.ndim != expect_ndim:
-        raise DimensionMismatch(f"ds_dout has {ds_dout.ndim} dims, expected {expect_ndim}")
-    if ds_dout.shape[n_out] != C:
-        raise DimensionMismatch(f"ds_dout channel dim {ds_dout.shape[n_out]} != number of channels {C}")
-    if not c["single"] and ds_dout.shape[-1] != B:
-        raise DimensionMismatch(f"ds_dout batch dim {ds_dout.shape[-1]} != number of poses {B}")
-    gt = ds_dout.to(dtype)
-    if not _is_grid_layout(gt):
-        gt = to_grid_layout(gt)
-    grid = tuple(gt.shape[:n_out])
-    g = _grid_arr(grid)
-
-    def out_buf(given, shape, name):
-        if given is None:
-            return torch.empty(shape, dtype=dtype, device=dev)
-        if (not isinstance(given, torch.Tensor) or given.device != dev or given.dtype != dtype
-                or tuple(given.shape) != tuple(shape) or not given.is_contiguous()):
-            raise DimensionMismatch(f"{name}: need a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}")
-        return given
-
-    d_pts = out_buf(ds_dpoints, (P, n_in), "ds_dpoints")
-    if ds_drotation is not None:
-        rv = ds_drotation.transpose(-1, -2) if not c["single"] else ds_drotation.t()[None]
-        if rv.shape != (B, n_in, n_out) or not rv.is_contiguous() or rv.dtype != dtype:
-            raise DimensionMismatch(
-                "ds_drotation must be a (B, N_out, N_in) transposed view of a contiguous (B, N_in, N_out) buffer")
-        d_rot = rv
-    else:
-        d_rot = torch.empty((B, n_in, n_out), dtype=dtype, device=dev)
-    d_trans = out_buf(None if ds_dtranslation is None else ds_dtranslation.reshape(B, n_out), (B, n_out),
-                      "ds_dtranslation")
-    d_bg = out_buf(None if ds_dbackground is None else ds_dbackground.reshape(B, C), (B, C), "ds_dbackground")
-    d_ow = out_buf(None if ds_dout_weight is None else ds_dout_weight.reshape(B), (B,), "ds_dout_weight")
+    P, B, C, n_in, n_out = c["P"], c["B"], c["C"], c["n_in"], c["n_out"]
+    gt = _image(ds_dout, "ds_dout", c, (("channels", C),))
+    d_pts = _out_buf(ds_dpoints, (P, n_in), "ds_dpoints", c)
+    d_rot = _rotation_buf(ds_drotation, c)
+    d_trans = _out_buf(ds_dtranslation, (B, n_out), "ds_dtranslation", c, reshape=True)
+    d_bg = _out_buf(ds_dbackground, (B, C), "ds_dbackground", c, reshape=True)
+    d_ow = _out_buf(ds_dout_weight, (B,), "ds_dout_weight", c, reshape=True)
     if not point_weight_grad and ds_dpoint_weight is not None:
         raise ValueError("point_weight_grad=False and a ds_dpoint_weight buffer contradict each other")
-    d_pw = out_buf(ds_dpoint_weight, (P, C), "ds_dpoint_weight") if point_weight_grad else None
-    suf = _SUFFIX[dtype]
-    algo_c = _lib.ALGOS[algo]
+    d_pw = _out_buf(ds_dpoint_weight, (P, C), "ds_dpoint_weight", c) if point_weight_grad else None
     flags = 0 if point_weight_grad else _lib.FLAG_NO_POINT_WEIGHT_GRAD
-    with torch.cuda.device(dev):
-        ws, ws_bytes = _workspace(_lib.OP_PULLBACK, algo_c, suf, n_in, grid, P, B, C, dev, workspace, flags)
-        fn = getattr(_lib.lib(), f"dpr_raster_pullback_channels_ex_{suf}")
-        _lib.check(fn(_stream_ptr(dev), algo_c, flags, n_in, n_out, g.ctypes.data_as(ctypes.c_void_p), P, B, C,
-                      _ptr(gt), _ptr(c["points"]), _ptr(c["rot"]), _ptr(c["trans"]), _ptr(c["ow"]),
-                      _ptr(c["pw"]), _ptr(d_pts), _ptr(d_rot), _ptr(d_trans), _ptr(d_bg), _ptr(d_ow),
-                      _ptr(d_pw), _ptr(ws), ws_bytes))
-    rot_math = d_rot.transpose(1, 2)
-    if c["single"]:
-        return PullbackResult(d_pts, rot_math[0], d_trans[0], d_bg[0], d_ow[0], d_pw)
-    return PullbackResult(d_pts, rot_math, d_trans, d_bg, d_ow, d_pw)
+    _launch("_channels", "dpr_raster_pullback_channels_ex", _lib.OP_PULLBACK, c, gt.shape[:n_out], algo, flags,
+            workspace, gt, c["points"], c["rot"], c["trans"], c["ow"], c["pw"], d_pts, d_rot, d_trans, d_bg, d_ow,
+            d_pw, tail=(C,))
+    rot, trans, bg, ow = _per_pose(c, d_rot, d_trans, d_bg, d_ow)
+    return PullbackResult(d_pts, rot, trans, bg, ow, d_pw)
 
 
 class _RasterChannelsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, grid_size, algo, points, rotation, translation, point_weight, background, out_weight):
         out = raster_channels(grid_size, points.detach(), rotation.detach(), translation.detach(),
-                              point_weight.detach() if isinstance(point_weight, torch.Tensor) else point_weight,
-                              background.detach() if isinstance(background, torch.Tensor) else background,
-                              out_weight.detach() if isinstance(out_weight, torch.Tensor) else out_weight,
-                              algo=algo)
-        ctx.opt_is_tensor = tuple(isinstance(t, torch.Tensor) for t in (point_weight, background, out_weight))
-        ctx.opt = tuple(None if isinstance(t, torch.Tensor) else t for t in (point_weight, background, out_weight))
-        ctx.save_for_backward(points, rotation, translation,
-                              *[t for t in (point_weight, background, out_weight) if isinstance(t, torch.Tensor)])
+                              _detach(point_weight), _detach(background), _detach(out_weight), algo=algo)
+        _save(ctx, (points, rotation, translation), (point_weight, background, out_weight))
         # forward and pullback pick their algorithms independently (no binning is shared)
         ctx.algo = "atomic" if algo == "tiled" else algo
         return out
 
     @staticmethod
     def backward(ctx, ds_dout):
-        saved = list(ctx.saved_tensors)
-        points, rotation, translation = saved[:3]
-        rest = saved[3:]
-        opt = [rest.pop(0) if ctx.opt_is_tensor[k] else ctx.opt[k] for k in range(3)]
-        pw, bg, ow = opt
+        (points, rotation, translation), opt = _restore(ctx, 3)
         need = ctx.needs_input_grad  # (grid_size, algo, points, rotation, translation, pw, bg, ow)
         pb = raster_pullback_channels_(ds_dout.detach(), points.detach(), rotation.detach(), translation.detach(),
-                                       pw.detach() if isinstance(pw, torch.Tensor) else pw,
-                                       bg.detach() if isinstance(bg, torch.Tensor) else bg,
-                                       ow.detach() if isinstance(ow, torch.Tensor) else ow,
-                                       algo=ctx.algo, point_weight_grad=bool(ctx.opt_is_tensor[0] and need[5]))
-        grads = [None, None,
-                 pb.points.to(points.dtype) if need[2] else None,
-                 pb.rotation.to(rotation.dtype) if need[3] else None,
-                 pb.translation.to(translation.dtype) if need[4] else None]
-        for k, gr in enumerate((pb.point_weight, pb.background, pb.out_weight)):
-            t = opt[k]
-            if ctx.opt_is_tensor[k] and need[5 + k]:
-                grads.append(gr.reshape(t.shape).to(t.dtype))
-            else:
-                grads.append(None)
-        return tuple(grads)
+                                       *map(_detach, opt), algo=ctx.algo,
+                                       point_weight_grad=bool(ctx.opt_is_tensor[0] and need[5]))
+        grads = (pb.points, pb.rotation, pb.translation, pb.point_weight, pb.background, pb.out_weight)
+        return (None, None, *_cast_grads(need[2:], grads, (points, rotation, translation, *opt)))
 
 
 def raster_channels_ad(grid_size, points, rotation, translation, point_weight, background=None, out_weight=None,

@@ -21,14 +21,11 @@ The primal background does not enter; out_weight / point_weight None mean 1, as 
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
+from ._args import DimensionMismatch, _canonicalise, _image, _launch, _resolve, _workspace_bytes, empty_grid
 from .channels import empty_channel_grid
-from .interface import (_REFUSED, DimensionMismatch, _SUFFIX, _algo_name, _allocate, _canonicalise, _grid_arr,
-                        _is_grid_layout, _ptr, _stream_ptr, empty_grid)
 
 MAX_TANGENTS = 16
 _NAMES = ("points_dot", "rotation_dot", "translation_dot", "background_dot", "out_weight_dot", "point_weight_dot")
@@ -44,21 +41,13 @@ def _n_tangents(tangents):
 
 def resolve_algo_jvp(grid_size, n_points: int, batch: int, n_in: int, tangents: int = 1) -> str:
     """Name of the algorithm `algo="auto"` picks for a JVP call (dpr_resolve_algo_jvp)."""
-    g = _grid_arr(grid_size)
-    rc = _lib.lib().dpr_resolve_algo_jvp(n_in, len(grid_size), g.ctypes.data_as(ctypes.c_void_p), n_points, batch,
-                                         tangents)
-    return _algo_name(rc)
+    return _resolve("dpr_resolve_algo_jvp", (), grid_size, n_points, batch, n_in, tangents)
 
 
 def workspace_bytes_jvp(grid_size, n_points: int, batch: int, n_in: int, tangents: int = 1, dtype=torch.float32,
                         algo: str = "auto") -> int:
     """dpr_workspace_bytes_jvp_ex_*: device bytes a JVP call needs."""
-    g = _grid_arr(grid_size)
-    need = getattr(_lib.lib(), f"dpr_workspace_bytes_jvp_ex_{_SUFFIX[dtype]}")(
-        _lib.ALGOS[algo], 0, n_in, len(grid_size), g.ctypes.data_as(ctypes.c_void_p), n_points, batch, tangents)
-    if need == _REFUSED:
-        raise _lib.DprError(_lib.ERR_INVALID_ARG, _lib.last_error())
-    return int(need)
+    return _workspace_bytes("_jvp", (_lib.ALGOS[algo], 0), dtype, grid_size, n_points, batch, n_in, tangents)
 
 
 def _tangent(t, name, c, lead, shape, flat, scalar_ok=False):
@@ -89,8 +78,7 @@ def raster_jvp_(out_dot, points, rotation, translation, background=None, out_wei
     current stream; not synchronised."""
     K = _n_tangents(tangents)
     c = _canonicalise(points, rotation, translation, background, out_weight, point_weight)
-    dev, dtype, P, B, n_in, n_out, single = (c["device"], c["dtype"], c["P"], c["B"], c["n_in"], c["n_out"],
-                                             c["single"])
+    P, B, n_in, n_out, single = c["P"], c["B"], c["n_in"], c["n_out"], c["single"]
     lead = () if tangents is None else (K,)
     pose = () if single else (B,)
     td = dict(
@@ -103,31 +91,10 @@ def raster_jvp_(out_dot, points, rotation, translation, background=None, out_wei
     )
     if td["rot"] is not None:  # column-major per pose, as `rotation`
         td["rot"] = td["rot"].transpose(-1, -2).contiguous()
-    if not isinstance(out_dot, torch.Tensor) or out_dot.device != dev:
-        raise RuntimeError("out_dot must be a tensor on the same HIP device as points")
-    expect_ndim = n_out + len(lead) + len(pose)
-    if out_dot.ndim != expect_ndim:
-        raise DimensionMismatch(f"out_dot has {out_dot.ndim} dims, expected {expect_ndim} for N_out={n_out}")
-    if tuple(out_dot.shape[n_out:]) != lead + pose:
-        raise DimensionMismatch(f"out_dot trailing dims {tuple(out_dot.shape[n_out:])} must be {lead + pose}")
-    if out_dot.dtype != dtype:
-        raise TypeError(f"out_dot dtype {out_dot.dtype} != promoted argument dtype {dtype}")
-    if not _is_grid_layout(out_dot):
-        raise ValueError("out_dot must have the memory order of empty_grid / empty_channel_grid")
-    grid = tuple(out_dot.shape[:n_out])
-    g = _grid_arr(grid)
-    suf = _SUFFIX[dtype]
-    algo_c = _lib.ALGOS[algo]
-    with torch.cuda.device(dev):
-        need = getattr(_lib.lib(), f"dpr_workspace_bytes_jvp_ex_{suf}")(
-            algo_c, 0, n_in, n_out, g.ctypes.data_as(ctypes.c_void_p), P, B, K)
-        # (a refused query: the entry point itself reports the status, before any launch)
-        ws, ws_bytes = _allocate(0 if need == _REFUSED else need, dev, workspace)
-        fn = getattr(_lib.lib(), f"dpr_raster_jvp_ex_{suf}")
-        _lib.check(fn(_stream_ptr(dev), algo_c, 0, n_in, n_out, g.ctypes.data_as(ctypes.c_void_p), P, B, K,
-                      _ptr(out_dot), _ptr(c["points"]), _ptr(c["rot"]), _ptr(c["trans"]), _ptr(c["ow"]),
-                      _ptr(c["pw"]), _ptr(td["points"]), _ptr(td["rot"]), _ptr(td["trans"]), _ptr(td["bg"]),
-                      _ptr(td["ow"]), _ptr(td["pw"]), _ptr(ws), ws_bytes))
+    _image(out_dot, "out_dot", c, [("tangents", k) for k in lead], out=True)
+    _launch("_jvp", "dpr_raster_jvp_ex", None, c, out_dot.shape[:n_out], algo, 0, workspace, out_dot, c["points"],
+            c["rot"], c["trans"], c["ow"], c["pw"], td["points"], td["rot"], td["trans"], td["bg"], td["ow"],
+            td["pw"], tail=(K,))
     return out_dot
 
 

@@ -802,6 +802,14 @@ def test_dimension_errors(dev):
         dpr_amd.raster_(dpr_amd.empty_grid((4, 4), 2, torch.float64, dev), pts, R, t)
     with pytest.raises(dpr_amd.DimensionMismatch):
         dpr_amd.raster_pullback_(dpr_amd.empty_grid((4, 4, 4), 3, torch.float64, dev), pts, R, t)
+    # a ds_drotation buffer on another device never reaches the kernel
+    rot_host = torch.empty(2, 3, 3, dtype=torch.float64).transpose(1, 2)
+    with pytest.raises(dpr_amd.DimensionMismatch):
+        dpr_amd.raster_pullback_(dpr_amd.empty_grid((4, 4, 4), 2, torch.float64, dev), pts, R, t,
+                                 ds_drotation=rot_host)
+    with pytest.raises(dpr_amd.DimensionMismatch):
+        dpr_amd.raster_pullback_channels_(dpr_amd.empty_channel_grid((4, 4, 4), 2, 2, torch.float64, dev),
+                                          pts, R, t, torch.ones(5, 2, **f64), ds_drotation=rot_host)
     # an embedding 2 -> 3 is a legal pair since round 6 (1 <= N_in, N_out <= 4: the reference's generic
     # signatures, src/raster.jl:5-13) ...
     out = dpr_amd.raster((4, 4, 4), torch.zeros(5, 2, **f64), torch.zeros(1, 3, 2, **f64),
