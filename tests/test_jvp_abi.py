@@ -28,33 +28,36 @@ def _g(grid):
 
 
 # ------------------------------------------------------------------ the definition, restated in numpy
-def jvp_reference(grid, points, rot, trans, ow, pw, tan, K, cell_dtype=np.float64):
+def jvp_reference(grid, points, rot, trans, ow, pw, tan, K, cell_dtype=np.float64, value_dtype=np.float64):
     """out_dot (grid..., K, B) in fp64 of the JVP definition in include/dpr.h.  rot (B, N_out, N_in),
     trans (B, N_out), ow (B,) / None, pw (P,) / None; tan: dict kind -> array with a leading K axis (points
     (K, P, N_in), rotation (K, B, N_out, N_in), translation (K, B, N_out), background / out_weight (K, B),
     point_weight (K, P)); missing kinds are zero.  Rejected points read none of their tangents.
     cell_dtype: the precision of the cell choice and the deltas (np.float32: the library's fp32 cells, bit for
-    bit); everything after them is fp64."""
+    bit); everything after them is fp64 -- or value_dtype: np.float32 gives the restatement's own fp32 rounding
+    (every deposit and every running cell sum in fp32, points in index order), the yardstick of an fp32 result."""
     ct = np.dtype(cell_dtype)
+    vt = np.dtype(value_dtype)
     pts_c = np.asarray(points, ct)
     rot_c = np.asarray(rot, ct)
     trans_c = np.asarray(trans, ct)
-    points = np.asarray(points, np.float64)
-    rot = np.asarray(rot, np.float64)
-    trans = np.asarray(trans, np.float64)
+    points = np.asarray(points, vt)
+    rot = np.asarray(rot, vt)
+    trans = np.asarray(trans, vt)
     P, n_in = points.shape
     B, n_out = rot.shape[0], rot.shape[1]
-    ow = np.ones(B) if ow is None else np.asarray(ow, np.float64)
-    pw = np.ones(P) if pw is None else np.asarray(pw, np.float64)
-    z = lambda shape: np.zeros(shape)
-    pd = tan.get("points", z((K, P, n_in)))
-    rd = tan.get("rotation", z((K, B, n_out, n_in)))
-    td = tan.get("translation", z((K, B, n_out)))
-    bgd = tan.get("background", z((K, B)))
-    owd = tan.get("out_weight", z((K, B)))
-    pwd = tan.get("point_weight", z((K, P)))
-    out = np.zeros(tuple(grid) + (K, B), order="F")
-    n = np.asarray(grid, np.float64)
+    ow = np.ones(B, vt) if ow is None else np.asarray(ow, vt)
+    pw = np.ones(P, vt) if pw is None else np.asarray(pw, vt)
+    z = lambda shape: np.zeros(shape, vt)
+    t = lambda kind, shape: np.asarray(tan[kind], vt) if kind in tan else z(shape)
+    pd = t("points", (K, P, n_in))
+    rd = t("rotation", (K, B, n_out, n_in))
+    td = t("translation", (K, B, n_out))
+    bgd = t("background", (K, B))
+    owd = t("out_weight", (K, B))
+    pwd = t("point_weight", (K, P))
+    out = np.zeros(tuple(grid) + (K, B), vt, order="F")
+    n = np.asarray(grid, vt)
     for b in range(B):
         # cell and deltas in the library's (the reference's) operation order
         coord = np.empty((P, n_out), dtype=ct)
@@ -67,7 +70,7 @@ def jvp_reference(grid, points, rot, trans, ow, pw, tan, K, cell_dtype=np.float6
         ok = np.all((c > -1) & (c <= n.astype(ct)), axis=1)
         r = np.ceil(np.where(ok[:, None], c, ct.type(0.0)))
         ref0 = r.astype(np.int64) - 1
-        dlo = (coord - (r - ct.type(0.5))).astype(np.float64)
+        dlo = (coord - (r - ct.type(0.5))).astype(vt)
         q = np.nonzero(ok)[0]
         for k in range(K):
             out[..., k, b] = bgd[k, b]
@@ -81,11 +84,11 @@ def jvp_reference(grid, points, rot, trans, ow, pw, tan, K, cell_dtype=np.float6
             plane = out[..., k, b]
             for s in range(1 << n_out):
                 bits = np.array([(s >> d) & 1 for d in range(n_out)])
-                fac = np.where(bits[None, :] == 1, dl, 1.0 - dl)
+                fac = np.where(bits[None, :] == 1, dl, vt.type(1.0) - dl)
                 dep = a * np.prod(fac, axis=1)
                 for m in range(n_out):
-                    others = np.prod(np.delete(fac, m, axis=1), axis=1) if n_out > 1 else np.ones(q.size)
-                    dep = dep + bn[:, m] * (1.0 if bits[m] else -1.0) * others
+                    others = np.prod(np.delete(fac, m, axis=1), axis=1) if n_out > 1 else np.ones(q.size, vt)
+                    dep = dep + bn[:, m] * vt.type(1.0 if bits[m] else -1.0) * others
                 idx = ref0[q] + bits[None, :]
                 inb = np.all((idx >= 0) & (idx < np.asarray(grid)[None, :]), axis=1)
                 np.add.at(plane, tuple(idx[inb].T), dep[inb])
