@@ -214,6 +214,15 @@ extern "C" {
  * fp32 rounding (2^-24 relative) for every cell except far corners of their only contributors (value below
  * ~2^-12 of the local weight), which keep at least 16 good bits.  Default weights (NULL) never trip the guard.
  * tests/test_parity_gpu.py::test_fp32_cells_reached_only_by_small_weights_keep_their_relative_precision.
+ * The scopes of the other op families (each takes maxw and the guard from its own scope, never from the one
+ * before it in the call): MULTI-CHANNEL on DPR_ALGO_TILED -- the channel of a pose, |point_weight[c, :]| of the
+ * points that pose bins; FORWARD-MODE DERIVATIVE on DPR_ALGO_TILED -- the (pose, tangent), with the bound
+ * m_p = |a| + sum_n |b_n| of a record in the place of |point_weight| (out_weight is part of a and b_n);
+ * POINT SAMPLING, ds_dimage on DPR_ALGO_TILED -- the pose: plane b is the single-pose tiled forward with the
+ * column ds_dvalues[:, b] as its weights; PER-POSE CLOUDS on DPR_ALGO_CHUNKED -- the guard per pose, over the
+ * whole cloud point_weight[b, :] (points outside the grid included), the scale per (pose, tile, slice).
+ * tests/test_families_precision_gpu.py holds every one of them to a per-cell bound relative to the weights that
+ * reach the cell.
  *
  * ENVIRONMENT.  DPR_MAX_TILES is the only variable the library reads (16..32768, default 32768): the number
  * of tiles DPR_ALGO_TILED handles per launch sequence before it cuts the grid into slabs along the last axis

@@ -96,6 +96,63 @@ def jvp_reference(grid, points, rot, trans, ow, pw, tan, K, cell_dtype=np.float6
     return out
 
 
+def cell_choice(grid, points, rot_b, trans_b, cell_dtype=np.float64):
+    """(ok (P,), ref0 (P, N_out), coord (P, N_out)) of one pose in `jvp_reference`'s operation order (np.float32:
+    the library's fp32 cells, bit for bit); rejected points have ref0 = -1."""
+    ct = np.dtype(cell_dtype)
+    pts, R, t = np.asarray(points, ct), np.asarray(rot_b, ct), np.asarray(trans_b, ct)
+    n_out, n_in = R.shape
+    coord = np.empty((len(pts), n_out), dtype=ct)
+    for d in range(n_out):
+        proj = R[d, 0] * pts[:, 0]
+        for j in range(1, n_in):
+            proj = proj + R[d, j] * pts[:, j]
+        coord[:, d] = (proj - (ct.type(-1.0) - t[d])) * (ct.type(grid[d]) / ct.type(2))
+    with np.errstate(invalid="ignore"):
+        c = coord - ct.type(0.5)
+        ok = np.all((c > -1) & (c <= np.asarray(grid, ct)), axis=1)
+        ref0 = np.ceil(np.where(ok[:, None], c, ct.type(0.0))).astype(np.int64) - 1
+    return ok, ref0, coord
+
+
+def footprint_sum(grid, ok, ref0, mag):
+    """S (grid...) in fp64: the sum of mag[p] over the accepted points p that touch the cell with any of their
+    2^N corners ref0 + {0, 1}^N."""
+    S = np.zeros(tuple(grid), np.float64)
+    q = np.nonzero(ok)[0]
+    n_out = ref0.shape[1]
+    m = np.asarray(mag, np.float64)[q]
+    for s in range(1 << n_out):
+        idx = ref0[q] + np.array([(s >> d) & 1 for d in range(n_out)])[None, :]
+        inb = np.all((idx >= 0) & (idx < np.asarray(grid)[None, :]), axis=1)
+        np.add.at(S, tuple(idx[inb].T), m[inb])
+    return S
+
+
+def jvp_terms(grid, points, rot, trans, ow, pw, tan, K, b, cell_dtype=np.float64):
+    """(ok (P,), ref0 (P, N_out), a (K, P), bn (K, P, N_out)) of pose b: the coefficients of `jvp_reference`'s
+    deposits (include/dpr.h: deposit = a * prod + sum_n b_n * d prod / d delta_n) in fp64, zero on rejected
+    points.  |a| + sum_n |b_n| is the bound the tiled JVP scales its fixed-point sums by."""
+    points, rot, trans = (np.asarray(x, np.float64) for x in (points, rot, trans))
+    P, n_in = points.shape
+    B, n_out = rot.shape[0], rot.shape[1]
+    ow = np.ones(B) if ow is None else np.asarray(ow, np.float64)
+    pw = np.ones(P) if pw is None else np.asarray(pw, np.float64)
+    t = lambda kind, shape: np.asarray(tan[kind], np.float64) if kind in tan else np.zeros(shape)
+    pd, rd, td = t("points", (K, P, n_in)), t("rotation", (K, B, n_out, n_in)), t("translation", (K, B, n_out))
+    owd, pwd = t("out_weight", (K, B)), t("point_weight", (K, P))
+    ok, ref0, _ = cell_choice(grid, points, rot[b], trans[b], cell_dtype)
+    a, bn = np.zeros((K, P)), np.zeros((K, P, n_out))
+    q = np.nonzero(ok)[0]
+    n = np.asarray(grid, np.float64)
+    for k in range(K):
+        cdot = (np.einsum("nj,pj->pn", rd[k, b], points[q]) + np.einsum("nj,pj->pn", rot[b], pd[k, q])
+                + td[k, b][None, :]) * (n / 2)[None, :]
+        a[k, q] = owd[k, b] * pw[q] + ow[b] * pwd[k, q]
+        bn[k, q] = (ow[b] * pw[q])[:, None] * cdot
+    return ok, ref0, a, bn
+
+
 def random_tangents(rng, K, P, B, n_in, n_out, kinds=KINDS):
     shapes = dict(points=(K, P, n_in), rotation=(K, B, n_out, n_in), translation=(K, B, n_out),
                   background=(K, B), out_weight=(K, B), point_weight=(K, P))

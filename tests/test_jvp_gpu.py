@@ -159,6 +159,9 @@ def test_planes_equal_single_tangent_calls(dev, npdt, tdt, algo, n_in, n_out):
 @pytest.mark.parametrize("npdt,tdt", DTYPES)
 @pytest.mark.parametrize("n_in,n_out", TILED_PAIRS)
 def test_tiled_agrees_with_atomic_and_the_guard(dev, npdt, tdt, n_in, n_out):
+    # (Norm-wise only: the light half of the guard input carries 1e-6 of the norm, so this would pass with every
+    # light deposit dropped.  The per-cell check of the guard and the scale, relative to the bounds that reach a
+    # cell, is tests/test_families_precision_gpu.py.)
     pr = Problem(dev, npdt, tdt, n_in, n_out, 2, 3, P=6000, grid_n=48)
     assert_close(pr.jvp("tiled"), pr.jvp("atomic"), 1e-12 if npdt == np.float64 else 1e-5, "tiled vs atomic")
     # point_weight tangents spanning 2^20: every (pose, tangent) scope trips the 2^10 guard (f64 LDS atomics)
