@@ -219,7 +219,7 @@ static void coarse_slices(size_t elem, int64_t P, int* nblk, int64_t* chunk) {
     if (*nblk < 1) *nblk = 1;
 }
 // workspace of the coarse sort: counts[nblk][4096] | totals[4096] | cell_start[4096]
-static size_t coarse_workspace_bytes(size_t elem, int64_t P) {
+size_t coarse_workspace_bytes(size_t elem, int64_t P) {
     int nblk;
     int64_t chunk;
     coarse_slices(elem, P < 1 ? 1 : P, &nblk, &chunk);

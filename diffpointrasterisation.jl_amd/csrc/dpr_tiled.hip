@@ -1,6 +1,7 @@
 // DPR_ALGO_TILED: per-pose binning of the points into voxel tiles, then one workgroup per
 // work item (a tile, or a part of a heavily loaded tile) that keeps the tile in LDS.
 // No global float atomics anywhere on this path.  DESIGN.md 4.2 has the table of stages.
+// (The slab cut of a grid, the workspace plan and the tiled_* queries: dpr_tiled_plan.hip, host only.)
 //
 // Per pose b -- or per POSE GROUP of up to 16 poses when the grid has few tiles (bins are then
 // (pose, tile) pairs; see pose_group()) -- sequential launches on the caller's stream,
@@ -32,141 +33,15 @@
 //   DPR_MAX_TILES=n      tiles per launch sequence (default 32768): lets a test walk slabs on small grids
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <set>
 #include <type_traits>
 #include <utility>
 
-#include "../../include/dpr.h"
-#include "dpr_device.h"
-#include "dpr_jvp.h"
-#include "dpr_tiled.h"
+#include "dpr_tiled_impl.h"
 
 namespace dpr {
-
-// ------------------------------------------------------------------ tile geometry
-template <int NO> struct TileDims;
-// 3-D tile shape and K4 block size (A/B measured on C3, profiles/r01_tile_shape_sweep.txt)
-template <> struct TileDims<3> {
-    static constexpr int T[3] = {64, 16, 8};
-};
-template <> struct TileDims<2> {
-    static constexpr int T[3] = {32, 32, 1};
-};
-constexpr int kMaxTiles = 32768;     // LDS cursor table: 4 B per tile, <= 128 KiB
-constexpr int kBinThreads = 1024;    // K1 / K3 block
-constexpr int kWcThreads = 1024;     // block of the write-combining scatter
-constexpr int kWcPpt = 4;            // points per thread of a write-combining sub-chunk (fp32)
-constexpr int kSplatThreads = 512;   // forward tile kernel block
-constexpr int kSplatRunsOcc = 4;     // waves per SIMD of k_tile_splat_runs: two blocks per CU
-// fp64: the ds_dout tile is 80 KB, two workgroups per CU -- 512 threads each keep 16 waves on the CU
-// as the fp32 kernel's four workgroups of 256 do (with 256: 2.3 waves per SIMD, half the wave time
-// spent waiting; profiles/r04_c5_sq_counters.txt)
-template <typename T> __host__ __device__ constexpr int gather_threads() {
-    return sizeof(T) == 8 ? 512 : 256;
-}
-// waves per SIMD the pullback tile kernels are compiled for (fp64: 128 VGPRs, so that two
-// workgroups of 512 fit a CU; fp32: four workgroups of 256 need no more than that either)
-template <typename T> __host__ __device__ constexpr int gather_waves_per_simd() { return 4; }
-constexpr int kUpb = 4;        // points per thread of the single-pose un-permute (a block = one scatter sub-chunk)
-constexpr int kGatherRb = 8;   // rows of the ds_dout tile a wave requests before it stores the first
-// (the pullback tile kernels run 4 workgroups = 16 waves per CU: their 40 KB ds_dout tile sets
-// that, not the ~100 VGPRs)
-constexpr int kMaxBinBlocks = 512;   // rows of the counts table (2 per CU)
-constexpr int kSplitChunks = 8;      // k_halo_gather work items per split tile (3-D: kSplitRows tile rows each;
-                                     // 2-D: 256 voxels a step of the flat loop)
-constexpr int kSplitRows = 16;       // rows (l1, l2) of a 64 x 16 x 8 tile per work item
-constexpr int kSplitGrid = 2048;     // ... and the blocks that walk them (idle blocks cost nothing
-                                     // measurable: a grid limited to the live items changed no kernel time)
-
-// Tile geometry of one launch sequence.  Grids of up to kMaxTiles tiles are one piece; larger
-// ones are processed in SLABS along the last axis: `nt[NO-1]` tile layers starting at global layer
-// `tz0`, the rest of the grid is invisible to the launch (points whose primary tile lies outside
-// are treated like points outside the grid).  A forward slab other than the first starts with a
-// GHOST layer (ghost = 1): the top layer of the slab below, binned and accumulated once more only
-// for its upper halo -- the first real layer's low faces need it, and the slab below has long
-// overwritten its halo buffer; ghost tiles flush no owned voxel and receive no halo.
-template <int NO> struct TileGeom {
-    int nt[NO];  // tiles per axis (of this slab)
-    int NT;      // tiles per pose (of this slab)
-    int tz0;     // first tile layer along the last axis
-    int ghost;   // 1: local layer 0 is a ghost layer
-};
-
-template <int NO> __host__ __device__ constexpr int tile_voxels() {
-    int v = 1;
-    for (int d = 0; d < NO; ++d) v *= TileDims<NO>::T[d];
-    return v;
-}
-template <int NO> __host__ __device__ constexpr int tile_voxels_halo() {
-    int v = 1;
-    for (int d = 0; d < NO; ++d) v *= TileDims<NO>::T[d] + 1;
-    return v;
-}
-template <int NO> __host__ __device__ constexpr int halo_count() {
-    return tile_voxels_halo<NO>() - tile_voxels<NO>();
-}
-
-// How a grid is cut into slabs: `per_layer` tiles in a layer of the last axis, `layers` layers,
-// at most `lps` real layers per slab (a slab's tile count incl. a ghost layer stays <= kMaxTiles).
-struct SlabCut {
-    int per_layer, layers, lps, nslab;
-};
-// tiles one launch sequence may hold: kMaxTiles, or less through DPR_MAX_TILES (read once; lets a
-// test walk slabs on a small grid)
-static int max_tiles() {
-    static const int v = [] {
-        const char* e = getenv("DPR_MAX_TILES");
-        int x = e ? atoi(e) : kMaxTiles;
-        return x < 16 ? 16 : (x > kMaxTiles ? kMaxTiles : x);
-    }();
-    return v;
-}
-template <int NO> static bool make_slab_cut(const int64_t* grid, SlabCut* sc) {
-    const int cap = max_tiles();  // tiles one launch sequence may hold (kMaxTiles unless DPR_MAX_TILES)
-    int64_t per = 1;
-    for (int d = 0; d + 1 < NO; ++d) per *= (grid[d] + TileDims<NO>::T[d] - 1) / TileDims<NO>::T[d];
-    const int64_t layers = (grid[NO - 1] + TileDims<NO>::T[NO - 1] - 1) / TileDims<NO>::T[NO - 1];
-    if (per > cap / 2 || layers > (1 << 20)) return false;  // (a real + a ghost layer must fit)
-    sc->per_layer = (int)per;
-    sc->layers = (int)layers;
-    if (per * layers <= cap) {
-        sc->lps = (int)layers;
-        sc->nslab = 1;
-    } else {
-        sc->lps = (int)(cap / per) - 1;
-        sc->nslab = (int)((layers + sc->lps - 1) / sc->lps);
-    }
-    return true;
-}
-// geometry of slab `s` (forward: with the ghost layer for s > 0)
-template <int NO>
-static TileGeom<NO> slab_geom(const int64_t* grid, const SlabCut& sc, int s, bool forward) {
-    TileGeom<NO> tg;
-    for (int d = 0; d + 1 < NO; ++d)
-        tg.nt[d] = (int)((grid[d] + TileDims<NO>::T[d] - 1) / TileDims<NO>::T[d]);
-    const int first = s * sc.lps;
-    const int real = (sc.layers - first < sc.lps) ? sc.layers - first : sc.lps;
-    tg.ghost = (forward && s > 0) ? 1 : 0;
-    tg.tz0 = first - tg.ghost;
-    tg.nt[NO - 1] = real + tg.ghost;
-    tg.NT = sc.per_layer * tg.nt[NO - 1];
-    return tg;
-}
-// the largest tile count any slab of the cut has (what the workspace is planned for)
-static int slab_max_tiles(const SlabCut& sc) {
-    return sc.nslab == 1 ? sc.per_layer * sc.layers : sc.per_layer * (sc.lps + 1);
-}
-
-// single-piece geometry (false: the grid needs slabs, or is beyond them)
-template <int NO> static bool make_geom(const int64_t* grid, TileGeom<NO>* tg) {
-    SlabCut sc;
-    if (!make_slab_cut<NO>(grid, &sc) || sc.nslab != 1) return false;
-    *tg = slab_geom<NO>(grid, sc, 0, true);
-    return true;
-}
 
 // primary tile of a point: tile of max(ref0, 0) per axis (ref0 in [-1, n-1]); -1 when that tile
 // lies outside the slab of this launch
@@ -403,25 +278,6 @@ __global__ __launch_bounds__(kBinThreads) void k_count(GridDesc<NO> gd, TileGeom
 }
 
 // ------------------------------------------------------------------ K2: scans
-// What a DPR_FLAG_KEEP_BINNING forward leaves at the start of the workspace, and what a
-// DPR_FLAG_REUSE_BINNING pullback checks ON THE DEVICE before it trusts the work list, the
-// records and the slot map: problem shape, element size, the identity of the point / weight
-// buffers and the pose VALUES (bit patterns).  state: kBinValid after a KEEP forward, 0 after
-// any other binning and after the pullback that consumed it (its gradient records overwrite
-// the point records in place, so a second reuse must not pass).  A pullback that finds no
-// matching header launches nothing that touches memory through the stale lists and returns
-// NaN in every output (loud, not silent).
-constexpr uint32_t kBinMagic = 0x44505242u, kBinValid = 1u;
-struct alignas(16) BinHeader {
-    uint32_t magic, state;
-    uint32_t elem, n_in, n_out, has_pw;
-    int64_t P;
-    int32_t grid[3];
-    uint32_t verdict;  // written by the consuming pullback's first kernel: 1 = header matched
-    uint64_t points, pw;
-    uint32_t layout, pad_[3];  // plan_layout_id() of the workspace layout the binning was written in
-    unsigned char pose[96];  // rotation | translation bytes of pose 0 (<= 9 + 3 doubles)
-};
 template <typename T, int NI, int NO>
 static BinHeader make_header(const int64_t* grid, int64_t P, const T* points, const T* pw) {
     BinHeader h;
@@ -452,15 +308,6 @@ __device__ __forceinline__ bool header_matches(const BinHeader* hdr, const BinHe
     return ok;
 }
 
-// One unit of work of the tile kernels: a contiguous record range of one tile.  Tiles with
-// more than `cap` records are split into several items (parts) so that a clustered cloud
-// (few heavily loaded tiles) still fills the chip; the parts of a split tile leave their LDS
-// tiles in overflow slabs that k_halo_gather sums.
-struct alignas(16) WorkItem {
-    uint32_t tile, begin, end;
-    uint32_t part_nparts;  // part | nparts << 16
-};
-
 // Wait HERE for every outstanding global load / store of the wave (s_waitcnt vmcnt(0) through the
 // builtin, which the compiler's own wait insertion sees; an inline-asm wait it does not).  Used
 // in front of loops that start with a prefetched element: left pending into the loop, that
@@ -476,26 +323,6 @@ template <typename R> __device__ __forceinline__ void pin_record(R& r) {
 #pragma unroll
     for (int k = 0; k < (int)(sizeof(r.v) / sizeof(r.v[0])); ++k) pin_value(r.v[k]);
 }
-
-// ---- LOCAL BINNING (DPR_FLAG_COHERENT_POINTS) ------------------------------------------------
-// For a spatially coherent cloud the per-pose permutation can stay LOCAL: a block orders one
-// sub-chunk of S consecutive points by tile in LDS and writes it out as ONE contiguous run of
-// records, plus a descriptor {tile, start, count} for every tile the sub-chunk touches (a
-// handful -- 13 of 2048 for a 4096-point sub-chunk of the Hilbert-sorted C3 cloud).  No count
-// pass over the points, no counts table, no column scan; the descriptors (3 % of the points'
-// bytes) are sorted by tile instead of the records, and the tile kernels walk the record runs
-// their descriptors name.  Correct for any order -- an incoherent cloud just yields about as
-// many descriptors as points and runs slowly, which is why the caller has to ask for it.
-struct alignas(8) RunDesc {
-    uint32_t start;       // first record of the run
-    uint32_t tile_count;  // tile | count << 15   (tile < 32768, count <= S <= 4096)
-    __host__ __device__ uint32_t tile() const { return tile_count & 0x7fffu; }
-    __host__ __device__ uint32_t count() const { return tile_count >> 15; }
-};
-constexpr int kMaxLocalTiles = 16384;  // tiles per pose local binning supports (its LDS histogram)
-constexpr int kMaxRuns = 256;        // descriptors per round of a work item in k_tile_splat ...
-constexpr int kMaxRunsGather = 64;   // ... and in k_tile_gather (their tables live in LDS: 4
-                                     // gather blocks per CU leave room for 64 runs)
 
 // LDS tables of one work item's runs + a forward-only cursor: logical record i of the item ->
 // index into the record array.  A thread asks for non-decreasing i only.
@@ -3244,331 +3071,57 @@ static int cu_count() {
     return cus[dev];
 }
 
-// Workspace layout (identical for raster and pullback so that a pullback can reuse the
-// binning a raster call left behind, DPR_FLAG_KEEP_BINNING / DPR_FLAG_REUSE_BINNING):
-//   counts table | totals | tile_start | work items, n_items, tile_parts, tile_slab | records | indices | slot_of | aux (halo / partials)
-struct Plan {
-    int bg;          // poses binned together (pose group, a power of two; 1 = per-pose pipeline)
-    int nblk;
-    int64_t chunk;
-    uint32_t cap;    // records per work item above which a tile is split
-    int max_items;   // NT + worst-case number of extra parts
-    int max_slabs;   // overflow slabs (parts of split tiles)
-    size_t off_hdr, off_counts, off_totals, off_tile_start, off_items, off_nitems, off_nzbins, off_tparts, off_tslab,
-        off_split, off_rec, off_idx, off_slot, off_aux, total;
-    // Cell sort of the cloud inside the call (dpr_coarse.h; batched poses on grids with more than
-    // 4096 tiles): what local binning of all poses of a batch needs; up to 16384 tiles per pose --
-    // beyond that the plain count / scatter pipeline runs on the cell-sorted copy
-    bool sort_inside;
-    size_t off_spts, off_spw, off_perm, off_iperm, off_sgrad, off_sgradw, off_sorttmp;
-    // KEEP_BINNING / REUSE_BINNING with B > 1: every pose owns a copy of the per-pose part of the
-    // layout (header ... slot map), pose_stride bytes apart, so that the pullback finds the binning
-    // of EVERY pose of the forward call; 0 when the poses share one copy (nothing is kept)
-    size_t pose_stride;
-    // local binning (DPR_FLAG_COHERENT_POINTS, or the cloud cell-sorted inside the call; NT <= 16384)
-    bool local;
-    int lb;                // poses binned per k_bin_local launch (each into its own copy of the
-                           // per-pose workspace: `copies` of them, pose_stride bytes apart)
-    int64_t copies;
-    int sub;               // points per sub-chunk
-    int64_t nsub;          // sub-chunks = blocks of k_bin_local
-    int64_t max_desc;      // descriptor slots: `sub` per sub-chunk
-    size_t off_ltot, off_dstart, off_dcursor, off_bdesc, off_desc, off_sdesc;  // ltot: ndesc[NT] | npts[NT] | max|pw| | ~min|pw|
+// ---- typed views of the workspace, the walk over the poses of a call
+// One pose copy of the per-pose part of the workspace (Plan: header ... slot map), typed.
+struct PoseWs {
+    char* base;
+    const Plan& pl;
+    template <typename X> X* at(size_t off) const { return (X*)(base + off); }
+    BinHeader* hdr() const { return at<BinHeader>(pl.off_hdr); }
+    uint32_t* counts() const { return at<uint32_t>(pl.off_counts); }
+    uint32_t* totals() const { return at<uint32_t>(pl.off_totals); }
+    uint32_t* tile_start() const { return at<uint32_t>(pl.off_tile_start); }
+    WorkItem* items() const { return at<WorkItem>(pl.off_items); }
+    uint32_t* n_items() const { return at<uint32_t>(pl.off_nitems); }  // [1]: record assignment of k_tile_splat
+    uint32_t* weight_keys() const { return n_items() + 2; }            // max / ~min |point_weight| bits
+    uint32_t* nzbins() const { return at<uint32_t>(pl.off_nzbins); }
+    uint32_t* tparts() const { return at<uint32_t>(pl.off_tparts); }
+    uint32_t* tslab() const { return at<uint32_t>(pl.off_tslab); }
+    uint32_t* n_split() const { return at<uint32_t>(pl.off_split); }
+    uint32_t* split() const { return n_split() + 1; }
+    template <typename R> R* rec() const { return at<R>(pl.off_rec); }
+    uint32_t* idx() const { return at<uint32_t>(pl.off_idx); }
+    uint32_t* slot() const { return at<uint32_t>(pl.off_slot); }
+    // local binning
+    RunDesc* sdesc() const { return at<RunDesc>(pl.off_sdesc); }
+    uint32_t* ltot() const { return at<uint32_t>(pl.off_ltot); }
+    uint32_t max_rec() const { return (uint32_t)(pl.nsub * pl.sub); }  // records of a locally binned pose
 };
 
-// Pose groups: with few tiles per pose (2-D projections, small 3-D grids) the bins become
-// (pose, tile) pairs of up to kMaxGroup poses, as long as they fit the write-combining
-// scatter's 4096 LDS cursors: the points are read once per group instead of once per pose and
-// the fixed per-launch costs (scans, halo pass, reductions, launch gaps) are shared.  Measured
-// (tools/pose_group_probe.py): 10 M points -> 512^2, 485 -> 383 us per pose (fwd + bwd);
-// 1 M points -> 128^3, 149 -> 65 us per pose.
-// Memory: records and slot map are sized P * g (20 / 36 bytes per point-pose), so a group of g
-// poses multiplies that part of the workspace by g -- bounded by P * g <= 2^27 (2.7 GB fp32,
-// 4.8 GB fp64) and by the caller through DPR_FLAG_MAX_POSE_GROUP(n) (include/dpr.h).
-constexpr int kMaxGroup = 16;
-static int pose_group(int NT, int64_t P, int64_t B, int max_group) {
-    const int limit = (max_group > 0 && max_group < kMaxGroup) ? max_group : kMaxGroup;
-    int bg = 1;
-    while (bg * 2 <= limit && bg * 2 <= B && NT * bg * 2 <= 4096 &&
-           P * bg * 2 <= ((int64_t)1 << 27))  // records of a group: <= 2 GiB (fp32)
-        bg *= 2;
-    return bg;
-}
-
-static Plan make_plan(size_t elem, int n_out, int NT1, int64_t P1, int64_t B, int max_group,
-                      bool coherent = false, int n_in = 3, bool share_batch = false,
-                      bool slabbed = false, bool fwd_only = false) {
-    Plan pl;
-    if (slabbed) coherent = false;  // local binning keeps a batch's bins: one slab at a time cannot
-    share_batch = share_batch && B > 1;
-    if (share_batch) max_group = 1;  // a kept binning is per pose
-    pl.pose_stride = 0;
-    pl.sort_inside = !coherent && NT1 > 4096 && B >= 4 && P1 >= 200000;
-    // Local binning is per pose: a batch that forms pose groups (few tiles) keeps the
-    // grouped pipeline, which reads the points once per group (10 M points -> 512^2, 4 poses:
-    // 0.56 ms grouped, 0.63 ms pose by pose on local bins)
-    pl.bg = pose_group(NT1, P1, B, max_group);
-    pl.local = (coherent || pl.sort_inside) && !slabbed && NT1 <= kMaxLocalTiles &&
-               pl.bg == 1;
-    // poses binned by one k_bin_local launch (the points are read once for all of them): every
-    // pose of a kept batch, else up to 8 -- each needs its own records, P * lb <= 2^29
-    pl.lb = 1;
-    if (pl.local && B > 1) {
-        if (share_batch) {
-            pl.lb = B < 16 ? (int)B : 16;  // (the B copies exist anyway)
-        } else {
-            pl.lb = B < 8 ? (int)B : 8;
-            while (pl.lb > 1 && P1 * pl.lb > ((int64_t)1 << 29)) --pl.lb;
-        }
+// The walk of raster_tiled / pullback_tiled over the poses of a call.
+struct PoseWalk {
+    const Plan& pl;
+    char* ws;
+    bool kept;  // KEEP_BINNING / REUSE_BINNING
+    int64_t B;
+    // poses of the group that starts with pose b
+    int64_t group(int64_t b) const {
+        int64_t nb = 1;
+        while (nb * 2 <= pl.bg && b + nb * 2 <= B) nb *= 2;
+        return nb;
     }
-    pl.copies = share_batch ? B : pl.lb;
-    const int NT = NT1 * pl.bg;          // bins
-    const int64_t P = P1 * pl.bg;        // records
-    // Slices of the cloud = blocks of k_count / the scatter = rows of the counts table.
-    int64_t nblk, chunk;
-    if (NT <= 4096) {
-        // write-combining scatter (one workgroup per CU: its LDS): at most one slice per CU, so
-        // that all of them run at once, and whole sub-chunks per slice (a partly filled round costs
-        // as much as a full one; 3e6 points: 489 slices of 1.5 rounds -> 245 of 3: 0.131 -> 0.124 ms)
-        const int64_t sub = (elem == 4) ? kWcPpt * kWcThreads : kWcPpt * kWcThreads / 2;
-        chunk = ((P1 + 255) / 256 + sub - 1) / sub * sub;
-        if (chunk < sub) chunk = sub;
-    } else {
-        nblk = (P1 + 8191) / 8192;
-        if (nblk < 1) nblk = 1;
-        if (nblk > kMaxBinBlocks) nblk = kMaxBinBlocks;
-        chunk = (P1 + nblk - 1) / nblk;
-        chunk = (chunk + kBinThreads - 1) / kBinThreads * kBinThreads;
-        if (chunk < kBinThreads) chunk = kBinThreads;
-    }
-    nblk = (P1 + chunk - 1) / chunk;
-    if (nblk < 1) nblk = 1;
-    pl.nblk = (int)nblk;
-    pl.chunk = chunk;
-    size_t o = 0;
-    pl.off_hdr = o;  // BinHeader: what a KEEP_BINNING forward left, checked by a REUSE pullback
-    o += align_up(sizeof(BinHeader));
-    pl.off_counts = o;
-    o += align_up((size_t)nblk * NT * 4);
-    pl.off_totals = o;
-    o += align_up((size_t)NT * 4);
-    pl.off_tile_start = o;
-    o += align_up((size_t)(NT + 1) * 4);
-    // split threshold: ~P/256 records (even a fully clustered cloud then yields >= 256 items,
-    // one per CU, while the headline Gaussian cloud has no tile above it), at least 4096; a
-    // split tile's parts hold more than cap/2 records each
-    // (a forward call that keeps nothing for a pullback splits later: the parts of a split tile
-    // cost the halo pass more than a 2x longer item costs the fixed-point tile kernel -- 1 M points
-    // -> 128^3: forward 0.065 -> 0.059 ms; the pullback's gather prefers the finer split)
-    int64_t cap = P / 256;
-    const int64_t cap_min = fwd_only ? 2 * 4096 : 4096;
-    if (cap < cap_min) cap = cap_min;
-    if (n_out == 2) {
-        // 2-D grids have few tiles (256 at 512^2) with cheap LDS tiles (8.7 KB): split
-        // earlier so that a dense projection still gives the chip ~2048 items
-        cap = P / 2048;
-        if (cap < 2048) cap = 2048;
-    }
-    pl.cap = (uint32_t)cap;
-    pl.max_slabs = (int)(2 * ((P + cap - 1) / cap) + 1);
-    pl.max_items = NT + pl.max_slabs;
-    pl.off_items = o;
-    o += align_up((size_t)pl.max_items * sizeof(WorkItem));
-    pl.off_nitems = o;  // [0] = items, [1] = record assignment of k_tile_splat, [2] / [3] = max / ~min |point_weight| bits
-    o += align_up(4);
-    pl.off_nzbins = o;  // bins touched per count block (k_count -> k_tilescan)
-    o += align_up((size_t)kMaxBinBlocks * 4);
-    pl.off_tparts = o;
-    o += align_up((size_t)NT * 4);
-    pl.off_tslab = o;
-    o += align_up((size_t)NT * 4);
-    pl.off_split = o;  // [0] = n_split, [1..] = split tile ids (at most max_slabs / 2)
-    o += align_up((size_t)(pl.max_slabs / 2 + 2) * 4);
-    pl.sub = elem == 4 ? 4096 : 2048;
-    pl.nsub = (P1 + pl.sub - 1) / pl.sub;
-    if (pl.nsub < 1) pl.nsub = 1;
-    pl.max_desc = 0;
-    int64_t nrec = P;  // records (+ spare slot for rejected points)
-    if (pl.local) {
-        pl.max_desc = pl.nsub * pl.sub;  // every sub-chunk owns `sub` descriptor slots ...
-        nrec = pl.nsub * pl.sub;         // ... and a slab of `sub` records
-        pl.off_ltot = o;  // (the cursors follow the totals directly: one clear covers both)
-        o += align_up((size_t)(2 * NT1 + 2) * 4);
-        pl.off_dcursor = o;
-        o += align_up((size_t)NT1 * 4);
-        pl.off_dstart = o;
-        o += align_up((size_t)(NT1 + 1) * 4);
-        pl.off_bdesc = o;
-        o += align_up((size_t)pl.nsub * 4);
-        pl.off_desc = o;
-        o += align_up((size_t)pl.max_desc * sizeof(RunDesc));
-        pl.off_sdesc = o;
-        o += align_up((size_t)pl.max_desc * sizeof(RunDesc));
-    }
-    pl.off_rec = o;
-    o += align_up((size_t)(nrec + 1) * 4 * elem);  // + spare slot for rejected points
-    pl.off_idx = o;
-    o += align_up((size_t)(P1 + 1) * 4);
-    pl.off_slot = o;
-    o += align_up((size_t)(P + 1) * 4);
-    (void)nrec;
-    if (pl.copies > 1) {  // everything up to here exists once per pose (of a kept batch / a local batch)
-        pl.pose_stride = o;
-        o += (size_t)(pl.copies - 1) * pl.pose_stride;
-    }
-    pl.off_spts = pl.off_spw = pl.off_perm = pl.off_iperm = pl.off_sgrad = pl.off_sgradw = pl.off_sorttmp = o;
-    if (pl.sort_inside) {
-        pl.off_spts = o;
-        o += align_up((size_t)P1 * n_in * elem);
-        pl.off_spw = o;
-        o += align_up((size_t)P1 * elem);
-        pl.off_perm = o;  // (unused since the coarse cell sort: only the inverse is needed)
-        pl.off_iperm = o;  // inverse permutation: the un-sort of the gradients gathers through it
-        o += align_up((size_t)P1 * 4);
-        pl.off_sgrad = o;
-        o += align_up((size_t)P1 * n_in * elem);
-        pl.off_sgradw = o;
-        o += align_up((size_t)P1 * elem);
-        pl.off_sorttmp = o;
-        o += align_up(coarse_workspace_bytes(elem, P1));
-    }
-    pl.off_aux = o;
-    // aux: forward = halo buffer | overflow slabs ; pullback = per-item partials
-    const size_t nvh = (n_out == 3) ? tile_voxels_halo<3>() : tile_voxels_halo<2>();
-    const size_t halo = align_up((size_t)NT * ((n_out == 3) ? halo_count<3>() : halo_count<2>()) * elem) +
-                        align_up((size_t)pl.max_slabs * nvh * elem);
-    const size_t partials = (size_t)pl.max_items * 16 * 8;
-    o += align_up(halo > partials ? halo : partials);
-    pl.total = o;
-    return pl;
-}
-
-// Identity of a workspace layout: a REUSE_BINNING pullback must read the lists where -- and in
-// the form in which -- the KEEP_BINNING forward wrote them.  The two calls compute their plans
-// independently (DPR_FLAG_COHERENT_POINTS and DPR_FLAG_MAX_POSE_GROUP move regions), so the
-// forward stores this id in the header and the pullback's kernels compare it on the device like
-// the rest of the header.
-static uint32_t plan_layout_id(const Plan& pl) {
-    uint64_t h = 1469598103934665603ull;  // FNV-1a over the fields that place or shape the lists
-    auto mix = [&](uint64_t v) {
-        for (int i = 0; i < 8; ++i) {
-            h ^= (v >> (8 * i)) & 0xffu;
-            h *= 1099511628211ull;
-        }
-    };
-    mix(pl.local ? 1 : 0);
-    mix((uint64_t)pl.bg);
-    mix((uint64_t)pl.sub);
-    mix((uint64_t)pl.cap);
-    mix(pl.off_items);
-    mix(pl.off_rec);
-    mix(pl.off_idx);
-    mix(pl.off_slot);
-    mix(pl.off_aux);
-    mix(pl.local ? pl.off_sdesc : 0);
-    mix(pl.pose_stride);
-    mix(pl.off_iperm);
-    mix((uint64_t)pl.lb);
-    const uint32_t id = (uint32_t)(h ^ (h >> 32));
-    return id ? id : 1u;
-}
-
-static bool grid_cut(int n_out, const int64_t* grid, SlabCut* sc) {
-    return n_out == 3 ? make_slab_cut<3>(grid, sc) : make_slab_cut<2>(grid, sc);
-}
-
-bool tiled_supported(int n_out, const int64_t* grid) {
-    SlabCut sc;
-    return grid_cut(n_out, grid, &sc);
-}
-
-// slabs the tiled path cuts the grid into (1: one piece; 0: not supported)
-int tiled_slabs(int n_out, const int64_t* grid) {
-    SlabCut sc;
-    return grid_cut(n_out, grid, &sc) ? sc.nslab : 0;
-}
-
-bool tiled_preferred(int op, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t G) {
-    (void)G;
-    if (P >= (int64_t)1 << 32) return false;
-    SlabCut sc;
-    if (!grid_cut(n_out, grid, &sc)) return false;
-    // A cloud that is SPARSE on the grid: the tiled path pays per tile (zeroing and flushing an LDS
-    // tile, staging a ds_dout tile: ~25 ns each) whether points fall into it or not, the direct
-    // kernels pay per point only.  Crossovers measured on 256^3 ... 768^3 and 2048^2 / 4096^2 with
-    // 1e5 ... 1e7 points, 1 and 4 poses (tools/sparse_grid_probe.py, profiles/r04_sparse_grids.txt):
-    // forward ~60 points per tile (3-D) / ~48 (2-D), pullback ~320 (3-D) / 150-430 (2-D) -- the
-    // direct pullback only READS the cells its points touch.  Below that AUTO regretted up to 2.8x
-    // (3e5 points -> 4096^2, pullback) with the thresholds that follow, which were fitted on grids
-    // of up to 2048 tiles.
-    const int64_t NT_all = (int64_t)sc.per_layer * sc.layers;
-    const int64_t per_tile = op == DPR_OP_RASTER ? (n_out == 3 ? 60 : 48)
-                                                 : (n_out == 3 ? 320 : (NT_all <= 4096 ? 150 : 430));
-    if (P < per_tile * NT_all) return false;
-    if (sc.nslab > 1) {
-        // More than 32768 tiles (e.g. 1024^3): every slab re-reads the cloud, and the tile kernels
-        // write the whole grid -- which the direct path's background fill does as well.  Forward:
-        // the LDS tiles beat scattered global atomics from ~1e6 points on (1e7 points -> 1024^3:
-        // measured in profiles/r04_experiments.md); the pullback's gathers are reads, the direct
-        // kernel keeps them.
-        return op == DPR_OP_RASTER && P >= 1000000;
-    }
-    const int NT = sc.per_layer * sc.layers;
-    // Measured crossovers (profiles/r01_algo_sweep.txt: one pose; r01_algo_sweep_batched.txt:
-    // 4-64 poses; 64^3 ... 256^3 and 128^2 / 512^2 grids).  One pose: the tiled pipeline's fixed
-    // cost (6-7 launches) is repaid from ~2-3e5 points on, forward and backward alike.  Batched
-    // poses on a grid that forms pose groups: the fixed cost is shared, the forward pays from
-    // ~6e4 points; the direct pullback kernel, which keeps a point in registers across the poses
-    // of a slice, stays ahead up to ~3e5 points (~6e5 when the grid is too large for groups).
-    const bool grouped = B >= 4 && pose_group(NT, P, B, 0) >= 4;
-    // (one pose on a small grid -- up to 256^2 or 128^3: from 1e5 points -- the direct kernel's atomics are
-    // at most 1.25x ahead there on a cloud that fills the grid and 2x behind on a clustered one,
-    // profiles/r03_auto_regret.txt)
-    // (two or three poses: the same per pose -- 1e5 points x 2 poses -> 128^3: tiled 0.058 ms, direct 0.099)
-    if (op == DPR_OP_RASTER && B < 4 && (NT <= 64 || (n_out == 3 && NT <= 256))) return P >= 100000;
-    if (op == DPR_OP_RASTER) return P >= (grouped ? 60000 : 250000);
-    if (B >= 4) return P >= (grouped ? 300000 : 600000);
-    return P >= 250000;
-}
-
-// tiles per pose of the tiled path's geometry (of its largest slab; -1: not supported)
-int tiled_tiles(int n_out, const int64_t* grid) {
-    SlabCut sc;
-    return grid_cut(n_out, grid, &sc) ? slab_max_tiles(sc) : -1;
-}
-
-// May a KEEP_BINNING / REUSE_BINNING pair with B > 1 poses share on the tiled path when
-// DPR_ALGO_AUTO decides?  Every pose then keeps its own records (Plan::pose_stride): only where
-// pose groups are not an option anyway (more than 2048 tiles per pose) and the kept records stay
-// below ~21 GB at fp64, ~13 GB at fp32 (P * B <= 2^29: a 4-word record, a slot and an index per
-// point and pose; independent of the element type, so that dpr_resolve_algo_ex needs none).  An
-// explicit DPR_ALGO_TILED shares for any B.  Never on a grid that is processed in slabs (a slab's
-// binning is overwritten by the next one).
-bool tiled_batch_share_ok(int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    if (B < 2 || P < 1 || P * B > ((int64_t)1 << 29)) return false;
-    SlabCut sc;
-    if (!grid_cut(n_out, grid, &sc) || sc.nslab != 1) return false;
-    return sc.per_layer * sc.layers * 2 > 4096;
-}
-
-size_t tiled_workspace_bytes(size_t elem, int op, unsigned flags, int n_in, int n_out,
-                             const int64_t* grid, int64_t P, int64_t B) {
-    (void)op;
-    if (P >= (int64_t)1 << 32) return (size_t)-1;  // refused by raster_tiled / pullback_tiled
-    SlabCut sc;
-    if (!grid_cut(n_out, grid, &sc)) return (size_t)-1;
-    if (sc.nslab > 1 && (flags & 3u)) return (size_t)-1;
-    // (sized for the plan of a sharing pair / a pullback: a forward call that keeps nothing splits
-    // heavy tiles later and needs no more than this -- so a workspace sized for `raster` serves every
-    // call of the same problem, as before)
-    return make_plan(elem, n_out, slab_max_tiles(sc), P, B, (int)((flags >> 8) & 0xffu),
-                     (flags & DPR_FLAG_COHERENT_POINTS) != 0, n_in, (flags & 3u) != 0, sc.nslab > 1)
-        .total;
-}
+    // copy of the per-pose workspace pose b lives in: its own when the binning is kept, else its
+    // place in the local batch
+    int64_t copy_of(int64_t b) const { return kept && B > 1 ? b : (pl.local ? b % pl.lb : 0); }
+    PoseWs at(int64_t b) const { return {ws + (size_t)copy_of(b) * pl.pose_stride, pl}; }
+    // local binning: pose b opens a batch (the call that bins all its poses), and the poses of that batch
+    bool opens_local_batch(int64_t b) const { return b % pl.lb == 0; }
+    int local_batch(int64_t b) const { return (int)((B - b < pl.lb) ? B - b : pl.lb); }
+};
 
 // Dynamic LDS above 48 KiB has to be allowed per kernel (and per device): done once for the
-// maximum the kernel can ask for (128 KiB of cursors at kMaxTiles), not per call.
-template <typename K> static int allow_big_lds(K kernel, size_t bytes) {
+// maximum the kernel can ask for (`max_bytes`: 128 KiB of cursors at kMaxTiles), not per call.
+template <typename K> static int allow_dynamic_lds(K kernel, size_t bytes, int max_bytes) {
     if (bytes <= 48 * 1024) return DPR_OK;
     static std::mutex mu;
     static std::set<std::pair<const void*, int>> done;  // (kernel, device) already raised
@@ -3576,11 +3129,11 @@ template <typename K> static int allow_big_lds(K kernel, size_t bytes) {
     DPR_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lock(mu);
     if (done.count({(const void*)kernel, dev})) return DPR_OK;
-    DPR_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kMaxTiles * 4));
+    DPR_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes));
     done.insert({(const void*)kernel, dev});
     return DPR_OK;
 }
+
 
 // Which scatter a binning uses: the write-combining one whenever its LDS tables fit.
 static bool scatter_is_wc(int NT, int nb) { return NT * nb <= 4096; }
@@ -3593,7 +3146,7 @@ static bool records_are_compact(int NT, int nb, bool has_pw, bool want_idx) {
 
 template <typename T, int NI, int NO, bool HAS_PW, bool WANT_IDX>
 static int launch_scatter(hipStream_t st, const GridDesc<NO>& gd, const TileGeom<NO>& tg,
-                          const Plan& pl, char* ws, int64_t P, const T* points, const T* pw,
+                          const Plan& pl, const PoseWs& w, int64_t P, const T* points, const T* pw,
                           const T* rot, const T* trans, int64_t b, int nb, const TileScanArgs& ts,
                           bool fused) {
     // write-combining variant: needs 2 NT counters + the sub-chunk in LDS
@@ -3604,12 +3157,10 @@ static int launch_scatter(hipStream_t st, const GridDesc<NO>& gd, const TileGeom
     hipLaunchKernelGGL((k_scatter_wc<T, NI, NO, HAS_PW, S, GROUP, W3>),                          \
                        dim3(pl.nblk + (fused ? 1 : 0)),                                          \
                        dim3(kWcThreads), lds2, st, gd, tg, P, pl.chunk, points, pw, rot, trans, \
-                       b, nb, (const uint32_t*)(ws + pl.off_counts),                             \
-                       (const uint32_t*)(ws + pl.off_tile_start),                                \
-                       (RecT<T, W3>*)(ws + pl.off_rec),                     \
-                       WANT_IDX ? (uint32_t*)(ws + pl.off_slot) : (uint32_t*)nullptr,            \
-                       (T*)nullptr, (T*)nullptr, 0, (uint32_t*)(ws + pl.off_nitems) + 2,          \
-                       fused ? 1 : 0, ts)
+                       b, nb, w.counts(), w.tile_start(),      \
+                       w.rec<RecT<T, W3>>(),                                                     \
+                       WANT_IDX ? w.slot() : (uint32_t*)nullptr,                                 \
+                       (T*)nullptr, (T*)nullptr, 0, w.weight_keys(), fused ? 1 : 0, ts)
         if constexpr (!HAS_PW) {
             if (records_are_compact(tg.NT, nb, false, WANT_IDX)) {
                 if (nb > 1) DPR_LAUNCH_WC(true, true);
@@ -3623,14 +3174,34 @@ static int launch_scatter(hipStream_t st, const GridDesc<NO>& gd, const TileGeom
         return DPR_OK;
     }
     const size_t lds = (size_t)tg.NT * 4;
-    if (int rc = allow_big_lds(k_scatter<T, NI, NO, HAS_PW, WANT_IDX>, lds)) return rc;
+    if (int rc = allow_dynamic_lds(k_scatter<T, NI, NO, HAS_PW, WANT_IDX>, lds, kMaxTiles * 4)) return rc;
     hipLaunchKernelGGL((k_scatter<T, NI, NO, HAS_PW, WANT_IDX>), dim3(pl.nblk), dim3(kBinThreads),
                        lds, st, gd, tg, P, pl.chunk, points, pw, rot, trans, b,
-                       (const uint32_t*)(ws + pl.off_counts),
-                       (const uint32_t*)(ws + pl.off_tile_start), (Rec4<T>*)(ws + pl.off_rec),
-                       (uint32_t*)(ws + pl.off_idx), (uint32_t*)(ws + pl.off_slot), (T*)nullptr,
-                       (T*)nullptr, 0, (uint32_t*)(ws + pl.off_nitems) + 2);
+                       w.counts(), w.tile_start(), w.rec<Rec4<T>>(),
+                       w.idx(), w.slot(), (T*)nullptr, (T*)nullptr, 0, w.weight_keys());
     return DPR_OK;
+}
+
+// The header of the binning of pose b and the pose words it is checked against: the fields TileScanArgs
+// and RunScanArgs share.  state = kBinValid: only a KEEP_BINNING forward may be reused.
+template <typename T, int NI, int NO, typename Args>
+static void fill_header(Args& a, const GridDesc<NO>& gd, const Plan& pl, int64_t P, const T* points, const T* pw,
+                        const T* hdr_points, const T* hdr_pw, const T* rot, const T* trans, int64_t b,
+                        bool keep_valid) {
+    // (the header names the caller's buffers; `points` may be the library's sorted copy)
+    if (!hdr_points) {
+        hdr_points = points;
+        hdr_pw = pw;
+    }
+    int64_t grid64[3] = {1, 1, 1};
+    for (int d = 0; d < NO; ++d) grid64[d] = gd.n[d];
+    a.hdr = make_header<T, NI, NO>(grid64, P, hdr_points, hdr_pw);
+    a.hdr.state = keep_valid ? kBinValid : 0u;
+    a.hdr.layout = plan_layout_id(pl);
+    a.rot = (const uint32_t*)(rot + b * (NO * NI));
+    a.rot_words = (int)(NO * NI * sizeof(T) / 4);
+    a.trans = (const uint32_t*)(trans + b * NO);
+    a.trans_words = (int)(NO * sizeof(T) / 4);
 }
 
 // K1-K3 for the poses [b, b + nb).  want_idx: a pullback will consume the binning.
@@ -3639,53 +3210,36 @@ static int bin_points(hipStream_t st, const GridDesc<NO>& gd, const TileGeom<NO>
                       const Plan& pl, char* ws, int64_t P, const T* points, const T* pw,
                       const T* rot, const T* trans, int64_t b, int nb, bool want_idx,
                       bool keep_valid, const T* hdr_points, const T* hdr_pw) {
-    // (the header names the caller's buffers; `points` may be the library's sorted copy)
-    if (!hdr_points) {
-        hdr_points = points;
-        hdr_pw = pw;
-    }
-    uint32_t* counts = (uint32_t*)(ws + pl.off_counts);
-    uint32_t* totals = (uint32_t*)(ws + pl.off_totals);
-    uint32_t* tile_start = (uint32_t*)(ws + pl.off_tile_start);
+    const PoseWs w{ws, pl};
     const int NTe = tg.NT * nb;
     const size_t lds = (size_t)NTe * 4;
     if (nb > 1) {
-        if (int rc = allow_big_lds(k_count<T, NI, NO, true>, lds)) return rc;
+        if (int rc = allow_dynamic_lds(k_count<T, NI, NO, true>, lds, kMaxTiles * 4)) return rc;
         hipLaunchKernelGGL((k_count<T, NI, NO, true>), dim3(pl.nblk), dim3(kBinThreads), lds, st,
-                           gd, tg, P, pl.chunk, points, rot, trans, b, nb, counts,
-                           (uint32_t*)(ws + pl.off_nzbins));
+                           gd, tg, P, pl.chunk, points, rot, trans, b, nb, w.counts(), w.nzbins());
     } else {
-        if (int rc = allow_big_lds(k_count<T, NI, NO, false>, lds)) return rc;
+        if (int rc = allow_dynamic_lds(k_count<T, NI, NO, false>, lds, kMaxTiles * 4)) return rc;
         hipLaunchKernelGGL((k_count<T, NI, NO, false>), dim3(pl.nblk), dim3(kBinThreads), lds, st,
-                           gd, tg, P, pl.chunk, points, rot, trans, b, nb, counts,
-                           (uint32_t*)(ws + pl.off_nzbins));
+                           gd, tg, P, pl.chunk, points, rot, trans, b, nb, w.counts(), w.nzbins());
     }
     stage_mark(st);
-    int64_t grid64[3] = {1, 1, 1};
-    for (int d = 0; d < NO; ++d) grid64[d] = gd.n[d];
     TileScanArgs ts;
-    ts.totals = totals;
+    ts.totals = w.totals();
     ts.NT = NTe;
     ts.cap = pl.cap;
-    ts.tile_start = tile_start;
-    ts.items = (WorkItem*)(ws + pl.off_items);
-    ts.n_items = (uint32_t*)(ws + pl.off_nitems);
-    ts.tile_parts = (uint32_t*)(ws + pl.off_tparts);
-    ts.tile_slab = (uint32_t*)(ws + pl.off_tslab);
-    ts.split_list = (uint32_t*)(ws + pl.off_split) + 1;
-    ts.n_split = (uint32_t*)(ws + pl.off_split);
-    ts.hdr = make_header<T, NI, NO>(grid64, P, hdr_points, hdr_pw);
-    ts.hdr.state = keep_valid ? kBinValid : 0u;  // only a KEEP_BINNING forward may be reused
-    ts.hdr.layout = plan_layout_id(pl);
-    ts.hdr_out = (BinHeader*)(ws + pl.off_hdr);
-    ts.rot = (const uint32_t*)(rot + b * (NO * NI));
-    ts.rot_words = (int)(NO * NI * sizeof(T) / 4);
-    ts.trans = (const uint32_t*)(trans + b * NO);
-    ts.trans_words = (int)(NO * sizeof(T) / 4);
-    ts.nonzero_bins = (const uint32_t*)(ws + pl.off_nzbins);
+    ts.tile_start = w.tile_start();
+    ts.items = w.items();
+    ts.n_items = w.n_items();
+    ts.tile_parts = w.tparts();
+    ts.tile_slab = w.tslab();
+    ts.split_list = w.split();
+    ts.n_split = w.n_split();
+    fill_header<T, NI, NO>(ts, gd, pl, P, points, pw, hdr_points, hdr_pw, rot, trans, b, keep_valid);
+    ts.hdr_out = w.hdr();
+    ts.nonzero_bins = w.nzbins();
     ts.nblk = pl.nblk;
     hipLaunchKernelGGL(k_colscan, dim3((NTe + kScanTiles - 1) / kScanTiles), dim3(1024), 0, st,
-                       counts, pl.nblk, NTe, totals, (uint32_t*)(ws + pl.off_nitems) + 2);
+                       w.counts(), pl.nblk, NTe, w.totals(), w.weight_keys());
     // The tile scan rides in the scatter launch as one extra workgroup when the write-combining
     // scatter runs (its workgroups scan the totals themselves) and a CU is left for it.
     const bool fused = scatter_is_wc(tg.NT, nb) && pl.nblk < cu_count();
@@ -3693,16 +3247,16 @@ static int bin_points(hipStream_t st, const GridDesc<NO>& gd, const TileGeom<NO>
     stage_mark(st);
     int rc;
     if (pw) {
-        rc = want_idx ? launch_scatter<T, NI, NO, true, true>(st, gd, tg, pl, ws, P, points, pw, rot, trans,
+        rc = want_idx ? launch_scatter<T, NI, NO, true, true>(st, gd, tg, pl, w, P, points, pw, rot, trans,
                                                               b, nb, ts, fused)
-                      : launch_scatter<T, NI, NO, true, false>(st, gd, tg, pl, ws, P, points, pw, rot,
+                      : launch_scatter<T, NI, NO, true, false>(st, gd, tg, pl, w, P, points, pw, rot,
                                                                trans, b, nb, ts, fused);
     } else {
         // without point weights the original index rides in the record for free; slot_of is
         // only written when a pullback will consume the binning
-        rc = want_idx ? launch_scatter<T, NI, NO, false, true>(st, gd, tg, pl, ws, P, points, pw, rot,
+        rc = want_idx ? launch_scatter<T, NI, NO, false, true>(st, gd, tg, pl, w, P, points, pw, rot,
                                                                trans, b, nb, ts, fused)
-                      : launch_scatter<T, NI, NO, false, false>(st, gd, tg, pl, ws, P, points, pw, rot,
+                      : launch_scatter<T, NI, NO, false, false>(st, gd, tg, pl, w, P, points, pw, rot,
                                                                 trans, b, nb, ts, fused);
     }
     stage_mark(st);
@@ -3713,28 +3267,11 @@ static int bin_points(hipStream_t st, const GridDesc<NO>& gd, const TileGeom<NO>
 // copies, k_bin_local (all nb poses, the points read once), k_runscan, k_place_desc.  `ws` is pose
 // copy 0 of the batch.  Same stage marks as bin_points (count | scan | scatter become
 // clear | bin_local | runscan + place).
-template <typename K> static int allow_lds_bytes(K kernel, size_t bytes) {
-    if (bytes <= 48 * 1024) return DPR_OK;
-    static std::mutex mu;
-    static std::set<std::pair<const void*, int>> done;
-    int dev = 0;
-    DPR_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    if (done.count({(const void*)kernel, dev})) return DPR_OK;
-    DPR_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kMaxLocalTiles * 4));
-    done.insert({(const void*)kernel, dev});
-    return DPR_OK;
-}
 template <typename T, int NI, int NO>
 static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGeom<NO>& tg,
                             const Plan& pl, char* ws, int64_t P, const T* points, const T* pw,
                             const T* rot, const T* trans, int64_t b, int nb, bool want_idx,
                             bool keep_valid, const T* hdr_points, const T* hdr_pw) {
-    if (!hdr_points) {  // the header names the caller's buffers
-        hdr_points = points;
-        hdr_pw = pw;
-    }
     // ndesc[NT] | npts[NT] | - | max|pw| bits, and behind them the placement's cursors
     const size_t ltot_bytes = (pl.off_dcursor - pl.off_ltot) + (size_t)tg.NT * 4;
     if (nb > 1)
@@ -3744,6 +3281,7 @@ static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGe
     stage_mark(st);
     const uint32_t spare = (uint32_t)(pl.nsub * pl.sub);
     const size_t lds = (size_t)tg.NT * 4;
+    // (the kernels of local binning find the pose copies themselves: they take the offsets)
     LocalBinArgs la;
     la.ws = ws;
     la.pose_stride = pl.pose_stride;
@@ -3756,7 +3294,7 @@ static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGe
     do {                                                                                          \
         auto kern = k_bin_local<T, NI, NO, HAS_PW, (sizeof(T) == 4 ? 4096 : 2048), W3, ONE, TH,  \
                                 STAGE>;                                                           \
-        if (int rc = allow_lds_bytes(kern, lds)) return rc;                                       \
+        if (int rc = allow_dynamic_lds(kern, lds, kMaxLocalTiles * 4)) return rc;                 \
         hipLaunchKernelGGL(kern, dim3((unsigned)pl.nsub), dim3(TH), lds, st, gd, tg, P, points,   \
                            pw, rot, trans, b, nb, la, want_idx ? 1 : 0, spare, (T*)nullptr,       \
                            (T*)nullptr, 0);                                                       \
@@ -3777,8 +3315,6 @@ static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGe
 #undef DPR_LAUNCH_LOCAL
 #undef DPR_LAUNCH_LOCAL2
     stage_mark(st);
-    int64_t grid64[3] = {1, 1, 1};
-    for (int d = 0; d < NO; ++d) grid64[d] = gd.n[d];
     RunScanArgs ra;
     ra.ws = ws;
     ra.pose_stride = pl.pose_stride;
@@ -3794,13 +3330,7 @@ static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGe
     ra.NT = tg.NT;
     ra.cap = pl.cap;
     ra.max_items = pl.max_items;
-    ra.hdr = make_header<T, NI, NO>(grid64, P, hdr_points, hdr_pw);
-    ra.hdr.state = keep_valid ? kBinValid : 0u;
-    ra.hdr.layout = plan_layout_id(pl);
-    ra.rot = (const uint32_t*)(rot + b * (NO * NI));
-    ra.rot_words = (int)(NO * NI * sizeof(T) / 4);
-    ra.trans = (const uint32_t*)(trans + b * NO);
-    ra.trans_words = (int)(NO * sizeof(T) / 4);
+    fill_header<T, NI, NO>(ra, gd, pl, P, points, pw, hdr_points, hdr_pw, rot, trans, b, keep_valid);
     // the run scan rides in the placement launch when every placement workgroup can scan the
     // descriptor counts itself (up to 4096 tiles)
     const bool fused = tg.NT <= 4096;
@@ -3815,26 +3345,24 @@ static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGe
     return DPR_OK;
 }
 
+// the halo pass of the poses [b, b + nb) of `out`
+template <typename T, int NO>
+static void launch_halo_gather(hipStream_t st, const GridDesc<NO>& gd, const TileGeom<NO>& tg, const PoseWs& w,
+                               const T* halo, const T* ovf, const T* bg, int64_t b, int nb, T* out) {
+    hipLaunchKernelGGL((k_halo_gather<T, NO>), dim3(tg.NT * nb + kSplitGrid), dim3(256), 0, st, gd, tg, halo, ovf,
+                       w.tparts(), w.tslab(), w.split(), w.n_split(), bg, b, nb, out);
+}
+
 template <typename T, int NI, int NO>
 int raster_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G, int64_t P,
                  int64_t B, T* out, const T* points, const T* rot, const T* trans, const T* bg,
                  const T* ow, const T* pw, void* ws_, size_t ws_bytes) {
     SlabCut sc;
-    if (!make_slab_cut<NO>(grid, &sc))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "DPR_ALGO_TILED: a tile layer of the grid has more than %d tiles", kMaxTiles / 2);
-    if (P >= (int64_t)1 << 32)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "DPR_ALGO_TILED: P must be < 2^32");
-    if (sc.nslab > 1 && (flags & 3u))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "DPR_ALGO_TILED: a grid of more than %d tiles is processed in slabs, whose "
-                    "binning cannot be kept (DPR_FLAG_KEEP_BINNING)", kMaxTiles);
+    if (int rc = tiled_check(NO, grid, P, flags, "DPR_FLAG_KEEP_BINNING", &sc)) return rc;
     const int NTmax = slab_max_tiles(sc);
     const bool keep = flags & DPR_FLAG_KEEP_BINNING;
     // KEEP_BINNING with B > 1: every pose keeps its own binning (Plan::pose_stride)
-    const Plan pl = make_plan(sizeof(T), NO, NTmax, P, B, (int)((flags >> 8) & 0xffu),
-                              (flags & DPR_FLAG_COHERENT_POINTS) != 0, NI, (flags & 3u) != 0,
-                              sc.nslab > 1, !(flags & 3u));
+    const Plan pl = make_plan(plan_request(sizeof(T), DPR_OP_RASTER, flags, NI, NO, sc, P, B));
     if (!ws_ || ws_bytes < pl.total)
         return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_TILED raster needs %zu workspace bytes, got %zu",
                     pl.total, ws_ ? ws_bytes : (size_t)0);
@@ -3855,48 +3383,38 @@ int raster_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G,
     T* halo = (T*)(ws + pl.off_aux);
     T* ovf = (T*)(ws + pl.off_aux +
                   align_up((size_t)NTmax * pl.bg * halo_count<NO>() * sizeof(T)));
-    // copy of the per-pose workspace pose b lives in: its own when the binning is kept, else its
-    // place in the local batch
-    auto copy_of = [&](int64_t b) { return (flags & 3u) && B > 1 ? b : (pl.local ? b % pl.lb : 0); };
-    for (int64_t b = 0, nb = 1; b < B; b += nb) {
-        for (nb = 1; nb * 2 <= pl.bg && b + nb * 2 <= B;) nb *= 2;  // poses of this group
+    const PoseWalk walk{pl, ws, (flags & 3u) != 0, B};
+    for (int64_t b = 0, nb; b < B; b += nb) {
+        nb = walk.group(b);  // poses of this group
         // per-pose part of the workspace (one copy, or one per pose when the binning is kept)
-        char* const wsb = ws + (size_t)copy_of(b) * pl.pose_stride;
-        char* const ws0 = pl.local ? ws + (size_t)copy_of(b - b % pl.lb) * pl.pose_stride : wsb;  // copy 0 of the local batch
+        const PoseWs w = walk.at(b);
+        const PoseWs w0 = pl.local ? walk.at(b - b % pl.lb) : w;  // copy 0 of the local batch
         // slabs of a grid beyond kMaxTiles tiles, bottom to top (one iteration otherwise): slab s + 1
         // re-bins the top layer of slab s as its ghost layer
         for (int slab = 0; slab < sc.nslab; ++slab) {
         const TileGeom<NO> tg = slab_geom<NO>(grid, sc, slab, true);
         if (pl.local) {
-            if (b % pl.lb == 0) {  // first pose of a local batch: bin all its poses
-                const int nlb = (int)((B - b < pl.lb) ? B - b : pl.lb);
-                if (int rc = bin_points_local<T, NI, NO>(st, gd, tg, pl, wsb, P, points, pw, rot, trans,
-                                                         b, nlb, keep, keep, user_points, user_pw))
+            if (walk.opens_local_batch(b)) {  // first pose of a local batch: bin all its poses
+                if (int rc = bin_points_local<T, NI, NO>(st, gd, tg, pl, w.base, P, points, pw, rot, trans, b,
+                                                         walk.local_batch(b), keep, keep, user_points, user_pw))
                     return rc;
             }
-        } else if (int rc = bin_points<T, NI, NO>(st, gd, tg, pl, wsb, P, points, pw, rot, trans, b,
+        } else if (int rc = bin_points<T, NI, NO>(st, gd, tg, pl, w.base, P, points, pw, rot, trans, b,
                                                   (int)nb, keep, keep, user_points, user_pw))
             return rc;
         // (k_tile_splat's record assignment: 2 = chosen on the device from the order of the cloud;
         // the last argument asks for fixed-point sums wherever FixScale allows them)
 #define DPR_LAUNCH_SPLAT_RUNS(HAS_PW, W3)                                                        \
     hipLaunchKernelGGL((k_tile_splat_runs<T, NI, NO, HAS_PW, W3, true>), dim3(pl.max_items),    \
-                       dim3(kSplatThreads), 0, st, gd, tg,                                      \
-                       (const RecT<T, W3>*)(wsb + pl.off_rec),                                  \
-                       (const RunDesc*)(wsb + pl.off_sdesc), (uint32_t)(pl.nsub * pl.sub),      \
-                       (const WorkItem*)(wsb + pl.off_items),                                   \
-                       (const uint32_t*)(wsb + pl.off_nitems),                                  \
-                       (const uint32_t*)(wsb + pl.off_tslab), rot, trans, ow, bg, b, out, halo, \
-                       ovf, pl.sort_inside ? 0 : 1, (const uint32_t*)(ws0 + pl.off_ltot) + 2 * tg.NT, \
-                       1)
+                       dim3(kSplatThreads), 0, st, gd, tg, w.rec<const RecT<T, W3>>(),          \
+                       w.sdesc(), w.max_rec(), w.items(), w.n_items(), w.tslab(), rot, trans,   \
+                       ow, bg, b, out, halo, ovf, pl.sort_inside ? 0 : 1,                       \
+                       w0.ltot() + 2 * tg.NT, 1)
 #define DPR_LAUNCH_SPLAT(HAS_PW, W3)                                                             \
     hipLaunchKernelGGL((k_tile_splat<T, NI, NO, HAS_PW, W3>), dim3(pl.max_items),               \
-                       dim3(kSplatThreads), 0, st, gd, tg,                                      \
-                       (const RecT<T, W3>*)(wsb + pl.off_rec),                                  \
-                       (const WorkItem*)(wsb + pl.off_items),                                   \
-                       (const uint32_t*)(wsb + pl.off_nitems),                                  \
-                       (const uint32_t*)(wsb + pl.off_tslab), rot, trans, ow, bg, b, out, halo, \
-                       ovf, 2, (const uint32_t*)(wsb + pl.off_nitems) + 2, 1, (const T*)nullptr)
+                       dim3(kSplatThreads), 0, st, gd, tg, w.rec<const RecT<T, W3>>(),          \
+                       w.items(), w.n_items(), w.tslab(), rot, trans, ow, bg, b, out, halo,     \
+                       ovf, 2, w.weight_keys(), 1, (const T*)nullptr)
         if (pl.local) {
             if (pw) DPR_LAUNCH_SPLAT_RUNS(true, false);
             else if (!keep) DPR_LAUNCH_SPLAT_RUNS(false, true);
@@ -3907,13 +3425,7 @@ int raster_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t G,
 #undef DPR_LAUNCH_SPLAT
 #undef DPR_LAUNCH_SPLAT_RUNS
         stage_mark(st);
-        hipLaunchKernelGGL((k_halo_gather<T, NO>),
-                           dim3(tg.NT * (int)nb + kSplitGrid),
-                           dim3(256), 0, st, gd, tg, (const T*)halo, (const T*)ovf,
-                           (const uint32_t*)(wsb + pl.off_tparts),
-                           (const uint32_t*)(wsb + pl.off_tslab),
-                           (const uint32_t*)(wsb + pl.off_split) + 1,
-                           (const uint32_t*)(wsb + pl.off_split), bg, b, (int)nb, out);
+        launch_halo_gather<T, NO>(st, gd, tg, w, halo, ovf, bg, b, (int)nb, out);
         stage_mark(st);
         }  // slabs
     }
@@ -3927,20 +3439,9 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
                    const T* ow, const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow,
                    T* d_pw, void* ws_, size_t ws_bytes, Residual<T> rs) {
     SlabCut sc;
-    if (!make_slab_cut<NO>(grid, &sc))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "DPR_ALGO_TILED: a tile layer of the grid has more than %d tiles", kMaxTiles / 2);
-    if (P >= (int64_t)1 << 32)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "DPR_ALGO_TILED: P must be < 2^32");
-    if (sc.nslab > 1 && (flags & 3u))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "DPR_ALGO_TILED: a grid of more than %d tiles is processed in slabs, whose "
-                    "binning cannot be kept (DPR_FLAG_REUSE_BINNING)", kMaxTiles);
-    const int NTmax = slab_max_tiles(sc);
+    if (int rc = tiled_check(NO, grid, P, flags, "DPR_FLAG_REUSE_BINNING", &sc)) return rc;
     const bool reuse = flags & DPR_FLAG_REUSE_BINNING;
-    const Plan pl = make_plan(sizeof(T), NO, NTmax, P, B, (int)((flags >> 8) & 0xffu),
-                              (flags & DPR_FLAG_COHERENT_POINTS) != 0, NI, (flags & 3u) != 0,
-                              sc.nslab > 1);
+    const Plan pl = make_plan(plan_request(sizeof(T), DPR_OP_PULLBACK, flags, NI, NO, sc, P, B));
     if (!ws_ || ws_bytes < pl.total)
         return fail(DPR_ERR_WORKSPACE,
                     "DPR_ALGO_TILED pullback needs %zu workspace bytes, got %zu", pl.total,
@@ -3978,21 +3479,21 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
                               (reuse || pl.local);
     // poses whose gradient records are summed by one un-permute pass
     const int64_t ub = !batch_unperm ? 1 : ((flags & 3u) ? B : pl.lb);
-    auto copy_of = [&](int64_t b) { return (flags & 3u) && B > 1 ? b : (pl.local ? b % pl.lb : 0); };
-    for (int64_t b = 0, nb = 1; b < B; b += nb) {
-        for (nb = 1; nb * 2 <= pl.bg && b + nb * 2 <= B;) nb *= 2;  // poses of this group
+    const PoseWalk walk{pl, ws, (flags & 3u) != 0, B};
+    for (int64_t b = 0, nb; b < B; b += nb) {
+        nb = walk.group(b);  // poses of this group
         // per-pose part of the workspace (one copy, or one per pose when the binning was kept)
-        char* const wsb = ws + (size_t)copy_of(b) * pl.pose_stride;
+        const PoseWs w = walk.at(b);
         // slabs of a grid beyond kMaxTiles tiles (one iteration otherwise): every slab bins the
         // cloud again, gathers its tiles, and ADDS its share of the point gradients and per-pose sums
         for (int slab = 0; slab < sc.nslab; ++slab) {
         const TileGeom<NO> tg = slab_geom<NO>(grid, sc, slab, false);
         const bool first_acc = b == 0 && slab == 0;  // the pass that overwrites ds_dpoints / ds_dpoint_weight
-        BinHeader* hdr = reuse ? (BinHeader*)(wsb + pl.off_hdr) : (BinHeader*)nullptr;
+        BinHeader* hdr = reuse ? w.hdr() : (BinHeader*)nullptr;
         PoseReduceArgs<T> pr;
         pr.partials = partials;
-        pr.items = (const WorkItem*)(wsb + pl.off_items);
-        pr.n_items = (const uint32_t*)(wsb + pl.off_nitems);
+        pr.items = w.items();
+        pr.n_items = w.n_items();
         pr.max_items = pl.max_items;
         pr.NT = tg.NT;
         pr.n_in = NI;
@@ -4007,43 +3508,34 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
         pr.accumulate = slab > 0 ? 1 : 0;
         const unsigned n_reduce = (unsigned)(rs.target ? NVAL + 1 : NVAL);
         bool reduced = false;
-        if (reuse) {
-            // The binning of the preceding raster call (same points / pose / grid) is in the
+        if (reuse || (pl.local && !walk.opens_local_batch(b))) {
+            // REUSE: the binning of the preceding raster call (same points / pose / grid) is in the
             // workspace (points without an in-range voxel are in no tile: the un-permute reads
-            // zeros from the spare slot for them).
+            // zeros from the spare slot for them).  A later pose of a local batch: binned with the
+            // first.  The three binning stages are marked, empty.
             stage_mark(st);
             stage_mark(st);
             stage_mark(st);
-        } else if (pl.local) {
-            if (b % pl.lb == 0) {  // first pose of a local batch: bin all its poses
-                const int nlb = (int)((B - b < pl.lb) ? B - b : pl.lb);
-                if (int rc = bin_points_local<T, NI, NO>(st, gd, tg, pl, wsb, P, points, pw, rot, trans,
-                                                         b, nlb, true, false, user_points, user_pw))
-                    return rc;
-            } else {
-                stage_mark(st);
-                stage_mark(st);
-                stage_mark(st);
-            }
-        } else if (int rc = bin_points<T, NI, NO>(st, gd, tg, pl, wsb, P, points, pw, rot, trans, b,
+        } else if (pl.local) {  // first pose of a local batch: bin all its poses
+            if (int rc = bin_points_local<T, NI, NO>(st, gd, tg, pl, w.base, P, points, pw, rot, trans, b,
+                                                     walk.local_batch(b), true, false, user_points, user_pw))
+                return rc;
+        } else if (int rc = bin_points<T, NI, NO>(st, gd, tg, pl, w.base, P, points, pw, rot, trans, b,
                                                   (int)nb, true, false, user_points, user_pw))
             return rc;
         // The gradient {d point, d point_weight} of every point overwrites its record; k_unpermute
         // brings the records back to the original order
 #define DPR_LAUNCH_GATHER_RUNS(HAS_PW)                                                           \
     hipLaunchKernelGGL((k_tile_gather_runs<T, NI, NO, HAS_PW, true, true, true>),                \
-                       dim3(pl.max_items), dim3(gather_threads<T>()), 0, st, gd, tg,                  \
-                       (Rec4<T>*)(wsb + pl.off_rec), (const RunDesc*)(wsb + pl.off_sdesc),       \
-                       pl.nsub * pl.sub, (const uint32_t*)(wsb + pl.off_idx),                    \
-                       (const WorkItem*)(wsb + pl.off_items),                                    \
-                       (const uint32_t*)(wsb + pl.off_nitems), pl.max_items, g, rot, trans, ow,  \
-                       b, d_pts, d_pw, partials, rs, want, hdr)
+                       dim3(pl.max_items), dim3(gather_threads<T>()), 0, st, gd, tg,             \
+                       w.rec<Rec4<T>>(), w.sdesc(), pl.nsub * pl.sub, w.idx(), w.items(),        \
+                       w.n_items(), pl.max_items, g, rot, trans, ow, b, d_pts, d_pw, partials,   \
+                       rs, want, hdr)
 #define DPR_LAUNCH_GATHER_PLAIN(HAS_PW)                                                          \
     hipLaunchKernelGGL((k_tile_gather<T, NI, NO, HAS_PW, true, true>), dim3(pl.max_items),       \
-                       dim3(gather_threads<T>()), 0, st, gd, tg, (Rec4<T>*)(wsb + pl.off_rec), P * nb, \
-                       (const uint32_t*)(wsb + pl.off_idx), (const WorkItem*)(wsb + pl.off_items), \
-                       (const uint32_t*)(wsb + pl.off_nitems), pl.max_items, g, rot, trans, ow,   \
-                       b, d_pts, d_pw, partials, rs, want, hdr)
+                       dim3(gather_threads<T>()), 0, st, gd, tg, w.rec<Rec4<T>>(), P * nb,       \
+                       w.idx(), w.items(), w.n_items(), pl.max_items, g, rot, trans, ow, b,      \
+                       d_pts, d_pw, partials, rs, want, hdr)
         if (pl.local) {
             if (pw) DPR_LAUNCH_GATHER_RUNS(true);
             else DPR_LAUNCH_GATHER_RUNS(false);
@@ -4058,9 +3550,8 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
 #define DPR_LAUNCH_UNPERM(FIRST, UPB, RB)                                                        \
     hipLaunchKernelGGL((k_unpermute<T, NI, FIRST, UPB>),                                         \
                        dim3((unsigned)((P + UPB * 1024 - 1) / (UPB * 1024)) + (RB)), dim3(1024), \
-                       0, st, P, (int)nb, (const Rec4<T>*)(wsb + pl.off_rec),                    \
-                       (const uint32_t*)(wsb + pl.off_slot), d_pts, d_pw, (const BinHeader*)hdr, \
-                       (int)(RB), pr, (size_t)0)
+                       0, st, P, (int)nb, w.rec<const Rec4<T>>(), w.slot(), d_pts, d_pw,         \
+                       (const BinHeader*)hdr, (int)(RB), pr, (size_t)0)
             if (batch_unperm) {
                 // a kept batch: the records of all poses are summed once, after the loop
             } else if (nb > 1) {
@@ -4083,19 +3574,13 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
         if (batch_unperm && ((b + 1) % ub == 0 || b + 1 == B)) {
             // the gradient records of the batch that ends with pose b: summed per point in one pass
             const int64_t bs = b - b % ub;  // first pose of the batch
-            char* const wsu = ws + (size_t)copy_of(bs) * pl.pose_stride;
-            const BinHeader* uh = reuse ? (const BinHeader*)(wsu + pl.off_hdr) : (const BinHeader*)nullptr;
+            const PoseWs wu = walk.at(bs);
+            const BinHeader* uh = reuse ? wu.hdr() : (const BinHeader*)nullptr;
             PoseReduceArgs<T> none{};
-            if (bs == 0)
-                hipLaunchKernelGGL((k_unpermute<T, NI, true, 1>), dim3((unsigned)((P + 1023) / 1024)),
-                                   dim3(1024), 0, st, P, (int)(b + 1 - bs),
-                                   (const Rec4<T>*)(wsu + pl.off_rec), (const uint32_t*)(wsu + pl.off_slot),
-                                   d_pts, d_pw, uh, 0, none, pl.pose_stride);
-            else
-                hipLaunchKernelGGL((k_unpermute<T, NI, false, 1>), dim3((unsigned)((P + 1023) / 1024)),
-                                   dim3(1024), 0, st, P, (int)(b + 1 - bs),
-                                   (const Rec4<T>*)(wsu + pl.off_rec), (const uint32_t*)(wsu + pl.off_slot),
-                                   d_pts, d_pw, uh, 0, none, pl.pose_stride);
+            auto unpermute_batch = bs == 0 ? k_unpermute<T, NI, true, 1> : k_unpermute<T, NI, false, 1>;
+            hipLaunchKernelGGL(unpermute_batch, dim3((unsigned)((P + 1023) / 1024)), dim3(1024), 0, st, P,
+                               (int)(b + 1 - bs), wu.rec<const Rec4<T>>(), wu.slot(), d_pts, d_pw, uh, 0, none,
+                               pl.pose_stride);
         }
     }
     if (pl.sort_inside && P > 0)
@@ -4151,20 +3636,6 @@ __global__ __launch_bounds__(256) void k_channel_weights(int64_t P, int C, const
         if (c < C) publish_max_abs(keys + 2 * c, key[c]);  // (C is uniform: every lane calls)
 }
 
-static size_t channel_part_bytes(size_t elem, int64_t P, int C) {
-    return align_up((size_t)C * (size_t)(P + 1) * elem) + align_up((size_t)C * 2 * 4);
-}
-
-// the single-channel plan of one pose (what a call with B = 1 and no flags runs)
-static Plan channel_plan(size_t elem, int n_in, int n_out, const SlabCut& sc, int64_t P) {
-    return make_plan(elem, n_out, slab_max_tiles(sc), P, 1, 1, false, n_in, false, false, true);
-}
-
-bool tiled_channels_supported(int n_out, const int64_t* grid, int64_t P) {
-    SlabCut sc;
-    return P < ((int64_t)1 << 32) && grid_cut(n_out, grid, &sc) && sc.nslab == 1;
-}
-
 // What the channel forward and the JVP share on DPR_ALGO_TILED: the one-pose plan of a single-slab grid, every pose
 // binned once (the binning ignores the weights: 4-word records carry the point index), and the halo pass of each
 // plane the caller's splat wrote.  The caller's own part of the workspace follows the plan's.
@@ -4181,12 +3652,11 @@ struct PoseBinning {
     // the support and workspace checks (`path` and `call` name the caller in the messages), the plan
     int init(const int64_t* grid, int64_t G, int64_t P, size_t need, void* ws_, size_t ws_bytes, const char* path,
              const char* call) {
-        if (!tiled_channels_supported(NO, grid, P))
+        SlabCut sc;
+        if (!pose_binning_cut(NO, grid, P, &sc))
             return fail(DPR_ERR_UNSUPPORTED_ALGO,
                         "%s: per-pose binning of a grid of at most %d tiles and P < 2^32 only", path, kMaxTiles);
-        SlabCut sc;
-        (void)make_slab_cut<NO>(grid, &sc);
-        pl = channel_plan(sizeof(T), NI, NO, sc, P);
+        pl = pose_plan(sizeof(T), NI, NO, sc, P);
         if (!ws_ || ws_bytes < need)
             return fail(DPR_ERR_WORKSPACE, "%s needs %zu workspace bytes, got %zu", call, need,
                         ws_ ? ws_bytes : (size_t)0);
@@ -4201,33 +3671,28 @@ struct PoseBinning {
         pass_blocks = (unsigned)blocks;
         return DPR_OK;
     }
+    PoseWs view() const { return {ws, pl}; }
     int bin(hipStream_t st, int64_t P, const T* points, const T* rot, const T* trans, const T* pw, int64_t b) const {
         return bin_points<T, NI, NO>(st, gd, tg, pl, ws, P, points, (const T*)nullptr, rot, trans, b, 1, true, false,
                                      points, pw);
     }
-    const Rec4<T>* rec() const { return (const Rec4<T>*)(ws + pl.off_rec); }
-    const uint32_t* n_rec() const { return (const uint32_t*)(ws + pl.off_tile_start) + tg.NT; }
+    const Rec4<T>* rec() const { return view().template rec<const Rec4<T>>(); }
+    const uint32_t* n_rec() const { return view().tile_start() + tg.NT; }
+    // one splat pass over the binned records of the pose (passed as pose 0) into the plane `out`: the
+    // instantiation KERNEL of k_tile_splat, its weight keys and its per-record operand (weights / coefficients)
+    template <typename K>
+    void splat(hipStream_t st, K kernel, const T* rot_b, const T* trans_b, const T* ow_b, const T* bg, T* out,
+               const uint32_t* keys, const T* per_record) const {
+        const PoseWs w = view();
+        hipLaunchKernelGGL(kernel, dim3(pl.max_items), dim3(kSplatThreads), 0, st, gd, tg, rec(), w.items(),
+                           w.n_items(), w.tslab(), rot_b, trans_b, ow_b, bg, (int64_t)0, out, halo, ovf, 2, keys, 1,
+                           per_record);
+    }
     // the halos of the plane `out` (background bg[0] for the low-face cells)
     void halo_gather(hipStream_t st, const T* bg, T* out) const {
-        hipLaunchKernelGGL((k_halo_gather<T, NO>), dim3(tg.NT + kSplitGrid), dim3(256), 0, st, gd, tg, (const T*)halo,
-                           (const T*)ovf, (const uint32_t*)(ws + pl.off_tparts), (const uint32_t*)(ws + pl.off_tslab),
-                           (const uint32_t*)(ws + pl.off_split) + 1, (const uint32_t*)(ws + pl.off_split), bg,
-                           (int64_t)0, 1, out);
+        launch_halo_gather<T, NO>(st, gd, tg, view(), halo, ovf, bg, (int64_t)0, 1, out);
     }
 };
-
-size_t tiled_channels_workspace_bytes(size_t elem, int n_in, int n_out, const int64_t* grid, int64_t P,
-                                      int64_t B, int C) {
-    if (!tiled_channels_supported(n_out, grid, P)) return (size_t)-1;
-    SlabCut sc;
-    (void)grid_cut(n_out, grid, &sc);
-    // (at least the single-channel DPR_ALGO_TILED workspace of the batch: a workspace sized for the
-    // single-channel call of the same shape plus the channel part always serves)
-    size_t base = tiled_workspace_bytes(elem, DPR_OP_RASTER, 0u, n_in, n_out, grid, P, B);
-    const size_t own = channel_plan(elem, n_in, n_out, sc, P).total;
-    if (own > base) base = own;
-    return base + channel_part_bytes(elem, P, C);
-}
 
 template <typename T, int NI, int NO>
 int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C, T* out,
@@ -4238,7 +3703,6 @@ int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_
     if (int rc = pb.init(grid, G, P, need, ws_, ws_bytes, "DPR_ALGO_TILED with channels",
                          "DPR_ALGO_TILED channel raster"))
         return rc;
-    const Plan& pl = pb.pl;
     char* const ws = pb.ws;
     const size_t off_ch = need - channel_part_bytes(sizeof(T), P, C);
     T* w_sorted = (T*)(ws + off_ch);
@@ -4258,19 +3722,11 @@ int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_
             const T* bg_c = bg ? bg + b * C + c : nullptr;
             T* out_c = out + (b * C + c) * G;
             if (pw)
-                hipLaunchKernelGGL((k_tile_splat<T, NI, NO, true, false, true>), dim3(pl.max_items),
-                                   dim3(kSplatThreads), 0, st, pb.gd, pb.tg, pb.rec(),
-                                   (const WorkItem*)(ws + pl.off_items), (const uint32_t*)(ws + pl.off_nitems),
-                                   (const uint32_t*)(ws + pl.off_tslab), rot_b, trans_b, ow_b, bg_c, (int64_t)0,
-                                   out_c, pb.halo, pb.ovf, 2, (const uint32_t*)(keys + 2 * c), 1,
-                                   (const T*)(w_sorted + (int64_t)c * (P + 1)));
+                pb.splat(st, k_tile_splat<T, NI, NO, true, false, true>, rot_b, trans_b, ow_b, bg_c, out_c,
+                         (const uint32_t*)(keys + 2 * c), (const T*)(w_sorted + (int64_t)c * (P + 1)));
             else
-                hipLaunchKernelGGL((k_tile_splat<T, NI, NO, false, false>), dim3(pl.max_items),
-                                   dim3(kSplatThreads), 0, st, pb.gd, pb.tg, pb.rec(),
-                                   (const WorkItem*)(ws + pl.off_items), (const uint32_t*)(ws + pl.off_nitems),
-                                   (const uint32_t*)(ws + pl.off_tslab), rot_b, trans_b, ow_b, bg_c, (int64_t)0,
-                                   out_c, pb.halo, pb.ovf, 2, (const uint32_t*)(ws + pl.off_nitems) + 2, 1,
-                                   (const T*)nullptr);
+                pb.splat(st, k_tile_splat<T, NI, NO, false, false>, rot_b, trans_b, ow_b, bg_c, out_c,
+                         (const uint32_t*)pb.view().weight_keys(), (const T*)nullptr);
             stage_mark(st);
             pb.halo_gather(st, bg_c, out_c);
             stage_mark(st);
@@ -4323,17 +3779,6 @@ __global__ __launch_bounds__(256) void k_jvp_coeffs(GridDesc<NO> gd, int64_t P, 
     publish_max_abs(keys, key);  // (every lane gets here)
 }
 
-static size_t jvp_part_bytes(size_t elem, int64_t P) {
-    return align_up((size_t)(P + 1) * 4 * elem) + align_up(2 * 4);
-}
-
-size_t tiled_jvp_workspace_bytes(size_t elem, int n_in, int n_out, const int64_t* grid, int64_t P) {
-    if (!tiled_channels_supported(n_out, grid, P)) return (size_t)-1;
-    SlabCut sc;
-    (void)grid_cut(n_out, grid, &sc);
-    return align_up(channel_plan(elem, n_in, n_out, sc, P).total) + jvp_part_bytes(elem, P);
-}
-
 template <typename T, int NI, int NO>
 int raster_tiled_jvp(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
                      const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan,
@@ -4341,7 +3786,6 @@ int raster_tiled_jvp(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, 
     const size_t need = tiled_jvp_workspace_bytes(sizeof(T), NI, NO, grid, P);
     PoseBinning<T, NI, NO> pb;
     if (int rc = pb.init(grid, G, P, need, ws_, ws_bytes, "DPR_ALGO_TILED JVP", "DPR_ALGO_TILED JVP")) return rc;
-    const Plan& pl = pb.pl;
     char* const ws = pb.ws;
     const size_t off_jvp = need - jvp_part_bytes(sizeof(T), P);
     Rec4<T>* coef = (Rec4<T>*)(ws + off_jvp);
@@ -4364,11 +3808,8 @@ int raster_tiled_jvp(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, 
             // the pose's parameters, the background tangent and the plane are passed as pose 0
             const T* bg_kb = bg_dot ? bg_dot + kb : nullptr;
             T* out_kb = out_dot + (b * K + k) * G;
-            hipLaunchKernelGGL((k_tile_splat<T, NI, NO, true, false, false, true>), dim3(pl.max_items),
-                               dim3(kSplatThreads), 0, st, pb.gd, pb.tg, pb.rec(),
-                               (const WorkItem*)(ws + pl.off_items), (const uint32_t*)(ws + pl.off_nitems),
-                               (const uint32_t*)(ws + pl.off_tslab), rot_b, trans_b, (const T*)nullptr, bg_kb,
-                               (int64_t)0, out_kb, pb.halo, pb.ovf, 2, (const uint32_t*)keys, 1, (const T*)coef);
+            pb.splat(st, k_tile_splat<T, NI, NO, true, false, false, true>, rot_b, trans_b, (const T*)nullptr, bg_kb,
+                     out_kb, (const uint32_t*)keys, (const T*)coef);
             stage_mark(st);
             pb.halo_gather(st, bg_kb, out_kb);
             stage_mark(st);

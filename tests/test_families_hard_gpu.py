@@ -62,7 +62,7 @@ pytestmark = pytest.mark.gpu
 DTYPES = [(np.float64, torch.float64), (np.float32, torch.float32)]
 TILE = {3: (64, 16, 8), 2: (32, 32)}
 # A tile is split into parts above max(P / 256, 4096) records (3-D; twice that in a forward-only call) or above
-# max(P / 2048, 2048) records (2-D) -- make_plan in csrc/dpr_tiled.hip.  Above SPLIT records a tile of these inputs
+# max(P / 2048, 2048) records (2-D) -- make_plan in csrc/dpr_tiled_plan.hip.  Above SPLIT records a tile of these inputs
 # is split on every path.
 SPLIT = {3: 8192, 2: 2048}
 SPEC = {  # name: n_in, n_out, grid, points, kind, seed

@@ -86,7 +86,7 @@ SPEC = {
     "W2_32": (3, 2, (100, 70), 12_000, 44),
     "W2_22": (2, 2, (100, 70), 12_000, 13),
 }
-CAP = {3: 4096, 2: 2048}  # records per tile below which no path splits a tile (make_plan in csrc/dpr_tiled.hip)
+CAP = {3: 4096, 2: 2048}  # records per tile below which no path splits a tile (make_plan in csrc/dpr_tiled_plan.hip)
 FAR = 8  # points far outside every grid, appended to every input
 CLOUD_GRIDS = {"C2": (64, 64), "C3": (40, 33, 20)}
 CLOUD_P = (1500, 20_000)  # one slice per (pose, tile) / several slices (test_chunked_tiles_and_slices)
