@@ -26,6 +26,7 @@ ALGO_AUTO = 0
 ALGO_ATOMIC = 1
 ALGO_TILED = 2
 ALGO_CHUNKED = 3
+ALGO_ORDERED = 4
 FLAG_KEEP_BINNING = 1
 FLAG_REUSE_BINNING = 2
 FLAG_COHERENT_POINTS = 4
@@ -37,7 +38,8 @@ def flag_max_pose_group(n: int) -> int:
     if not 0 <= int(n) <= 16:
         raise ValueError("max_pose_group must be in 0..16")
     return (int(n) & 0xFF) << 8
-ALGOS = {"auto": ALGO_AUTO, "atomic": ALGO_ATOMIC, "tiled": ALGO_TILED, "chunked": ALGO_CHUNKED}
+ALGOS = {"auto": ALGO_AUTO, "atomic": ALGO_ATOMIC, "tiled": ALGO_TILED, "chunked": ALGO_CHUNKED,
+         "ordered": ALGO_ORDERED}
 
 EXPORTS = [
     "dpr_version", "dpr_last_error", "dpr_stage_timing_begin", "dpr_stage_timing_end",

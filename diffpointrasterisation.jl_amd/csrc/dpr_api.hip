@@ -17,6 +17,7 @@
 #include "dpr_kernels_clouds.h"
 #include "dpr_kernels_jvp.h"
 #include "dpr_kernels_sample.h"
+#include "dpr_ordered.h"
 #include "dpr_tiled.h"
 
 namespace dpr {
@@ -425,6 +426,11 @@ static int raster_impl(void* stream, int algo, unsigned flags, int n_in, int n_o
         constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
         if (algo == DPR_ALGO_ATOMIC && !(flags & 3u))
             return raster_atomic<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, bg, ow, pw);
+        if (algo == DPR_ALGO_ORDERED) {  // every (n_in, n_out); COHERENT_POINTS / MAX_POSE_GROUP: nothing to do with them
+            if (flags & 3u)
+                return fail(DPR_ERR_UNSUPPORTED_ALGO, "DPR_ALGO_ORDERED keeps / reuses no binning");
+            return raster_ordered<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, bg, ow, pw, ws, ws_bytes);
+        }
         if constexpr (!dims_have_all_algos(NI, NO)) {
             return fail(DPR_ERR_UNSUPPORTED_ALGO,
                         "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only (no flags)", n_in, n_out);
@@ -643,6 +649,12 @@ static int pullback_impl(void* stream, int algo, unsigned flags, int n_in, int n
         if (algo == DPR_ALGO_ATOMIC && !(flags & 3u))
             return pullback_atomic<T, NI, NO>(st, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans,
                                               d_bg, d_ow, d_pw, rs);
+        if (algo == DPR_ALGO_ORDERED) {
+            if (flags & 3u)
+                return fail(DPR_ERR_UNSUPPORTED_ALGO, "DPR_ALGO_ORDERED keeps / reuses no binning");
+            return pullback_ordered<T, NI, NO>(st, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans,
+                                               d_bg, d_ow, d_pw, ws, ws_bytes, rs);
+        }
         if constexpr (!dims_have_all_algos(NI, NO)) {
             return fail(DPR_ERR_UNSUPPORTED_ALGO,
                         "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only (no flags)", n_in, n_out);
@@ -691,6 +703,16 @@ static size_t workspace_impl(int op, int algo, unsigned flags, int n_in, int n_o
         op = DPR_OP_PULLBACK;  // (same buffers as the plain pullback of the algorithm chosen for it)
     }
     if (algo == DPR_ALGO_ATOMIC) return 0;
+    if (algo == DPR_ALGO_ORDERED) {
+        if (flags & 3u) {
+            fail(DPR_ERR_UNSUPPORTED_ALGO, "DPR_ALGO_ORDERED keeps / reuses no binning");
+            return (size_t)-1;
+        }
+        const size_t n = ordered_workspace_bytes(op, n_in, n_out, grid, P, B);
+        if (n == (size_t)-1)
+            fail(DPR_ERR_UNSUPPORTED_ALGO, "DPR_ALGO_ORDERED: the extended grid must fit 32-bit keys and P <= 2^32 - 2");
+        return n;
+    }
     if (!dims_have_all_algos(n_in, n_out)) {
         fail(DPR_ERR_UNSUPPORTED_ALGO, "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only", n_in,
              n_out);

@@ -22,6 +22,7 @@
 
 #include "../../include/dpr.h"
 #include "dpr_hilbert.h"
+#include "dpr_ordered.h"
 #include "dpr_tiled.h"
 
 namespace dpr {
@@ -101,6 +102,16 @@ static size_t radix_temp_bytes(int64_t P) {
     (void)rocprim::radix_sort_pairs(nullptr, temp, nul, nul, nul, nul, (size_t)P, 0, 32,
                                     (hipStream_t)0);
     return temp;
+}
+
+// the same instantiation for the other callers of the library (dpr_ordered.hip): bytes of temporary storage, and the
+// stable sort of (key, value) pairs on key bits [begin_bit, end_bit)
+size_t radix_pairs_temp_bytes(int64_t P) { return radix_temp_bytes(P < 1 ? 1 : P); }
+hipError_t radix_sort_pairs_u32(void* temp, size_t temp_bytes, uint32_t* keys_in, uint32_t* keys_out,
+                                uint32_t* vals_in, uint32_t* vals_out, size_t n, unsigned begin_bit,
+                                unsigned end_bit, hipStream_t st) {
+    return rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit,
+                                     st);
 }
 
 size_t sort_workspace_bytes(int64_t P) {

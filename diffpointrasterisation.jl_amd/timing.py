@@ -29,6 +29,9 @@ STAGES = {
     # DPR_ALGO_CHUNKED on 2-D grids (chunk-owned tiles): pass algo="chunked2d"
     ("raster", "chunked2d"): ["sort", "fill", "chunk_splat"],
     ("pullback", "chunked2d"): ["sort", "grid_sum", "chunk_gather", "reduce+unsort"],
+    # DPR_ALGO_ORDERED: the forward walks its four stages once per pose, the pullback once per call
+    ("raster", "ordered"): ["keys", "sort", "ranges", "gather"],
+    ("pullback", "ordered"): ["grid_sum", "gather", "reduce"],
 }
 
 _hip = None

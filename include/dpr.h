@@ -37,8 +37,8 @@
  * combination -- the reference is generic in both (src/raster.jl:5-13).
  * (2,2), (3,3), (3,2) -- the shapes the reference tests (src/raster.jl:112,
  * test/data.jl:13-19) -- have every algorithm; all other pairs (incl. n_out > n_in and 4-D) run on
- * DPR_ALGO_ATOMIC (what DPR_ALGO_AUTO resolves to for them; the other algorithms
- * and the KEEP / REUSE flags return DPR_ERR_UNSUPPORTED_ALGO).
+ * DPR_ALGO_ATOMIC (what DPR_ALGO_AUTO resolves to for them) or, on request, DPR_ALGO_ORDERED; the other
+ * algorithms and the KEEP / REUSE flags return DPR_ERR_UNSUPPORTED_ALGO.
  *
  * Error behaviour: the reference throws DimensionMismatch / ArgumentError before
  * any launch (src/raster.jl:14-23, ext/...CUDAExt.jl:246-262).  Here every entry
@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define DPR_VERSION 109 /* 0.1.9: + per-pose point clouds (dpr_raster_clouds_ex_*) */
+#define DPR_VERSION 110 /* 0.1.10: + DPR_ALGO_ORDERED (bit-reproducible raster and pullback) */
 
 /* status codes */
 #define DPR_OK 0
@@ -128,13 +128,48 @@ extern "C" {
                               1e6), the forward from 32 poses of a dense cloud of 3e6 points and
                               from 16 poses of a sparse one (P * 10 <= G) of 2e5 points.
                               Correct for any point order.
-   The multi-channel entry points (MULTI-CHANNEL below) run DPR_ALGO_ATOMIC or, for the forward,
+                           */
+#define DPR_ALGO_ORDERED 4 /* every sum in a FIXED order: all seven outputs (out, the six gradients) and the
+                              residual's loss are bit-reproducible -- run to run, device to device, whatever
+                              B and wherever the pose stands in the batch (SUMMATION ORDER below).  Opt-in:
+                              DPR_ALGO_AUTO never resolves to it.  For dpr_raster_ex_*, dpr_raster_pullback_ex_*
+                              and dpr_raster_residual_pullback_ex_*, both element types, every (n_in, n_out)
+                              with 1 <= n_in, n_out <= 4, any B.  No floating-point atomics.
+                              FORWARD, pose by pose: a 32-bit key per point (its reference cell on the grid
+                              extended by one cell on the low side of every axis; all ones for a rejected
+                              point), a stable radix sort of (key, point index) on the key bits that grid
+                              needs, a start table over the extended grid (a lower-bound search per entry),
+                              then one thread per output cell merges the <= 2^N index-sorted lists of its
+                              source cells by point index and adds the one neighbour of each point that
+                              lands on the cell, starting from the background: the forward is BIT-IDENTICAL
+                              to the serial reference order (pose, point, neighbour).
+                              PULLBACK: one thread per point, the pose loop over ALL poses inside the thread
+                              (never sliced, never atomic); per-pose sums through fixed chunks (below).
+                              COST: a cell's sum is serial by contract, so the forward's time grows with the
+                              most populated cell (a thread adds its cell's contributions one after another);
+                              a cloud concentrated on a few cells runs at the speed of those cells.
+                              LIMITS (DPR_ERR_UNSUPPORTED_ALGO, (size_t)-1 from the workspace query): the
+                              extended grid, prod (n_d + 1), must have at most 2^32 - 1 cells, and
+                              P <= 2^32 - 2.  Workspace: forward 16 P bytes + the sort's temporary storage
+                              + 4 (prod (n_d + 1) + 1) bytes, independent of B (0 for P = 0); pullback 8 bytes
+                              per (point chunk, pose, scalar) and 16 per (cell chunk, pose).
+                              FLAGS: KEEP / REUSE are refused (nothing to keep), COHERENT_POINTS and
+                              MAX_POSE_GROUP are accepted and ignored, NO_POINT_WEIGHT_GRAD is honoured.
+                              The other op families (channels, sampling, JVP, per-pose clouds) do not have
+                              it: DPR_ERR_UNSUPPORTED_ALGO. */
+/* The multi-channel entry points (MULTI-CHANNEL below) run DPR_ALGO_ATOMIC or, for the forward,
    DPR_ALGO_TILED: AUTO takes DPR_ALGO_TILED where the single-channel rule above prefers it for the shape
    and the grid is one slab, DPR_ALGO_ATOMIC otherwise (always for the pullback).
    The sampling entry points (SAMPLING below) run DPR_ALGO_ATOMIC for the forward; their pullback takes
    DPR_ALGO_TILED where the single-pose forward of the shape would, DPR_ALGO_ATOMIC otherwise.
    The per-pose cloud entry points (PER-POSE CLOUDS below) run DPR_ALGO_ATOMIC, DPR_ALGO_TILED (the single-pose
    tiled calls, pose by pose) or DPR_ALGO_CHUNKED (pose-owned LDS tiles). */
+
+/* Chunk sizes of DPR_ALGO_ORDERED's per-pose sums (compile-time constants; the reduction trees depend on
+ * nothing else): consecutive points per partial of ds_drotation / ds_dtranslation / ds_dout_weight, consecutive
+ * cells of a plane per partial of ds_dbackground / loss. */
+#define DPR_ORDERED_POINT_CHUNK 2048
+#define DPR_ORDERED_CELL_CHUNK 16384
 
 /* SUMMATION ORDER.  The reference promises none for its float atomics (src/raster.jl:64) and sums
  * serially per pose on the CPU (src/raster_pullback.jl:39-72).  Here, per algorithm and output:
@@ -163,6 +198,17 @@ extern "C" {
  *                        LDS atomics, rounding level.  3-D                                              inside) adds its waves' sums with f64 LDS atomics in
  *                        chunk lists (sparse clouds): f64 LDS                                           arrival order: rounding level of f64
  *                        atomics + diverted global atomics
+ *   DPR_ALGO_ORDERED     starts as background[b]; the            one thread per point, accumulators     the cloud cut into chunks of DPR_ORDERED_POINT_CHUNK
+ *                        contributions voxel_weight(dlo, s,      start at 0, poses added in index       consecutive points; a chunk's terms reduced in T by
+ *                        ow * pw) that land on a cell are added   order; never sliced over poses,        a fixed tree (sub-steps of 256 points: wave_sum,
+ *                        one at a time, in T, in ascending        never atomic: the bits of the serial   waves in index order; sub-steps in order); the chunk
+ *                        point index (a point reaches a cell      reference (oracle_raster_pullback)     partials added in f64 in ascending chunk order and
+ *                        through at most one neighbour): the                                             rounded to T once.  ds_dbackground and the residual's
+ *                        order and the BITS of the serial                                                loss: the same over chunks of DPR_ORDERED_CELL_CHUNK
+ *                        reference (oracle_raster), fp32 and                                             consecutive cells of plane b.  Nothing depends on B,
+ *                        fp64; independent of launch geometry,                                           the pose's index, a slice count or the CU count:
+ *                        device, B and the pose's index                                                  NONE OF IT VARIES -- same bits run to run, and for
+ *                                                                                                       a pose alone or anywhere inside a batch
  *
  *   channels (dpr_raster_channels_ex_* / dpr_raster_pullback_channels_ex_*, see MULTI-CHANNEL below):
  *   DPR_ALGO_TILED       fp32, fixed-point regime: every plane
@@ -314,7 +360,8 @@ int dpr_resolve_flags_ex(int op, unsigned flags, int n_in, int n_out, const int6
  * DPR_ALGO_CHUNKED, 3-D grids -- raster: boxes, plan, own_splat, combine;
  * pullback: direct_gather, pose_reduce.
  * DPR_ALGO_CHUNKED, 2-D grids -- raster: sort, fill, chunk_splat;
- * pullback: sort, grid_sum, chunk_gather, reduce+unsort. */
+ * pullback: sort, grid_sum, chunk_gather, reduce+unsort.
+ * DPR_ALGO_ORDERED, per pose -- raster: keys, sort, ranges, gather; pullback (once): grid_sum, gather, reduce. */
 int dpr_stage_timing_begin(void **events, int capacity);
 int dpr_stage_timing_end(void);
 

@@ -268,6 +268,7 @@ end
 # headline step is exactly this pairing; its `no_share` entry is the generic rrule.
 # Loaded only when ChainRulesCore is (a second weak dependency of this extension).
 const DPR_ALGO_AUTO, DPR_FLAG_KEEP_BINNING, DPR_FLAG_REUSE_BINNING = Cint(0), Cuint(1), Cuint(2)
+const DPR_ALGO_ORDERED = Cint(4)  # every sum in a fixed order: bit-reproducible raster and pullback (dpr.h)
 # The rrule drops the point_weight tangent whenever that argument was defaulted
 # (/root/reference/ext/DiffPointRasterisationChainRulesCoreExt.jl:23,70): the pullback is then told
 # not to compute or store it (`want_pw = false`: NULL pointer + this flag, include/dpr.h).
