@@ -110,8 +110,8 @@ extern "C" {
                               of 64-point chunks instead.  PULLBACK: a thread per point in cloud
                               order gathers its eight ds_dout cells straight from memory (no
                               workspace beyond the partial sums: 0.9 MB per pose, 64 poses at
-                              most); fp32 batches run the pose loop inside the kernel, fp64
-                              batches one launch per pose.
+                              most); batches run the pose loop inside the kernel, 64 poses per
+                              launch.
                               What AUTO picks with DPR_FLAG_COHERENT_POINTS: the owner-tile
                               forward for >= 2 poses of a DENSE cloud (0.4 <= P / G <= 2) on a
                               grid of >= 1024 such tiles (256^3: 1216); the chunk-list forward
@@ -176,28 +176,35 @@ extern "C" {
  *
  *   algorithm            forward `out`                           ds_dpoints / ds_dpoint_weight         per-pose sums (ds_drotation, ds_dtranslation,
  *                                                                                                       ds_dout_weight, ds_dbackground)
- *   DPR_ALGO_ATOMIC      global float atomics: depends on the    one thread per point, poses in        wave -> block -> one float atomic per block:
- *                        execution order (varies run to run,     index order: bit-reproducible         varies run to run at rounding level
- *                        rounding level)
+ *   DPR_ALGO_ATOMIC      global float atomics: depends on the    one thread per point.  Pose loop      wave -> block -> one float atomic per block:
+ *                        execution order (varies run to run,     inside the thread (B == 1, or         varies run to run at rounding level
+ *                        rounding level)                         P >= 524 033): bit-reproducible,
+ *                                                                the bits of the serial reference.
+ *                                                                Otherwise the poses are sliced:
+ *                                                                rounding level (note 1)
  *   DPR_ALGO_TILED       fp32: 64-bit fixed-point sums per       one gradient record per (point,       per-thread sums in T over the tile's records
- *                        tile, EXACT -- independent of the       pose), poses added in index order:    (their order in the tile's list varies), then
- *                        order of the points and of execution;   bit-reproducible                      f64 across threads and tiles in a fixed order:
- *                        tiles split into parts (> max(4096,                                           rounding level of T within a tile
- *                        P/256) records) add their parts in
+ *                        tile, EXACT -- independent of the       pose), added per point in a fixed     (their order in the tile's list varies), then
+ *                        order of the points and of execution;   order, group by group (note 2):       f64 across threads and tiles in a fixed order:
+ *                        tiles split into parts (> max(4096,     bit-reproducible, the same bits for   rounding level of T within a tile
+ *                        P/256) records) add their parts in      any order of the points
  *                        fp32 in a fixed order, the records
  *                        of a part vary: rounding level.
  *                        fp64: f64 LDS atomics, order-dependent
  *                        at 1e-16 relative
- *   DPR_ALGO_CHUNKED     2-D: exact fixed-point sums per chunk   registers across the poses, fixed      2-D: the 4096 terms of a (chunk, pose) as a
- *                        (fp32), then float atomics into the     order: bit-reproducible for a given    fixed tree in T (fp32 data; fp64: f64 across
- *                        image across chunks: run to run,        point order (2-D); 3-D: one thread     threads), the partials per (chunk, pose) in f64
- *                        rounding level.  3-D owner tiles:       per point, poses added in index        in a fixed order.  3-D: per-thread sums in T over
- *                        fp32 EXACT (64-bit fixed point, split   order through memory: bit-             a slice of the cloud (its size follows the CU
- *                        tiles summed as integers) -- the same   reproducible                           count of the device), then f64: one pose per launch
- *                        bits for any point order; fp64: f64                                            in a fixed order; the fp32 batch kernel (pose loop
- *                        LDS atomics, rounding level.  3-D                                              inside) adds its waves' sums with f64 LDS atomics in
- *                        chunk lists (sparse clouds): f64 LDS                                           arrival order: rounding level of f64
- *                        atomics + diverted global atomics
+ *   DPR_ALGO_CHUNKED     2-D: exact fixed-point sums per chunk   2-D: registers across the poses of     2-D: the 4096 terms of a (chunk, pose) as a
+ *                        (fp32; note 3), then float atomics      a chunk.  All poses in one block       fixed tree in T (fp32 data; fp64: f64 across
+ *                        into the image across chunks: run to    (B == 1, or P >= 4 190 209 and         threads), the partials per (chunk, pose) in f64
+ *                        run, rounding level.  3-D owner tiles:  B <= 64): bit-reproducible, the same   in a fixed order, however the poses are sliced
+ *                        fp32 EXACT (64-bit fixed point, split   bits wherever the point stands in the  (ds_dbackground: k_grid_sum, one float atomic per
+ *                        tiles summed as integers) -- the same   cloud.  Otherwise the poses are        4096 cells -- a fixed order up to 4096 cells).
+ *                        bits for any point order; fp64: f64     sliced: rounding level (note 1).       3-D: per-thread sums in T over a slice of the cloud
+ *                        LDS atomics, rounding level.  3-D       3-D: one thread per point, poses       (its size follows the CU count of the device), then
+ *                        chunk lists (sparse clouds): f64 LDS    added in index order (registers        f64.  One pose: a fixed order.  Batches (pose loop
+ *                        atomics + diverted global atomics       across a launch of <= 64 poses,        inside): fp64 ds_drotation / ds_dtranslation /
+ *                                                                memory between launches): bit-         ds_dout_weight in a fixed order; fp32 data, and
+ *                                                                reproducible, the same bits for any    ds_dbackground of either type, add their waves'
+ *                                                                point order                            sums with f64 LDS atomics in arrival order:
+ *                                                                                                       rounding level of f64
  *   DPR_ALGO_ORDERED     starts as background[b]; the            one thread per point, accumulators     the cloud cut into chunks of DPR_ORDERED_POINT_CHUNK
  *                        contributions voxel_weight(dlo, s,      start at 0, poses added in index       consecutive points; a chunk's terms reduced in T by
  *                        ow * pw) that land on a cell are added   order; never sliced over poses,        a fixed tree (sub-steps of 256 points: wave_sum,
@@ -225,9 +232,11 @@ extern "C" {
  *                        different cap / record order of split tiles).
  *                        A channel whose guard trips (or fp64 data):
  *                        f64 LDS atomics, as the single-channel call
- *   DPR_ALGO_ATOMIC      global float atomics, each contribution     one thread per point, poses in index   as DPR_ALGO_ATOMIC; the channels are
- *                        the single-channel value: rounding level    order, channels folded per gather:     folded per gather before the sums:
- *                                                                    bit-reproducible                       rounding level
+ *   DPR_ALGO_ATOMIC      global float atomics, each contribution     one thread per point, channels folded  as DPR_ALGO_ATOMIC; the channels are
+ *                        the single-channel value: rounding level    per gather.  Pose loop inside the      folded per gather before the sums:
+ *                                                                    thread (B == 1, or P >= 524 033):      rounding level
+ *                                                                    bit-reproducible; otherwise the poses
+ *                                                                    are sliced: rounding level (note 1)
  *
  *   per-pose clouds (dpr_raster_clouds_ex_* / dpr_raster_pullback_clouds_ex_*, see PER-POSE CLOUDS below):
  *   DPR_ALGO_ATOMIC      global float atomics: rounding level        one thread per (point, pose), one      wave -> block -> one float atomic per block:
@@ -241,6 +250,28 @@ extern "C" {
  *                        slices: float atomics across slices,                                               order: bit-reproducible run to run
  *                        rounding level; fp64 / guard tripped:                                              (ds_dbackground: k_grid_sum's block atomics,
  *                        f64 LDS atomics, rounding level                                                    rounding level on grids of several blocks)
+ *
+ * Note 1, pose slices.  A per-point kernel that would leave the device idle cuts the B poses into slices on
+ * the second grid axis; every slice adds its share of ds_dpoints / ds_dpoint_weight with float atomics onto
+ * zeroed buffers.  DPR_ALGO_ATOMIC and its channel form: fewer than 2048 blocks of 256 points (P <= 523 776)
+ * and B > 1 give up to min(B, ceil(2048 / blocks)) slices; from 2048 blocks on (P >= 524 033) one slice, whatever B.
+ * 2-D DPR_ALGO_CHUNKED: a slice holds pps = min(64, ceil(B / s)) poses, with s = min(B, ceil(1024 / chunks)) below
+ * 1024 chunks of 4096 points (P <= 4 190 208) and s = 1 from there on, and there are ceil(B / pps) slices.  A block
+ * never takes more than 64 poses, so one slice needs B == 1, or P >= 4 190 209 and B <= 64; at P >= 4 190 209,
+ * 65 <= B <= 128 gives two slices and B >= 129 three or more -- B >= 129 is sliced at any P.
+ * From three slices on the arrival order decides the bits: rounding level, varies run to run.  Two slices give
+ * the same bits run to run (two shares onto zero commute), but in general not those of the serial order.  A
+ * point that every pose rejects keeps the +0 of the memset.  Callers who need the bits: DPR_ALGO_ORDERED.
+ * Note 2, pose groups.  DPR_ALGO_TILED adds a point's records in index order within a group of poses binned
+ * together (16 / 8 / 4 / 2 / 1 poses by the grid's tile count and DPR_FLAG_MAX_POSE_GROUP; up to 8 poses of a
+ * DPR_FLAG_COHERENT_POINTS batch on local bins) and then adds the groups' sums in index order: for groups of
+ * 4 + 2 + 1 poses (g0 + g1 + g2 + g3) + (g4 + g5) + g6.  A batch whose binning was kept (KEEP / REUSE) and
+ * DPR_FLAG_MAX_POSE_GROUP(1) add pose by pose, ((g0 + g1) + g2) + ...: the same bits as each other, and as the
+ * grouped sum only while no group after the first holds more than one pose.
+ * Note 3, fixed-point forwards.  "EXACT" and "exact fixed-point sums" (DPR_ALGO_TILED, both DPR_ALGO_CHUNKED forwards,
+ * fp32) hold in the fixed-point regime: the non-zero |point_weight| of the scope within a span of 2^10, none NaN / Inf
+ * (PRECISION OF THE FIXED-POINT SUMS below; NULL weights always).  A scope with wider weights sums with IEEE f64
+ * atomics: rounding level, like fp64 data.
  *
  * "Rounding level" = the differences any two summation orders of the same terms show in the
  * accumulation type; no output depends on the order beyond that.  The contributions themselves
