@@ -18,6 +18,8 @@ from .sample import (SamplePullbackResult, resolve_algo_sample, sample, sample_,
 from .jvp import raster_jvp, raster_jvp_, resolve_algo_jvp, workspace_bytes_jvp
 from .clouds import (raster_clouds, raster_clouds_, raster_clouds_ad, raster_pullback_clouds_, resolve_algo_clouds,
                      workspace_bytes_clouds)
+from .smooth import (raster_pullback_smooth_, raster_smooth, raster_smooth_, raster_smooth_ad, resolve_algo_smooth,
+                     workspace_bytes_smooth)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -34,4 +36,6 @@ __all__ = [
     "raster_jvp", "raster_jvp_", "resolve_algo_jvp", "workspace_bytes_jvp",
     "raster_clouds", "raster_clouds_", "raster_pullback_clouds_", "raster_clouds_ad", "resolve_algo_clouds",
     "workspace_bytes_clouds",
+    "raster_smooth", "raster_smooth_", "raster_pullback_smooth_", "raster_smooth_ad", "resolve_algo_smooth",
+    "workspace_bytes_smooth",
 ]

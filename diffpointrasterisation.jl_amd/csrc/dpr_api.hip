@@ -18,6 +18,7 @@
 #include "dpr_kernels_jvp.h"
 #include "dpr_kernels_sample.h"
 #include "dpr_ordered.h"
+#include "dpr_smooth.h"
 #include "dpr_tiled.h"
 
 namespace dpr {
@@ -1530,6 +1531,157 @@ static size_t workspace_clouds_impl(int op, int algo, unsigned flags, int n_in, 
     return clouds_workspace_bytes(sizeof(T), op, algo, n_in, n_out, grid, P, B);
 }
 
+// ---------------------------------------------------------------- smooth splat
+// dpr_raster_smooth_ex_* / dpr_raster_pullback_smooth_ex_* (include/dpr.h, "SMOOTH SPLAT"; kernels: dpr_smooth.hip).
+// (2,2), (3,3), (3,2) only.  DPR_ALGO_ATOMIC: forward and pullback; DPR_ALGO_TILED: forward.
+// (before check_common: the grid of a pair without kernels is not looked at)
+static int check_smooth_dims(int n_in, int n_out) {
+    if (!smooth_dims_supported(n_in, n_out))
+        return fail(DPR_ERR_UNSUPPORTED_DIMS,
+                    "unsupported (n_in, n_out) = (%d, %d); the smooth splat supports (2,2), (3,3), (3,2)", n_in, n_out);
+    return DPR_OK;
+}
+static int check_smooth(int op, unsigned flags) {
+    if (op == DPR_OP_RESIDUAL_PULLBACK)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth splat has no residual pullback");
+    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
+        return fail(DPR_ERR_INVALID_ARG, "smooth splat: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
+    if (flags & 3u)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "the smooth splat keeps / reuses no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
+    return DPR_OK;
+}
+
+// AUTO (dpr_resolve_algo_smooth), from the shape alone (profiles/smooth_probe.txt, fp32, uniform clouds in either
+// order, 1 and 16 poses).  The pullback is DPR_ALGO_ATOMIC.  The forward is DPR_ALGO_TILED from a point count on,
+// where the tile ids fit the sort key, and DPR_ALGO_ATOMIC below it: the tiled path pays a sort and four launches
+// per pose (0.07-0.1 ms), the atomic one 3^N atomics per point.
+//  - 3-D grids, from 1e5 points: 1e5 -> 128^3 0.113 against 0.145 ms (16 poses 1.24 / 1.70), -> 256^3 0.149 / 0.148
+//    (16 poses 1.98 / 1.84: the one row where the rule loses, 1.08x); 3e4 -> 128^3 0.091 against 0.071 ATOMIC;
+//    1e7 -> 256^3 0.64 against 9.9 ms.
+//  - 2-D grids, from 5e5 points (9 atomics per point, not 27): 3e5 -> 512^2 0.173 against 0.148 ms ATOMIC (16 poses
+//    2.21 / 1.82), 1e6 0.229 against 0.412 (3.14 / 5.98).  Between 3e5 and 1e6 nothing was measured.
+constexpr int64_t kSmoothTiledMinPoints3D = 100000;
+constexpr int64_t kSmoothTiledMinPoints2D = 500000;
+static int resolve_algo_smooth(int algo, int op, int n_out, const int64_t* grid, int64_t P) {
+    if (algo != DPR_ALGO_AUTO) return algo;
+    const int64_t min_points = n_out == 3 ? kSmoothTiledMinPoints3D : kSmoothTiledMinPoints2D;
+    if (op == DPR_OP_RASTER && P >= min_points && smooth_tile_count(n_out, grid, P) != 0) return DPR_ALGO_TILED;
+    return DPR_ALGO_ATOMIC;
+}
+
+// bytes of workspace, or (size_t)-1 (message recorded) when the algorithm cannot run the call
+static size_t smooth_workspace_bytes(int op, int algo, int n_out, const int64_t* grid, int64_t P) {
+    if (algo == DPR_ALGO_ATOMIC) return 0;  // (the pullback's per-pose partials leave their block as atomics)
+    if (algo != DPR_ALGO_TILED) {
+        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth splat runs on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d",
+             algo);
+        return (size_t)-1;
+    }
+    if (op != DPR_OP_RASTER) {
+        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth pullback runs on DPR_ALGO_ATOMIC only");
+        return (size_t)-1;
+    }
+    const size_t n = smooth_tiled_workspace_bytes(n_out, grid, P);
+    if (n == (size_t)-1)
+        fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth DPR_ALGO_TILED: too many tiles for a 32-bit key or P > 2^32 - 2");
+    return n;
+}
+
+template <class F> static int with_smooth_dims(int n_in, int n_out, F&& f) {
+    if (n_in == 2 && n_out == 2) return f(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
+    if (n_in == 3 && n_out == 3) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
+    if (n_in == 3 && n_out == 2) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{});
+    return fail(DPR_ERR_UNSUPPORTED_DIMS, "smooth splat: unsupported (n_in, n_out) = (%d, %d)", n_in, n_out);
+}
+
+template <typename T>
+static int raster_smooth_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                              int64_t P, int64_t B, T* out, const T* points, const T* rot, const T* trans,
+                              const T* bg, const T* ow, const T* pw, void* ws, size_t ws_bytes) {
+    int64_t G = 0;
+    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
+    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
+    if (int rc = check_smooth(DPR_OP_RASTER, flags)) return rc;
+    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    algo = resolve_algo_smooth(algo, DPR_OP_RASTER, n_out, grid, P);
+    const size_t need = smooth_workspace_bytes(DPR_OP_RASTER, algo, n_out, grid, P);
+    if (need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
+    if (B == 0) return DPR_OK;
+    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
+    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
+        return fail(DPR_ERR_WORKSPACE, "smooth splat (algorithm %d) needs %zu workspace bytes, got %zu", algo, need,
+                    ws ? ws_bytes : (size_t)0);
+    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    fill_background(st, out, G, B, bg);
+    stage_mark(st);
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        const int rc = algo == DPR_ALGO_TILED
+                           ? smooth_fwd_tiled<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, ow, pw, ws, ws_bytes)
+                           : smooth_fwd_atomic<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, ow, pw);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+template <typename T>
+static int pullback_smooth_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                int64_t P, int64_t B, const T* g, const T* points, const T* rot, const T* trans,
+                                const T* ow, const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw,
+                                void* ws, size_t ws_bytes) {
+    (void)ws_bytes;
+    int64_t G = 0;
+    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
+    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
+    if (int rc = check_smooth(DPR_OP_PULLBACK, flags)) return rc;
+    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
+    algo = resolve_algo_smooth(algo, DPR_OP_PULLBACK, n_out, grid, P);
+    if (smooth_workspace_bytes(DPR_OP_PULLBACK, algo, n_out, grid, P) == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
+    if (B == 0) return DPR_OK;  // (every output is empty)
+    if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
+    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+    if (!d_rot || !d_trans || !d_bg || !d_ow) return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
+    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
+        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * n_out * n_in), st));
+    DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * n_out), st));
+    DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
+    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
+    grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
+    stage_mark(st);
+    int64_t slices = 1;
+    const int poses_per_slice = pose_slices(P, B, &slices);  // (the linear atomic pullback's: SUMMATION ORDER, note 1)
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        const int rc = smooth_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
+            st, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice,
+            slices);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+template <typename T>
+static size_t workspace_smooth_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                    int64_t P, int64_t B) {
+    int64_t G = 0;
+    if (check_smooth_dims(n_in, n_out)) return (size_t)-1;
+    if (check_common(n_in, n_out, grid, P, B, &G)) return (size_t)-1;
+    if (check_smooth(op, flags)) return (size_t)-1;
+    algo = resolve_algo_smooth(algo, op, n_out, grid, P);
+    return smooth_workspace_bytes(op, algo, n_out, grid, P);
+}
+
 }  // namespace dpr
 
 extern "C" {
@@ -1813,5 +1965,41 @@ int dpr_resolve_algo_clouds(int op, int n_in, int n_out, const int64_t* grid, in
 DPR_DEFINE_CLOUDS(f32, float)
 DPR_DEFINE_CLOUDS(f64, double)
 #undef DPR_DEFINE_CLOUDS
+
+int dpr_resolve_algo_smooth(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
+    int64_t G = 0;
+    if (int rc = dpr::check_smooth_dims(n_in, n_out)) return rc;
+    if (int rc = dpr::check_common(n_in, n_out, grid, P, B, &G)) return rc;
+    if (int rc = dpr::check_smooth(op, 0u)) return rc;
+    return dpr::resolve_algo_smooth(DPR_ALGO_AUTO, op, n_out, grid, P);
+}
+
+#define DPR_DEFINE_SMOOTH(SUF, T)                                                                              \
+    size_t dpr_workspace_bytes_smooth_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,          \
+                                               const int64_t* grid, int64_t P, int64_t B) {                    \
+        return dpr::workspace_smooth_impl<T>(op, algo, flags, n_in, n_out, grid, P, B);                        \
+    }                                                                                                          \
+    int dpr_raster_smooth_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,                \
+                                   const int64_t* grid, int64_t P, int64_t B, T* out, const T* points,         \
+                                   const T* rotation, const T* translation, const T* background,               \
+                                   const T* out_weight, const T* point_weight, void* workspace,                \
+                                   size_t workspace_bytes) {                                                   \
+        return dpr::raster_smooth_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, out, points, rotation, \
+                                          translation, background, out_weight, point_weight, workspace,        \
+                                          workspace_bytes);                                                    \
+    }                                                                                                          \
+    int dpr_raster_pullback_smooth_ex_##SUF(                                                                   \
+        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, \
+        const T* ds_dout, const T* points, const T* rotation, const T* translation, const T* out_weight,       \
+        const T* point_weight, T* ds_dpoints, T* ds_drotation, T* ds_dtranslation, T* ds_dbackground,          \
+        T* ds_dout_weight, T* ds_dpoint_weight, void* workspace, size_t workspace_bytes) {                     \
+        return dpr::pullback_smooth_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, ds_dout, points,     \
+                                            rotation, translation, out_weight, point_weight, ds_dpoints,       \
+                                            ds_drotation, ds_dtranslation, ds_dbackground, ds_dout_weight,     \
+                                            ds_dpoint_weight, workspace, workspace_bytes);                     \
+    }
+DPR_DEFINE_SMOOTH(f32, float)
+DPR_DEFINE_SMOOTH(f64, double)
+#undef DPR_DEFINE_SMOOTH
 
 }  // extern "C"

@@ -1,0 +1,68 @@
+// The smooth splat (include/dpr.h, "SMOOTH SPLAT"): quadratic B-spline weights on 3^N cells per point.
+// Index arithmetic shared by the host plan and the kernels of dpr_smooth.hip, and the entry points dpr_api.hip calls.
+#pragma once
+#include "dpr_tiled.h"
+
+namespace dpr {
+
+// ---- tiles of DPR_ALGO_TILED ----------------------------------------------------------------------------------
+// A workgroup owns a tile and keeps it, plus one halo cell on both sides of every axis, as f64 cells in LDS:
+// 3-D 16 x 8 x 8 (18 x 10 x 10 cells, 14 400 bytes), 2-D 64 x 16 (66 x 18 cells, 9 504 bytes) -- ten workgroups and
+// more per CU's 160 KB.
+template <int NO> struct SmoothTileShape;
+template <> struct SmoothTileShape<2> {
+    static constexpr int e[2] = {64, 16};
+};
+template <> struct SmoothTileShape<3> {
+    static constexpr int e[3] = {16, 8, 8};
+};
+template <int NO> constexpr int smooth_lds_cells() {
+    int c = 1;
+    for (int d = 0; d < NO; ++d) c *= SmoothTileShape<NO>::e[d] + 2;
+    return c;
+}
+
+template <int NO> struct SmoothTiles {
+    int nt[NO];     // tiles per axis
+    int64_t tiles;  // their product
+};
+template <int NO> SmoothTiles<NO> smooth_tiles(const int64_t* grid) {
+    SmoothTiles<NO> t;
+    t.tiles = 1;
+    for (int d = 0; d < NO; ++d) {
+        const int e = SmoothTileShape<NO>::e[d];
+        t.nt[d] = (int)((grid[d] + e - 1) / e);
+        t.tiles *= t.nt[d];
+    }
+    return t;
+}
+
+constexpr uint32_t kSmoothNoKey = 0xffffffffu;  // a rejected point; sorts behind every tile
+
+// (2,2), (3,3), (3,2): the pairs the smooth splat is compiled for
+constexpr bool smooth_dims_supported(int n_in, int n_out) {
+    return (n_in == 2 && n_out == 2) || (n_in == 3 && n_out == 3) || (n_in == 3 && n_out == 2);
+}
+
+// tiles of the grid, or 0 where DPR_ALGO_TILED cannot run the call: tile ids 0 .. tiles - 1 must stay below the
+// all-ones key and the index of a point must fit 32 bits (P <= 2^32 - 2)
+int64_t smooth_tile_count(int n_out, const int64_t* grid, int64_t P);
+// bytes of workspace of the tiled forward (0 for P = 0); independent of B
+size_t smooth_tiled_workspace_bytes(int n_out, const int64_t* grid, int64_t P);
+
+// The point kernels.  `out` holds the background already; the pullback's per-pose sums are zeroed and
+// ds_dbackground is done by the caller (dpr_api.hip).
+template <typename T, int NI, int NO>
+int smooth_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out, const T* points,
+                      const T* rot, const T* trans, const T* ow, const T* pw);
+template <typename T, int NI, int NO>
+int smooth_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out, const T* points,
+                     const T* rot, const T* trans, const T* ow, const T* pw, void* ws, size_t ws_bytes);
+// poses_per_slice / slices: the pose slicing of the linear atomic pullback (pose_slices of dpr_api.hip); with
+// more than one slice ds_dpoints / ds_dpoint_weight are zeroed here and added with atomics
+template <typename T, int NI, int NO>
+int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* g,
+                      const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts, T* d_rot,
+                      T* d_trans, T* d_ow, T* d_pw, int poses_per_slice, int64_t slices);
+
+}  // namespace dpr

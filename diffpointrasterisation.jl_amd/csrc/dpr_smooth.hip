@@ -1,0 +1,524 @@
+// The smooth splat: quadratic B-spline (TSC) weights on 3^N cells per point (include/dpr.h, "SMOOTH SPLAT").
+//
+//   coord_d = ((R p + t)_d + 1) * n_d / 2,  j0_d = floor(coord_d),  u_d = coord_d - (j0_d + 1/2)  in [-1/2, 1/2)
+//   w_d(-1) = (1/2 - u)^2 / 2    w_d(0) = 3/4 - u^2    w_d(+1) = (1/2 + u)^2 / 2         (sum: 1)
+//   out[j0 + s] += out_weight * point_weight * prod_d w_d(s_d),  s in {-1, 0, +1}^N, cells outside the grid dropped
+//
+//   DPR_ALGO_ATOMIC forward   k_smooth_fwd_atomic: one thread per point, pose loop inside, 3^N global atomics
+//   DPR_ALGO_ATOMIC pullback  k_smooth_bwd: k_bwd_gather's shape (point gradients in registers across the poses of a
+//                             slice, per-pose sums wave -> block -> one atomic per block); the 3^N gathers are issued
+//                             one 3^(N-1) slab at a time and contracted axis by axis (the weights are separable)
+//   DPR_ALGO_TILED forward    per pose: k_smooth_keys (tile of the clamped centre cell, all ones for a rejected
+//                             point) -> stable radix sort of (key, index) -> k_smooth_ranges (start table over the
+//                             tiles) -> k_smooth_tile: one workgroup per tile adds its run of points into an LDS tile
+//                             + halo of f64 cells (ds_add_f64) and adds every non-zero cell inside the grid onto
+//                             `out` with one global atomic in T, rows of axis 0 on consecutive lanes.  No global
+//                             atomic per point; a cell receives at most 3^N tile partials.
+#include <hip/hip_runtime.h>
+
+#include "../../include/dpr.h"
+#include "dpr_ordered.h"
+#include "dpr_ordered_index.h"
+#include "dpr_smooth.h"
+
+namespace dpr {
+
+constexpr int kSmBlock = 256;
+
+template <typename T> __device__ __forceinline__ T floor_t(T x);
+template <> __device__ __forceinline__ float floor_t<float>(float x) { return floorf(x); }
+template <> __device__ __forceinline__ double floor_t<double>(double x) { return floor(x); }
+
+// Centre cell j0 (0-based, -1 .. n_d) and offset u from its centre.  false: the point is rejected for the pose
+// (some coord outside [-1, n_d + 1); the test runs in floating point before the conversion to int and rejects
+// NaN / Inf).  The projection has ref_and_deltas' operation order.
+template <typename T, int NI, int NO>
+__device__ __forceinline__ bool smooth_cell(const T (&p)[NI], const Pose<T, NI, NO>& ps, const GridDesc<NO>& gd,
+                                            int (&j0)[NO], T (&u)[NO]) {
+    bool ok = true;
+#pragma unroll
+    for (int d = 0; d < NO; ++d) {
+        T proj = ps.R[d] * p[0];
+#pragma unroll
+        for (int j = 1; j < NI; ++j) proj = proj + ps.R[d + j * NO] * p[j];
+        const T origin = T(-1) - ps.t[d];
+        const T scale = T(gd.n[d]) / T(2);
+        const T coord = (proj - origin) * scale;
+        ok = ok && (coord >= T(-1)) && (coord < T(gd.n[d] + 1));
+        const T f = floor_t<T>(coord);
+        j0[d] = ok ? (int)f : 0;
+        u[d] = coord - (f + T(0.5));
+    }
+    return ok;
+}
+
+// the three weights of an axis and their derivatives in coord
+template <typename T> __device__ __forceinline__ void spline_weights(T u, T (&w)[3]) {
+    const T a = T(0.5) - u, b = T(0.5) + u;
+    w[0] = a * a * T(0.5);
+    w[1] = T(0.75) - u * u;
+    w[2] = b * b * T(0.5);
+}
+template <typename T> __device__ __forceinline__ void spline_derivatives(T u, T (&dw)[3]) {
+    dw[0] = -(T(0.5) - u);
+    dw[1] = T(-2) * u;
+    dw[2] = T(0.5) + u;
+}
+
+// Per axis: the weights and, for the three cells j0 - 1 .. j0 + 1, whether the cell is in the grid and its
+// column-major offset term (0 for a dropped cell: the product would overflow an int next to 2^31 cells).
+template <typename T, int NO> struct SmoothAxes {
+    T w[NO][3];
+    int off[NO][3];
+    bool in[NO][3];
+};
+template <typename T, int NO>
+__device__ __forceinline__ SmoothAxes<T, NO> smooth_axes(const int (&j0)[NO], const T (&u)[NO],
+                                                         const GridDesc<NO>& gd) {
+    SmoothAxes<T, NO> ax;
+    int stride = 1;
+#pragma unroll
+    for (int d = 0; d < NO; ++d) {
+        spline_weights<T>(u[d], ax.w[d]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int c = j0[d] + k - 1;
+            ax.in[d][k] = c >= 0 && c < gd.n[d];
+            ax.off[d][k] = ax.in[d][k] ? c * stride : 0;
+        }
+        stride *= gd.n[d];
+    }
+    return ax;
+}
+
+// ---------------------------------------------------------------- DPR_ALGO_ATOMIC forward
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_fwd_atomic(GridDesc<NO> gd, int64_t P, int64_t B,
+                                                                T* __restrict__ out, const T* __restrict__ points,
+                                                                const T* __restrict__ rot,
+                                                                const T* __restrict__ trans,
+                                                                const T* __restrict__ ow, const T* __restrict__ pw) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (p >= P) return;
+    T pt[NI];
+    load_point<T, NI>(points, p, pt);
+    const T pwi = pw ? pw[p] : T(1);
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+        const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b);
+        int j0[NO];
+        T u[NO];
+        if (!smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) continue;
+        const T w = ps.ow * pwi;
+        const SmoothAxes<T, NO> ax = smooth_axes<T, NO>(j0, u, gd);
+        T* o = out + b * gd.G;
+#pragma unroll
+        for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+            const bool in2 = NO == 3 ? ax.in[NO - 1][k2] : true;
+            const int off2 = NO == 3 ? ax.off[NO - 1][k2] : 0;
+            const T w2 = NO == 3 ? ax.w[NO - 1][k2] * w : w;
+#pragma unroll
+            for (int k1 = 0; k1 < 3; ++k1) {
+                const T w12 = ax.w[1][k1] * w2;
+#pragma unroll
+                for (int k0 = 0; k0 < 3; ++k0)
+                    if (in2 && ax.in[1][k1] && ax.in[0][k0])
+                        atomic_add<T>(o + (off2 + ax.off[1][k1] + ax.off[0][k0]), ax.w[0][k0] * w12);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- DPR_ALGO_ATOMIC pullback
+// The sums of one (point, pose) without out_weight * point_weight:
+//   W = sum_s g[j0 + s] prod_d w_d(s_d),   dcoord[k] = sum_s g[j0 + s] w'_k(s_k) prod_{d != k} w_d(s_d).
+// The nine gathers of a plane (axes 0 and 1) are requested before the first is used; a dropped cell fetches cell 0
+// of the pose and is replaced by 0 (a select, not a multiplication).  3-D: plane after plane, so that nine values
+// are live at a time, not 27.
+template <typename T, int NO, typename Fetch>
+__device__ __forceinline__ void smooth_point_backward(const int (&j0)[NO], const T (&u)[NO], const GridDesc<NO>& gd,
+                                                      Fetch fetch, T (&dcoord)[NO], T& W) {
+    const SmoothAxes<T, NO> ax = smooth_axes<T, NO>(j0, u, gd);
+    T dw[NO][3];
+#pragma unroll
+    for (int d = 0; d < NO; ++d) spline_derivatives<T>(u[d], dw[d]);
+    auto plane = [&](int base, bool vb, T& S, T& S0, T& S1) {
+        T gq[3][3];
+#pragma unroll
+        for (int k1 = 0; k1 < 3; ++k1)
+#pragma unroll
+            for (int k0 = 0; k0 < 3; ++k0) {
+                const bool v = vb && ax.in[1][k1] && ax.in[0][k0];
+                const T x = fetch(v ? base + ax.off[1][k1] + ax.off[0][k0] : 0);
+                gq[k1][k0] = v ? x : T(0);
+            }
+        S = T(0);
+        S0 = T(0);
+        S1 = T(0);
+#pragma unroll
+        for (int k1 = 0; k1 < 3; ++k1) {
+            const T a = (gq[k1][0] * ax.w[0][0] + gq[k1][1] * ax.w[0][1]) + gq[k1][2] * ax.w[0][2];
+            const T da = (gq[k1][0] * dw[0][0] + gq[k1][1] * dw[0][1]) + gq[k1][2] * dw[0][2];
+            S += a * ax.w[1][k1];
+            S0 += da * ax.w[1][k1];
+            S1 += a * dw[1][k1];
+        }
+    };
+    if constexpr (NO == 2) {
+        plane(0, true, W, dcoord[0], dcoord[1]);
+    } else {
+        W = T(0);
+#pragma unroll
+        for (int d = 0; d < NO; ++d) dcoord[d] = T(0);
+#pragma unroll
+        for (int k2 = 0; k2 < 3; ++k2) {
+            T S, S0, S1;
+            plane(ax.off[2][k2], ax.in[2][k2], S, S0, S1);
+            W += S * ax.w[2][k2];
+            dcoord[0] += S0 * ax.w[2][k2];
+            dcoord[1] += S1 * ax.w[2][k2];
+            dcoord[2] += S * dw[2][k2];
+        }
+    }
+}
+
+// Pre-zeroed: ds_drotation, ds_dtranslation, ds_dout_weight; with accumulate_points also ds_dpoints and
+// ds_dpoint_weight (the poses are cut into slices on grid.y, every slice adds its share with atomics).
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_bwd(
+    GridDesc<NO> gd, int64_t P, int64_t B, const T* __restrict__ g, const T* __restrict__ points,
+    const T* __restrict__ rot, const T* __restrict__ trans, const T* __restrict__ ow, const T* __restrict__ pw,
+    T* __restrict__ ds_dpoints, T* __restrict__ ds_drotation, T* __restrict__ ds_dtranslation,
+    T* __restrict__ ds_dout_weight, T* __restrict__ ds_dpoint_weight, int poses_per_slice, int accumulate_points) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    constexpr int NV = NO * NI + NO + 1;  // dR | dt | d out_weight
+    constexpr int NW = kSmBlock / kWave;
+    __shared__ T red[NW][NV];
+
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    const bool live = p < P;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    T pt[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) pt[j] = T(0);
+    if (live) load_point<T, NI>(points, p, pt);
+    const T pwi = (live && pw) ? pw[p] : T(1);
+
+    T acc_pt[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) acc_pt[j] = T(0);
+    T acc_pw = T(0);
+
+    const int64_t b_lo = (int64_t)blockIdx.y * poses_per_slice;
+    const int64_t b_hi = (b_lo + poses_per_slice < B) ? b_lo + poses_per_slice : B;
+    for (int64_t b = b_lo; b < b_hi; ++b) {
+        const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b);
+        T vals[NV];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) vals[k] = T(0);
+        int j0[NO];
+        T u[NO];
+        if (live && smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) {
+            const T* gb = g + b * gd.G;
+            T dcoord[NO], W;
+            smooth_point_backward<T, NO>(j0, u, gd, [&](int off) { return gb[off]; }, dcoord, W);
+            const T opw = ps.ow * pwi;
+            T scaled[NO];
+#pragma unroll
+            for (int n = 0; n < NO; ++n) scaled[n] = (dcoord[n] * opw) * (T(gd.n[n]) / T(2));
+#pragma unroll
+            for (int n = 0; n < NO; ++n) {
+#pragma unroll
+                for (int j = 0; j < NI; ++j) vals[n + j * NO] = scaled[n] * pt[j];
+                vals[NO * NI + n] = scaled[n];
+            }
+            vals[NO * NI + NO] = W * pwi;
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {  // rotation' * scaled
+                T v = ps.R[0 + j * NO] * scaled[0];
+#pragma unroll
+                for (int n = 1; n < NO; ++n) v = v + ps.R[n + j * NO] * scaled[n];
+                acc_pt[j] += v;
+            }
+            acc_pw += W * ps.ow;
+        }
+        // per-pose sums: wave -> block -> one atomic per scalar per block
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const T s = wave_sum<T>(vals[k]);
+            if (lane == 0) red[wave][k] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < NV) {
+            T s = red[0][threadIdx.x];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) s += red[w][threadIdx.x];
+            const int k = threadIdx.x;
+            if (s != T(0)) {
+                if (k < NO * NI)
+                    atomic_add<T>(ds_drotation + b * (NO * NI) + k, s);
+                else if (k < NO * NI + NO)
+                    atomic_add<T>(ds_dtranslation + b * NO + (k - NO * NI), s);
+                else
+                    atomic_add<T>(ds_dout_weight + b, s);
+            }
+        }
+        __syncthreads();
+    }
+    if (live) {
+        if (accumulate_points) {
+#pragma unroll
+            for (int j = 0; j < NI; ++j) atomic_add<T>(ds_dpoints + p * NI + j, acc_pt[j]);
+            if (ds_dpoint_weight) atomic_add<T>(ds_dpoint_weight + p, acc_pw);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NI; ++j) ds_dpoints[p * NI + j] = acc_pt[j];
+            if (ds_dpoint_weight) ds_dpoint_weight[p] = acc_pw;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- DPR_ALGO_TILED forward
+// key = id of the tile (column-major over the tiles, axis 0 fastest) that holds cell j0 clamped into the grid
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_keys(GridDesc<NO> gd, SmoothTiles<NO> tl, int64_t P, int64_t b,
+                                                          const T* __restrict__ points, const T* __restrict__ rot,
+                                                          const T* __restrict__ trans, uint32_t* __restrict__ keys,
+                                                          uint32_t* __restrict__ idx) {
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (p >= P) return;
+    T pt[NI];
+    load_point<T, NI>(points, p, pt);
+    const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, nullptr, b);
+    int j0[NO];
+    T u[NO];
+    uint32_t key = kSmoothNoKey;
+    if (smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) {
+        uint32_t stride = 1;
+        key = 0;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            const int c = j0[d] < 0 ? 0 : (j0[d] >= gd.n[d] ? gd.n[d] - 1 : j0[d]);
+            key += (uint32_t)(c / SmoothTileShape<NO>::e[d]) * stride;
+            stride *= (uint32_t)tl.nt[d];
+        }
+    }
+    keys[p] = key;
+    idx[p] = (uint32_t)p;
+}
+
+// start[k] = first position of the sorted keys with key >= k, for k = 0 .. tiles (start[tiles]: accepted points)
+__global__ __launch_bounds__(kSmBlock) void k_smooth_ranges(const uint32_t* __restrict__ keys, uint32_t count,
+                                                            uint64_t entries, int bits,
+                                                            uint32_t* __restrict__ start) {
+    const uint64_t k = (uint64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (k >= entries) return;
+    start[k] = ord_lower_bound(keys, count, (uint32_t)k, bits);
+}
+
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_tile(GridDesc<NO> gd, SmoothTiles<NO> tl, int64_t P, int64_t b,
+                                                          T* __restrict__ out, const T* __restrict__ points,
+                                                          const T* __restrict__ rot, const T* __restrict__ trans,
+                                                          const T* __restrict__ ow, const T* __restrict__ pw,
+                                                          const uint32_t* __restrict__ start,
+                                                          const uint32_t* __restrict__ idx) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    constexpr int NC = smooth_lds_cells<NO>();
+    __shared__ double cells[NC];
+    // the tile's run of the sorted points, clamped: a damaged table can shorten a walk, never leave idx[0 .. P)
+    uint32_t begin, end;
+    ord_cell_range(start, blockIdx.x, (uint32_t)P, begin, end);
+    if (begin >= end) return;  // (uniform: an empty tile adds nothing)
+    int org[NO];               // first cell of the tile
+    {
+        uint32_t t = blockIdx.x;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            org[d] = (int)(t % (uint32_t)tl.nt[d]) * SmoothTileShape<NO>::e[d];
+            t /= (uint32_t)tl.nt[d];
+        }
+    }
+    for (int i = threadIdx.x; i < NC; i += kSmBlock) cells[i] = 0.0;
+    __syncthreads();
+
+    const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b);
+    for (uint32_t i = begin + threadIdx.x; i < end; i += kSmBlock) {
+        const uint32_t p = idx[i];
+        if ((int64_t)p >= P) continue;  // (never for an index k_smooth_keys wrote)
+        T pt[NI];
+        load_point<T, NI>(points, (int64_t)p, pt);
+        int j0[NO];
+        T u[NO];
+        if (!smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) continue;
+        const T w = ps.ow * (pw ? pw[p] : T(1));
+        // LDS cell l = (cell - org) + 1 per axis; only cells of the grid that lie on the tile + halo are added
+        T wt[NO][3];
+        int loff[NO][3];
+        bool in[NO][3];
+        int lstride = 1;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            spline_weights<T>(u[d], wt[d]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int c = j0[d] + k - 1, l = c - org[d] + 1;
+                in[d][k] = c >= 0 && c < gd.n[d] && l >= 0 && l < SmoothTileShape<NO>::e[d] + 2;
+                loff[d][k] = in[d][k] ? l * lstride : 0;
+            }
+            lstride *= SmoothTileShape<NO>::e[d] + 2;
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+            const bool in2 = NO == 3 ? in[NO - 1][k2] : true;
+            const int off2 = NO == 3 ? loff[NO - 1][k2] : 0;
+            const T w2 = NO == 3 ? wt[NO - 1][k2] * w : w;
+#pragma unroll
+            for (int k1 = 0; k1 < 3; ++k1) {
+                const T w12 = wt[1][k1] * w2;
+#pragma unroll
+                for (int k0 = 0; k0 < 3; ++k0)
+                    if (in2 && in[1][k1] && in[0][k0])
+                        atomicAdd(&cells[off2 + loff[1][k1] + loff[0][k0]], (double)(wt[0][k0] * w12));
+            }
+        }
+    }
+    __syncthreads();
+
+    // flush: consecutive threads walk axis 0 of the tile + halo, so a wave's atomics cover rows of `out`
+    T* o = out + b * gd.G;
+    for (int i = threadIdx.x; i < NC; i += kSmBlock) {
+        const double v = cells[i];
+        int rest = i, off = 0, stride = 1;
+        bool in_grid = true;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            const int ext = SmoothTileShape<NO>::e[d] + 2;
+            const int c = org[d] + (rest % ext) - 1;
+            rest /= ext;
+            in_grid = in_grid && c >= 0 && c < gd.n[d];
+            off += in_grid ? c * stride : 0;
+            stride *= gd.n[d];
+        }
+        if (in_grid && v != 0.0) atomic_add<T>(o + off, (T)v);
+    }
+}
+
+// ---------------------------------------------------------------- host
+int64_t smooth_tile_count(int n_out, const int64_t* grid, int64_t P) {
+    if (P > (int64_t)0xfffffffeLL) return 0;
+    const int64_t tiles = n_out == 2 ? smooth_tiles<2>(grid).tiles : n_out == 3 ? smooth_tiles<3>(grid).tiles : 0;
+    return tiles < (int64_t)0x7fffffffLL ? tiles : 0;  // (also the largest launch: one workgroup per tile)
+}
+
+struct SmoothPlan {
+    size_t off_keys_in, off_keys_out, off_idx_in, off_idx_out, off_temp, temp_bytes, off_start, total;
+};
+static SmoothPlan smooth_plan(int64_t tiles, int64_t P) {
+    SmoothPlan pl{};
+    if (P <= 0) return pl;
+    size_t o = 0;
+    pl.off_keys_in = o;  o += align_up((size_t)P * 4);
+    pl.off_keys_out = o; o += align_up((size_t)P * 4);
+    pl.off_idx_in = o;   o += align_up((size_t)P * 4);
+    pl.off_idx_out = o;  o += align_up((size_t)P * 4);
+    pl.off_temp = o;
+    pl.temp_bytes = radix_pairs_temp_bytes(P);
+    o += align_up(pl.temp_bytes);
+    pl.off_start = o;    o += align_up((size_t)(tiles + 1) * 4);
+    pl.total = o;
+    return pl;
+}
+
+size_t smooth_tiled_workspace_bytes(int n_out, const int64_t* grid, int64_t P) {
+    const int64_t tiles = smooth_tile_count(n_out, grid, P);
+    if (tiles == 0) return (size_t)-1;
+    return smooth_plan(tiles, P).total;
+}
+
+template <typename T, int NI, int NO>
+int smooth_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out, const T* points,
+                      const T* rot, const T* trans, const T* ow, const T* pw) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    dim3 g((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)(B < 65535 ? B : 65535));
+    hipLaunchKernelGGL((k_smooth_fwd_atomic<T, NI, NO>), g, dim3(kSmBlock), 0, st, gd, P, B, out, points, rot, trans,
+                       ow, pw);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+template <typename T, int NI, int NO>
+int smooth_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out, const T* points,
+                     const T* rot, const T* trans, const T* ow, const T* pw, void* ws_, size_t ws_bytes) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const int64_t tiles = smooth_tile_count(NO, grid, P);
+    if (tiles == 0)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth DPR_ALGO_TILED: too many tiles for a 32-bit key or P > 2^32 - 2");
+    const SmoothPlan pl = smooth_plan(tiles, P);
+    if (!ws_ || ws_bytes < pl.total)
+        return fail(DPR_ERR_WORKSPACE, "smooth DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
+                    ws_ ? ws_bytes : (size_t)0);
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    const SmoothTiles<NO> tl = smooth_tiles<NO>(grid);
+    char* ws = (char*)ws_;
+    uint32_t* keys_in = (uint32_t*)(ws + pl.off_keys_in);
+    uint32_t* keys_out = (uint32_t*)(ws + pl.off_keys_out);
+    uint32_t* idx_in = (uint32_t*)(ws + pl.off_idx_in);
+    uint32_t* idx_out = (uint32_t*)(ws + pl.off_idx_out);
+    uint32_t* start = (uint32_t*)(ws + pl.off_start);
+    const int bits = ord_key_bits((uint64_t)tiles);
+    const dim3 blk(kSmBlock);
+    const dim3 pgrid((unsigned)((P + kSmBlock - 1) / kSmBlock));
+    const dim3 rgrid((unsigned)((tiles + 1 + kSmBlock - 1) / kSmBlock));
+    for (int64_t b = 0; b < B; ++b) {
+        hipLaunchKernelGGL((k_smooth_keys<T, NI, NO>), pgrid, blk, 0, st, gd, tl, P, b, points, rot, trans, keys_in,
+                           idx_in);
+        stage_mark(st);
+        DPR_HIP(radix_sort_pairs_u32(ws + pl.off_temp, pl.temp_bytes, keys_in, keys_out, idx_in, idx_out, (size_t)P,
+                                     0u, (unsigned)bits, st));
+        stage_mark(st);
+        hipLaunchKernelGGL(k_smooth_ranges, rgrid, blk, 0, st, (const uint32_t*)keys_out, (uint32_t)P,
+                           (uint64_t)(tiles + 1), bits, start);
+        stage_mark(st);
+        hipLaunchKernelGGL((k_smooth_tile<T, NI, NO>), dim3((unsigned)tiles), blk, 0, st, gd, tl, P, b, out, points,
+                           rot, trans, ow, pw, (const uint32_t*)start, (const uint32_t*)idx_out);
+        stage_mark(st);
+    }
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+template <typename T, int NI, int NO>
+int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* g,
+                      const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts, T* d_rot,
+                      T* d_trans, T* d_ow, T* d_pw, int poses_per_slice, int64_t slices) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    const int accumulate = slices > 1;
+    if (accumulate) {
+        DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
+        if (d_pw) DPR_HIP(hipMemsetAsync(d_pw, 0, sizeof(T) * (size_t)P, st));
+    }
+    dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)slices);
+    hipLaunchKernelGGL((k_smooth_bwd<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, g, points, rot, trans, ow, pw,
+                       d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice, accumulate);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+#define DPR_SMOOTH_INSTANTIATE(T, NI, NO)                                                                           \
+    template int smooth_fwd_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, T*, const T*, \
+                                              const T*, const T*, const T*, const T*);                             \
+    template int smooth_fwd_tiled<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, T*, const T*,  \
+                                             const T*, const T*, const T*, const T*, void*, size_t);               \
+    template int smooth_bwd_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, const T*,     \
+                                              const T*, const T*, const T*, const T*, const T*, T*, T*, T*, T*,    \
+                                              T*, int, int64_t);
+#define DPR_SMOOTH_INSTANTIATE_T(T) \
+    DPR_SMOOTH_INSTANTIATE(T, 2, 2) DPR_SMOOTH_INSTANTIATE(T, 3, 3) DPR_SMOOTH_INSTANTIATE(T, 3, 2)
+DPR_SMOOTH_INSTANTIATE_T(float)
+DPR_SMOOTH_INSTANTIATE_T(double)
+
+}  // namespace dpr

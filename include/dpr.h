@@ -251,6 +251,21 @@ extern "C" {
  *                        rounding level; fp64 / guard tripped:                                              (ds_dbackground: k_grid_sum's block atomics,
  *                        f64 LDS atomics, rounding level                                                    rounding level on grids of several blocks)
  *
+ *   smooth splat (dpr_raster_smooth_ex_* / dpr_raster_pullback_smooth_ex_*, see SMOOTH SPLAT below):
+ *   DPR_ALGO_ATOMIC      global float atomics in T, in arrival      one thread per point.  Pose loop       wave -> block -> one float atomic per block:
+ *                        order: rounding level                       inside the thread (B == 1, or          rounding level
+ *                                                                    P >= 524 033): one thread adds all
+ *                                                                    poses in index order, one plain
+ *                                                                    store: bit-reproducible.  Otherwise
+ *                                                                    the poses are sliced: rounding level
+ *                                                                    (note 1)
+ *   DPR_ALGO_TILED       f64 LDS atomics within a tile (arrival
+ *   (forward only)       order, 1e-16 relative), rounded to T once
+ *                        per (tile, cell); a cell receives <= 3^N
+ *                        such partials as float atomics in T onto
+ *                        the background: rounding level, not
+ *                        bit-reproducible
+ *
  * Note 1, pose slices.  A per-point kernel that would leave the device idle cuts the B poses into slices on
  * the second grid axis; every slice adds its share of ds_dpoints / ds_dpoint_weight with float atomics onto
  * zeroed buffers.  DPR_ALGO_ATOMIC and its channel form: fewer than 2048 blocks of 256 points (P <= 523 776)
@@ -778,6 +793,90 @@ int dpr_raster_pullback_clouds_ex_f32(void *stream, int algo, unsigned flags, in
                                       float *ds_dout_weight, float *ds_dpoint_weight, void *workspace,
                                       size_t workspace_bytes);
 int dpr_raster_pullback_clouds_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, const double *ds_dout,
+                                      const double *points, const double *rotation, const double *translation,
+                                      const double *out_weight, const double *point_weight, double *ds_dpoints,
+                                      double *ds_drotation, double *ds_dtranslation, double *ds_dbackground,
+                                      double *ds_dout_weight, double *ds_dpoint_weight, void *workspace,
+                                      size_t workspace_bytes);
+
+/* ---- SMOOTH SPLAT: quadratic B-spline weights on 3^N cells, C1 in the point position ---------------------------
+ * dpr_raster_* deposits a point with N-linear weights on 2^N cells: the image is continuous in the point position,
+ * its gradient only piecewise constant per cell.  These entry points deposit with the next kernel order up, the
+ * quadratic B-spline (particle-in-cell codes: TSC, triangular-shaped cloud): 3^N cells per point, weights that are
+ * C1 in the position and sum to 1, so the pullback is continuous across cell boundaries and agrees with finite
+ * differences everywhere.  Not in the reference.  Argument shapes, layouts, batching, defaults, background,
+ * out_weight and point_weight are those of dpr_raster_ex_* / dpr_raster_pullback_ex_*; only the kernel differs.
+ * For pose b and axis d of the output, with n_d cells (0-based cell j has its centre at j + 1/2):
+ *     coord_d  = ((R_b p + t_b)_d + 1) * n_d / 2
+ *     j0_d     = floor(coord_d)                 the cell whose centre is nearest
+ *     u_d      = coord_d - (j0_d + 1/2)         in [-1/2, 1/2)
+ *     w_d(-1)  = (1/2 - u_d)^2 / 2     w_d(0)  = 3/4 - u_d^2     w_d(+1)  = (1/2 + u_d)^2 / 2
+ *     w'_d(-1) = -(1/2 - u_d)          w'_d(0) = -2 u_d          w'_d(+1) = 1/2 + u_d
+ *     out[j0 + s, b] += out_weight[b] * point_weight[p] * prod_d w_d(s_d)        for s in {-1, 0, +1}^n_out
+ * A point is accepted for a pose when -1 <= coord_d < n_d + 1 on every axis (tested in floating point before any
+ * conversion to int; NaN / Inf are rejected).  Target cells outside the grid are dropped one by one, so mass is
+ * lost only within 1.5 cells of the border.  `out` starts from background[b].
+ * The pullback differentiates exactly this (no "cell held fixed": the function is C1).  Per point and pose,
+ *     dcoord_k = ow * pw * sum_s g[j0 + s] * w'_k(s_k) * prod_{d != k} w_d(s_d),     scaled = dcoord * n / 2,
+ *     ds_dtranslation += scaled,  ds_drotation += scaled * p^T,  ds_dpoints[p] += R^T * scaled,
+ *     W = sum_s g[j0 + s] * prod_d w_d(s_d),  ds_dout_weight += W * pw,  ds_dpoint_weight[p] += W * ow,
+ * and ds_dbackground[b] = sum(ds_dout[.., b]).  All six pullback outputs and `out` are overwritten.
+ * (n_in, n_out): (2,2), (3,3) and (3,2); every other pair DPR_ERR_UNSUPPORTED_DIMS.
+ * op: DPR_OP_RASTER or DPR_OP_PULLBACK (DPR_OP_RESIDUAL_PULLBACK: DPR_ERR_UNSUPPORTED_ALGO).  Flags:
+ * DPR_FLAG_NO_POINT_WEIGHT_GRAD keeps its meaning (ds_dpoint_weight may then be NULL), KEEP / REUSE are refused
+ * (DPR_ERR_UNSUPPORTED_ALGO), DPR_FLAG_COHERENT_POINTS and DPR_FLAG_MAX_POSE_GROUP are accepted and ignored.
+ * Algorithms (DPR_ALGO_CHUNKED, DPR_ALGO_ORDERED: DPR_ERR_UNSUPPORTED_ALGO).
+ *   DPR_ALGO_ATOMIC  forward: one thread per point, pose loop inside, 3^N global float atomics per accepted
+ *                    (point, pose).  Pullback: one thread per point, the poses looped inside the thread (sliced
+ *                    exactly as dpr_raster_pullback_ex_* on DPR_ALGO_ATOMIC slices them, SUMMATION ORDER note 1),
+ *                    the 3^N gathers issued one 3^(N-1) plane at a time, per-pose sums wave -> block -> one float
+ *                    atomic per block, ds_dbackground one float atomic per block of cells.  Workspace 0: the
+ *                    per-pose partials leave their block as atomics.
+ *   DPR_ALGO_TILED   forward only (pullback: DPR_ERR_UNSUPPORTED_ALGO).  Per pose, the workspace reused: a 32-bit
+ *                    key per point (the id of the tile that holds cell j0 clamped into the grid; all ones for a
+ *                    rejected point), a stable radix sort of (key, point index) on the bits the tile count needs,
+ *                    a start table over the tiles, then one workgroup per tile: it zeroes an LDS array of f64
+ *                    cells over the tile plus one halo cell on both sides of every axis (3-D tiles 16 x 8 x 8,
+ *                    2-D 64 x 16), adds every contribution of its run of points with f64 LDS atomics, and adds
+ *                    each non-zero cell that lies inside the grid onto the background-filled `out` with one
+ *                    global atomic in T, rows of axis 0 on consecutive lanes.  No global atomic per point; a
+ *                    cell receives at most 3^N tile partials.  Workspace: 16 P bytes + the sort's temporary
+ *                    storage + 4 (tiles + 1) bytes, every piece rounded up to 256, independent of B; 0 for P = 0.
+ *                    LIMITS (DPR_ERR_UNSUPPORTED_ALGO, (size_t)-1 from the query): P <= 2^32 - 2 and fewer than
+ *                    2^31 - 1 tiles.  COST: one workgroup owns a tile and adds its points 256 at a time, so the
+ *                    forward's time grows with the most populated tile; a cloud packed into a few tiles runs at
+ *                    the speed of those tiles (and many points on one cell serialise on its LDS atomic).
+ * AUTO (dpr_resolve_algo_smooth), from the shape alone, never from the points: the pullback DPR_ALGO_ATOMIC; the
+ * forward DPR_ALGO_TILED from 100 000 points on for a 3-D grid and from 500 000 for a 2-D grid (where the limits
+ * above hold), DPR_ALGO_ATOMIC below (profiles/smooth_probe.txt: the tiled path pays a sort and four launches per
+ * pose, the atomic one 3^N atomics per point).
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): as for the per-pose clouds --
+ * a bad op, negative P / B, a bad grid, a NULL required pointer, a misaligned data pointer DPR_ERR_INVALID_ARG; a
+ * workspace smaller than dpr_workspace_bytes_smooth_ex_* or not 256-byte aligned DPR_ERR_WORKSPACE.
+ * dpr_workspace_bytes_smooth_ex_* returns (size_t)-1 for every refused combination; dpr_resolve_algo_smooth a
+ * negative status. */
+int dpr_resolve_algo_smooth(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_smooth_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                         const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_smooth_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                         const int64_t *grid, int64_t P, int64_t B);
+int dpr_raster_smooth_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                             int64_t P, int64_t B, float *out, const float *points, const float *rotation,
+                             const float *translation, const float *background, const float *out_weight,
+                             const float *point_weight, void *workspace, size_t workspace_bytes);
+int dpr_raster_smooth_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                             int64_t P, int64_t B, double *out, const double *points, const double *rotation,
+                             const double *translation, const double *background, const double *out_weight,
+                             const double *point_weight, void *workspace, size_t workspace_bytes);
+int dpr_raster_pullback_smooth_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, const float *ds_dout,
+                                      const float *points, const float *rotation, const float *translation,
+                                      const float *out_weight, const float *point_weight, float *ds_dpoints,
+                                      float *ds_drotation, float *ds_dtranslation, float *ds_dbackground,
+                                      float *ds_dout_weight, float *ds_dpoint_weight, void *workspace,
+                                      size_t workspace_bytes);
+int dpr_raster_pullback_smooth_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
                                       const int64_t *grid, int64_t P, int64_t B, const double *ds_dout,
                                       const double *points, const double *rotation, const double *translation,
                                       const double *out_weight, const double *point_weight, double *ds_dpoints,
