@@ -1,4 +1,5 @@
-"""Launch-size cuts and offsets past 2^32 in the op families (channels, JVP, sampling, per-pose clouds, ORDERED).
+"""Launch-size cuts and offsets past 2^32 in the op families (channels, JVP, sampling, per-pose clouds, ORDERED, the
+smooth splat).
 
 Part A: plane / pose counts across the cuts at 65535 (grid.y), 2^20 (k_ord_reduce blocks) and 256 (the LDS staging
 round of k_ord_reduce), on tiny grids.  Part B: a whole plane, pose or cloud past element 2^32 (fp32, 17 GB arrays:
@@ -9,9 +10,11 @@ What guards what (csrc/dpr_api.hip unless another file is named):
 
   fill_background    `out + k0 * G`, `bg + k0`, cut inside a pose    test_channels_planes_across_the_launch_cut
                      cut between poses                               test_channels_poses_across_the_pose_stride,
-                                                                     test_clouds_poses_across_the_launch_cuts
+                                                                     test_clouds_poses_across_the_launch_cuts,
+                                                                     test_smooth_poses_across_the_launch_cuts
   grid_sum           `g + k0 * G`, `d_bg + k0`                       test_channels_planes_across_the_launch_cut,
-                                                                     test_clouds_poses_across_the_launch_cuts
+                                                                     test_clouds_poses_across_the_launch_cuts,
+                                                                     test_smooth_poses_across_the_launch_cuts
   k_fwd_atomic_ch    pose stride over gridDim.y = 65535              test_channels_poses_across_the_pose_stride
   raster_jvp_run     `q0` loop; k_jvp_fill: q -> bg_dot[k * B + b]   test_jvp_planes_across_the_launch_cut
   k_clouds_fwd_atomic, k_clouds_bwd_atomic: pose stride              test_clouds_poses_across_the_launch_cuts
@@ -21,6 +24,9 @@ What guards what (csrc/dpr_api.hip unless another file is named):
                                             test_ordered_poses_across_the_launch_cut_and_the_reduce_stride
   k_ord_reduce       second staging round, point chunks              test_ordered_reduce_second_round_of_point_chunks
                      second staging round, cell chunks (and loss)    test_ordered_reduce_second_round_of_cell_chunks
+  k_smooth_fwd_atomic (dpr_smooth.hip) pose stride over gridDim.y    test_smooth_poses_across_the_launch_cuts
+  k_smooth_bwd       (dpr_smooth.hip) `b_lo = blockIdx.y * poses_per_slice`, 1010 slices of 65 poses
+                                                                     test_smooth_poses_across_the_launch_cuts
   (b * C + c) * G    channels TILED and ATOMIC, (3, 3)               test_channels_planes_past_2_pow_32
   (b * K + k) * G    JVP TILED and ATOMIC, (3, 3)                    test_jvp_planes_past_2_pow_32
   b * G              image and ds_dimage, sampling ATOMIC / TILED    test_sample_image_past_2_pow_32
@@ -28,6 +34,8 @@ What guards what (csrc/dpr_api.hip unless another file is named):
   b * G              clouds TILED, ATOMIC and CHUNKED                test_clouds_out_past_2_pow_32
   b * P * NI         clouds ATOMIC and CHUNKED                       test_clouds_points_past_2_pow_32
   b * G              ORDERED forward and pullback                    test_ordered_pose_past_2_pow_32
+  b * G              smooth ATOMIC and TILED forward (k_smooth_fwd_atomic, k_smooth_tile), ATOMIC pullback
+                     (k_smooth_bwd), (3, 3)                          test_smooth_pose_past_2_pow_32
 
 Not reachable: the JVP's tangent offset k * P * NI stays below 2^32 at the 16-tangent limit even for P = 2^23,
 NI = 3 (15 * 2^23 * 3 = 1.4 * 2^28), so that second, small-grid call is left out; the (K, P, NI) tangents of
@@ -36,7 +44,9 @@ test_jvp_planes_past_2_pow_32 are read at their small offsets only.
 Part A selects planes / poses 0, 65534, 65535, 65536 and the last, and adds one device-side check of the whole
 tensor.  test_ordered_poses_across_the_launch_cut_and_the_reduce_stride gives only the five selected poses a
 sensitivity in its plain pullback (the serial oracle needs 6.6 s for all 70 000 poses); its residual pullback runs
-on a dense batch.  The seven *_past_2_pow_32 tests sit at the 2^32 floor: 17 GB arrays are their point.
+on a dense batch.  The eight *_past_2_pow_32 tests sit at the 2^32 floor: 17 GB arrays are their point.
+The smooth splat's TILED forward is left out of Part A: it launches four kernels per pose from the host (262 400
+launches at B = 65 600) and its per-pose loop has no cut; its `b * G` is in Part B.
 
 Mutation record (scratch builds of libdpr, one MI355X run each; every mutant keeps its accesses inside the buffers,
 a truncated offset wraps DOWN).  Each line: the mutant, the test it failed, the first assertion that fired.
@@ -65,6 +75,10 @@ a truncated offset wraps DOWN).  Each line: the mutant, the test it failed, the 
   32-bit b * G (ds_dout) in k_clouds_bwd_tile  clouds_out_past: chunked ds_dpoints[256]
   32-bit b * P * NI in k_clouds_bwd_atomic     clouds_points_past: atomic ds_dpoints[342]
   32-bit b * G (ds_dout) in k_ord_bwd          ordered_pose_past: ds_dpoints, 286 389 of 300 000 elements differ
+  k_smooth_fwd_atomic `b += gridDim.y` -> no stride   smooth_poses: out[.., 65535] (77 % off; poses 0 and 65534 pass before)
+  32-bit b * G (out) in k_smooth_fwd_atomic    smooth_pose_past: atomic: out[.., 256]
+  32-bit b * G (out) in k_smooth_tile          smooth_pose_past: tiled: out[.., 256] (ATOMIC passes before)
+  32-bit b * G (ds_dout) in k_smooth_bwd       smooth_pose_past: ds_dpoints (100 % off; both forwards pass before)
 Argued from the code, not run: the `out + k0 * G` / `d_bg + k0` halves of the two driver cuts, k_clouds_bwd_tile's
 `b0` and the strides of k_clouds_fwd_atomic / k_clouds_bwd_atomic (the idioms above, in kernels whose wrong pose
 would show in the same assertions), and every mutant that moves an access past its allocation."""
@@ -77,6 +91,7 @@ import torch
 
 import dpr_amd
 from tests import data as D
+from tests import smooth_reference as SR
 from tests.test_channels_gpu import tol as channels_tol
 from tests.test_clouds_gpu import check_against_oracle as clouds_check_against_oracle
 from tests.test_clouds_gpu import tol as clouds_tol
@@ -84,6 +99,7 @@ from tests.test_jvp_abi import jvp_reference, random_tangents
 from tests.test_jvp_gpu import tol as jvp_tol
 from tests.test_ordered_gpu import POSE_FIELDS, assert_same_bits, grid_to_dev, pose_args, pullback_ordered
 from tests.test_ordered_gpu import tol as ordered_tol
+from tests.test_parity_gpu import tol as smooth_tol
 from tests.test_sample_gpu import tol as sample_tol
 
 gpu = pytest.mark.gpu
@@ -107,6 +123,7 @@ A_CLOUDS = dict(B=65_600, P=16, grid=(16, 16))
 A_ORDERED = dict(B=70_000, P=300, grid=(4, 4, 4), n_in=3)
 A_ORD_POINTS = dict(B=2, P=257 * POINT_CHUNK + 17, grid=(8, 8, 8), n_in=3)
 A_ORD_CELLS = dict(B=2, P=3000, grid=(162, 162, 162), n_in=3)
+A_SMOOTH = dict(B=65_600, P=300, grid=(8, 8))
 B_CHANNELS = dict(C=16, B=17, grid=(256,) * 3, P=100_000)
 B_JVP = dict(K=16, B=17, grid=(256,) * 3, P=100_000)
 B_SAMPLE_IMAGE = dict(B=257, grid=(256,) * 3, P=100_000)
@@ -114,6 +131,7 @@ B_SAMPLE_VALUES = dict(B=257, grid=(16,) * 3, P=2 ** 24)
 B_CLOUDS_OUT = dict(B=257, grid=(256,) * 3, P=20_000)
 B_CLOUDS_POINTS = dict(B=343, grid=(16, 16), P=2 ** 22, n_in=3)
 B_ORDERED = dict(B=257, grid=(256,) * 3, P=100_000)
+B_SMOOTH = dict(B=257, grid=(256,) * 3, P=100_000)
 
 
 @pytest.fixture(scope="module")
@@ -510,6 +528,64 @@ def test_ordered_reduce_second_round_of_cell_chunks(oracle, dev, npdt, tdt):
     assert_same_bits(got.background, pb.background, "residual with target 0 and scale 1: ds_dbackground")
 
 
+# ------------------------------------------------------------------ A.7 smooth splat: B poses
+@gpu
+@pytest.mark.parametrize("npdt,tdt", DTYPES)
+@pytest.mark.parametrize("n_in,n_out", [(2, 2), (3, 2)])
+def test_smooth_poses_across_the_launch_cuts(dev, npdt, tdt, n_in, n_out):
+    """ATOMIC forward: k_smooth_fwd_atomic strides the poses over gridDim.y = 65535, fill_background is cut between
+    poses.  Pullback: grid_sum's cut, and k_smooth_bwd takes its poses from blockIdx.y (2 blocks of points: 1010
+    slices of 65 poses).  Everything against tests/smooth_reference.py in fp64 on the inputs of the working type."""
+    s = A_SMOOTH
+    B, P, grid = s["B"], s["P"], s["grid"]
+    assert B > LAUNCH
+    d = D.make(n_points=P, n_in=n_in, n_out=n_out, batch=B, grid_n=grid, seed=70 + n_in, dtype=npdt)
+    rng = np.random.default_rng(71)
+    r = lambda a: np.asarray(a, dtype=npdt).astype(np.float64)
+    pts, R, t = r(d.points), r(d.rotations), r(d.translations)
+    pts[::25] *= 3.0  # some outside the grid
+    pts = r(pts)
+    pw, ow_all = r(rng.uniform(0.5, 1.5, size=P)), r(rng.uniform(0.5, 1.5, size=B))
+    bg = r(distinct(B, 14))
+    assert len(np.unique(bg)) == B
+    sel = around_the_cut(B)
+    rest = np.ones(B, dtype=bool)
+    rest[sel] = False
+    to = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev).to(tdt)
+    dpts, dR, dt, dbg, dpw = (to(a) for a in (pts, R, t, bg, pw))
+    isel, irest = T(np.asarray(sel), dev), T(rest, dev)
+    # forward: out_weight is non-zero only on the five poses around the cut
+    ow = np.where(rest, 0.0, ow_all)
+    out = dpr_amd.raster_smooth(grid, dpts, dR, dt, dbg, to(ow), dpw, algo="atomic")
+    assert tuple(out.shape) == grid + (B,) and out.dtype == tdt
+    ref = SR.raster_smooth(grid, pts, R[sel], t[sel], bg[sel], ow[sel], pw)
+    for i, b in enumerate(sel):
+        assert float(np.abs(ref[..., i] - bg[b]).max()) > 0.1
+        assert_close(out[..., b], ref[..., i].astype(npdt), smooth_tol(npdt, "out"), f"out[.., {b}]")
+    mem = out.permute(2, 1, 0)
+    assert mem.is_contiguous()
+    assert_planes_equal(mem[irest][None], dbg[irest][None], "a pose of out_weight 0 is not its background")
+    # pullback: ds_dout is non-zero only in those five poses; every out_weight is
+    gen = torch.Generator(device=dev).manual_seed(72)
+    g_mem = torch.zeros((B,) + grid[::-1], dtype=tdt, device=dev)
+    g_mem[isel] = torch.randn((len(sel),) + grid[::-1], generator=gen, dtype=tdt, device=dev)
+    g = g_mem.permute(2, 1, 0)
+    pb = dpr_amd.raster_pullback_smooth_(g, dpts, dR, dt, dbg, to(ow_all), dpw)
+    torch.cuda.synchronize()
+    want = SR.raster_pullback_smooth(g[..., isel].cpu().numpy().astype(np.float64), pts, R[sel], t[sel], ow_all[sel],
+                                     pw)
+    assert_close(pb.points, want[0].astype(npdt), smooth_tol(npdt, "points"), "ds_dpoints")
+    assert_close(pb.point_weight, want[5].astype(npdt), smooth_tol(npdt, "points"), "ds_dpoint_weight")
+    for name, got, e in (("ds_drotation", pb.rotation, want[1]), ("ds_dtranslation", pb.translation, want[2]),
+                         ("ds_dout_weight", pb.out_weight, want[4])):
+        for i, b in enumerate(sel):
+            assert float(np.abs(e[i]).max()) > 0
+            assert_close(got[b:b + 1], e[i:i + 1].astype(npdt), smooth_tol(npdt, "pose"), f"{name}[{b}]")
+        assert not bool((got[irest] != 0).any()), f"{name}: a pose without sensitivity is not 0"
+    assert_plane_sums(pb.background, g, n_out, npdt, "ds_dbackground")
+    assert bool((pb.background[isel] != 0).all())
+
+
 # =================================================================== Part B: a whole plane past element 2^32
 def host_plane(t):
     """A (n, n, n) plane of a grid-layout tensor -> numpy"""
@@ -865,13 +941,62 @@ def test_ordered_pose_past_2_pow_32(oracle, dev):
     torch.cuda.empty_cache()
 
 
+# ------------------------------------------------------------------ B.6 smooth splat
+@gpu
+def test_smooth_pose_past_2_pow_32(dev):
+    """257 poses of 256^3: pose 256 starts at element 2^32.  ATOMIC and TILED forward with out_weight zero except
+    for poses 0 and 256; the pullback with ds_dout zero except in pose 256.  Against tests/smooth_reference.py in
+    fp64 on the fp32 inputs."""
+    s = B_SMOOTH
+    B, grid, P = s["B"], s["grid"], s["P"]
+    G, last = cells(grid), B - 1
+    assert last * G >= 2 ** 32
+    rng = np.random.default_rng(49)
+    r64 = lambda a: np.asarray(a, np.float64)
+    pts = cloud_f32(rng, P)
+    R, t = poses_f32(rng, B)
+    pw = rng.uniform(0.5, 1.5, size=P).astype(F32)
+    bg = distinct(B, 6).astype(F32)
+    ow_all = rng.uniform(0.5, 1.5, size=B).astype(F32)
+    ow = only_first_and_last(ow_all)
+    dpts, dR, dt, dpw, dbg = (T(a, dev) for a in (pts, R, t, pw, bg))
+    refs = {b: SR.raster_smooth(grid, r64(pts), r64(R[b:b + 1]), r64(t[b:b + 1]), r64(bg[b:b + 1]), r64(ow[b:b + 1]),
+                                r64(pw))[..., 0].astype(F32) for b in (0, last)}
+    for algo in ("atomic", "tiled"):
+        out = dpr_amd.raster_smooth(grid, dpts, dR, dt, dbg, T(ow, dev), dpw, algo=algo)
+        torch.cuda.synchronize()
+        for b in (last, 0):
+            assert_close(out[..., b], refs[b], smooth_tol(F32, "out"), f"{algo}: out[.., {b}]")
+        assert_planes_equal(out.permute(3, 2, 1, 0)[1:last], dbg[1:last], f"{algo}: a middle pose")
+        del out
+        torch.cuda.empty_cache()
+    del refs
+    gen = torch.Generator(device=dev).manual_seed(49)
+    g_mem = torch.zeros((B,) + grid, device=dev)
+    g_mem[last].normal_(generator=gen)
+    g = g_mem.permute(3, 2, 1, 0)
+    pb = dpr_amd.raster_pullback_smooth_(g, dpts, dR, dt, dbg, T(ow_all, dev), dpw)
+    torch.cuda.synchronize()
+    ref = SR.raster_pullback_smooth(host_plane(g[..., last])[..., None], r64(pts), r64(R[last:]), r64(t[last:]),
+                                    r64(ow_all[last:]), r64(pw))
+    assert_close(pb.points, ref[0], smooth_tol(F32, "points"), "ds_dpoints")
+    assert_close(pb.point_weight, ref[5], smooth_tol(F32, "points"), "ds_dpoint_weight")
+    for name, got, e in (("rotation", pb.rotation, ref[1]), ("translation", pb.translation, ref[2]),
+                         ("background", pb.background, ref[3]), ("out_weight", pb.out_weight, ref[4])):
+        assert_close(got[last:], e, smooth_tol(F32, "pose"), f"ds_d{name}[{last}]")
+        assert not bool((got[:last] != 0).any()), f"ds_d{name} of the poses before the last is not 0"
+    del g, g_mem, pb
+    torch.cuda.empty_cache()
+
+
 # =================================================================== the CPU side
 def test_shapes_cross_the_limit_they_name_and_no_other():
     """Recomputed from DPR_ORDERED_POINT_CHUNK / DPR_ORDERED_CELL_CHUNK of include/dpr.h and the literals 65535,
     2^20 and 256 of the drivers: a later change of a constant must not move a test back inside the first launch."""
     GB = 2 ** 30
     # Part A: one limit each, tiny planes (at most 1 MB in fp64), small arrays
-    for s in (A_CHANNELS_PLANES, A_CHANNELS_POSES, A_JVP_PLANES, A_JVP_POSES, A_CLOUDS, A_ORDERED, A_ORD_POINTS):
+    for s in (A_CHANNELS_PLANES, A_CHANNELS_POSES, A_JVP_PLANES, A_JVP_POSES, A_CLOUDS, A_ORDERED, A_ORD_POINTS,
+              A_SMOOTH):
         assert cells(s["grid"]) * 8 <= 2 ** 20, s
         assert cells(s["grid"]) * s["B"] * s.get("C", s.get("K", 1)) < 2 ** 31, s  # no offset near 2^32
     for s, per_pose in ((A_CHANNELS_PLANES, "C"), (A_JVP_PLANES, "K")):
@@ -893,6 +1018,15 @@ def test_shapes_cross_the_limit_they_name_and_no_other():
     s = A_ORD_CELLS
     assert STAGE < -(-cells(s["grid"]) // CELL_CHUNK) <= 2 * STAGE and -(-s["P"] // POINT_CHUNK) <= STAGE
     assert s["B"] <= LAUNCH and s["B"] * 15 <= REDUCE_BLOCKS and cells(s["grid"]) * s["B"] < 2 ** 31
+    # the smooth splat: the pose stride of the forward, and pose_slices (csrc/dpr_api.hip) for the pullback: 2 blocks of
+    # 256 points, 1024 slices wanted, 65 poses per slice, 1010 slices; the poses around the cut lie in three of them
+    s = A_SMOOTH
+    assert LAUNCH < s["B"] <= 2 * LAUNCH
+    pblocks = -(-s["P"] // 256)
+    wanted = min(s["B"], -(-2048 // pblocks), LAUNCH)
+    per_slice = -(-s["B"] // wanted)
+    assert (pblocks, wanted, per_slice, -(-s["B"] // per_slice)) == (2, 1024, 65, 1010)
+    assert sorted({b // per_slice for b in around_the_cut(s["B"])}) == [0, 1008, 1009]
     # Part B: the last plane / pose / cloud starts at or past element 2^32 and the one before it below; no launch
     # cut; within the entry points' own limits (check_common: grid[d] <= 32768, G <= 2^31 - 1; C, K <= 16;
     # check_sample_sizes / check_clouds_sizes: products below 2^60; ORDERED: prod (n_d + 1) <= 2^32 - 1) and
@@ -905,7 +1039,8 @@ def test_shapes_cross_the_limit_they_name_and_no_other():
             ("sample values", B_SAMPLE_VALUES, B_SAMPLE_VALUES["P"], 1),
             ("clouds out", B_CLOUDS_OUT, cells(B_CLOUDS_OUT["grid"]), 1),
             ("clouds points", B_CLOUDS_POINTS, B_CLOUDS_POINTS["P"] * B_CLOUDS_POINTS["n_in"], 2),  # and ds_dpoints
-            ("ordered", B_ORDERED, cells(B_ORDERED["grid"]), 1)):
+            ("ordered", B_ORDERED, cells(B_ORDERED["grid"]), 1),
+            ("smooth", B_SMOOTH, cells(B_SMOOTH["grid"]), 1)):
         B = s["B"]
         assert (B - 1) * stride >= 2 ** 32 > (B - 2) * stride, name
         assert B * s.get("C", s.get("K", 1)) <= LAUNCH, name
@@ -917,3 +1052,5 @@ def test_shapes_cross_the_limit_they_name_and_no_other():
     assert int(np.prod([n + 1 for n in B_ORDERED["grid"]])) <= 2 ** 32 - 1
     assert (B_JVP["K"] - 1) * 2 ** 23 * 3 < 2 ** 32  # the JVP's tangent offsets: out of reach (module docstring)
     assert B_ORDERED["B"] * 15 <= REDUCE_BLOCKS and -(-B_ORDERED["P"] // POINT_CHUNK) <= STAGE
+    # the smooth TILED forward takes the call: 16 x 32 x 32 tiles (3-D 16 x 8 x 8), far below its 2^31 - 1 limit
+    assert int(np.prod([-(-n // e) for n, e in zip(B_SMOOTH["grid"], (16, 8, 8))])) == 16384
