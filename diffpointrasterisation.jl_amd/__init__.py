@@ -20,6 +20,8 @@ from .clouds import (raster_clouds, raster_clouds_, raster_clouds_ad, raster_pul
                      workspace_bytes_clouds)
 from .smooth import (raster_pullback_smooth_, raster_smooth, raster_smooth_, raster_smooth_ad, resolve_algo_smooth,
                      workspace_bytes_smooth)
+from .sample_smooth import (resolve_algo_sample_smooth, sample_smooth, sample_smooth_, sample_smooth_ad,
+                            sample_smooth_pullback_, workspace_bytes_sample_smooth)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -38,4 +40,6 @@ __all__ = [
     "workspace_bytes_clouds",
     "raster_smooth", "raster_smooth_", "raster_pullback_smooth_", "raster_smooth_ad", "resolve_algo_smooth",
     "workspace_bytes_smooth",
+    "sample_smooth", "sample_smooth_", "sample_smooth_pullback_", "sample_smooth_ad", "resolve_algo_sample_smooth",
+    "workspace_bytes_sample_smooth",
 ]

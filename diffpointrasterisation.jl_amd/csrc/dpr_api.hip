@@ -1682,6 +1682,141 @@ static size_t workspace_smooth_impl(int op, int algo, unsigned flags, int n_in, 
     return smooth_workspace_bytes(op, algo, n_out, grid, P);
 }
 
+// ---------------------------------------------------------------- smooth sampling
+// dpr_sample_smooth_ex_* / dpr_sample_smooth_pullback_ex_* (include/dpr.h, "SMOOTH SAMPLING"; kernels:
+// dpr_smooth.hip).  Forward: DPR_ALGO_ATOMIC.  Pullback: DPR_ALGO_ATOMIC, the fused kernel with image atomics;
+// DPR_ALGO_TILED, the same kernel without them, then ds_dimage pose by pose from the tiled smooth forward.
+static int check_sample_smooth_op(int op, unsigned flags) {
+    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
+        return fail(DPR_ERR_INVALID_ARG, "smooth sampling: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
+    if (flags & 3u)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "smooth sampling keeps / reuses no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
+    return DPR_OK;
+}
+
+// AUTO: the forward is ATOMIC; the pullback is TILED where the smooth forward of one pose of the shape would be
+// (the measured rows: profiles/sample_smooth_probe.txt)
+static int resolve_algo_sample_smooth(int algo, int op, int n_out, const int64_t* grid, int64_t P) {
+    if (algo != DPR_ALGO_AUTO) return algo;
+    if (op == DPR_OP_PULLBACK) return resolve_algo_smooth(DPR_ALGO_AUTO, DPR_OP_RASTER, n_out, grid, P);
+    return DPR_ALGO_ATOMIC;
+}
+
+// bytes of workspace, or (size_t)-1 (message recorded) when the algorithm cannot run the call
+static size_t sample_smooth_workspace_bytes(int op, int algo, int n_out, const int64_t* grid, int64_t P) {
+    if (algo == DPR_ALGO_ATOMIC) return 0;
+    if (algo != DPR_ALGO_TILED) {
+        fail(DPR_ERR_UNSUPPORTED_ALGO,
+             "smooth sampling runs on DPR_ALGO_ATOMIC and, the pullback, DPR_ALGO_TILED, not algorithm %d", algo);
+        return (size_t)-1;
+    }
+    if (op != DPR_OP_PULLBACK) {
+        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth sampling forward runs on DPR_ALGO_ATOMIC only");
+        return (size_t)-1;
+    }
+    const size_t n = smooth_tiled_workspace_bytes(n_out, grid, P);
+    if (n == (size_t)-1)
+        fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth DPR_ALGO_TILED: too many tiles for a 32-bit key or P > 2^32 - 2");
+    return n;
+}
+
+// the host checks both entry points share; *G_out and the resolved *algo come back
+static int check_sample_smooth(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
+                               int64_t B, int64_t* G_out, size_t* need) {
+    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
+    if (int rc = check_common(n_in, n_out, grid, P, B, G_out)) return rc;
+    if (int rc = check_sample_smooth_op(op, flags)) return rc;
+    *algo = resolve_algo_sample_smooth(*algo, op, n_out, grid, P);
+    *need = sample_smooth_workspace_bytes(op, *algo, n_out, grid, P);
+    if (*need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
+    return check_sample_sizes(P, B, *G_out);
+}
+
+template <typename T>
+static int sample_smooth_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                              int64_t P, int64_t B, T* values, const T* image, const T* points, const T* rot,
+                              const T* trans, void* ws, size_t ws_bytes) {
+    (void)ws_bytes;
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_sample_smooth(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return rc;
+    if (P == 0 || B == 0) return DPR_OK;
+    if (!values) return fail(DPR_ERR_INVALID_ARG, "values is NULL");
+    if (!image) return fail(DPR_ERR_INVALID_ARG, "image is NULL");
+    if (!points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+    if (int rc = check_alignment<T>(ws, {values, image, points, rot, trans})) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    int64_t slices = 1;
+    const int pps = pose_slices(P, B, &slices);
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        const int rc = sample_smooth_fwd<T, decltype(ni)::value, decltype(no)::value>(
+            st, grid, G, P, B, values, image, points, rot, trans, pps, slices);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+template <typename T>
+static int sample_smooth_pullback_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
+                                       const int64_t* grid, int64_t P, int64_t B, const T* dv, const T* image,
+                                       const T* points, const T* rot, const T* trans, T* d_img, T* d_pts, T* d_rot,
+                                       T* d_trans, void* ws, size_t ws_bytes) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_sample_smooth(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return rc;
+    if (!d_img && !d_pts && !d_rot && !d_trans)
+        return fail(DPR_ERR_INVALID_ARG, "smooth sampling pullback: every output is NULL");
+    const bool tiled = algo == DPR_ALGO_TILED;
+    if (tiled && d_img && P > 0 && B > 0 && need > 0 && (!ws || ws_bytes < need))
+        return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_TILED smooth sampling pullback needs %zu workspace bytes, got %zu",
+                    need, ws ? ws_bytes : (size_t)0);
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (P > 0 && B > 0) {
+        if (!dv) return fail(DPR_ERR_INVALID_ARG, "ds_dvalues is NULL");
+        if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+        if ((d_pts || d_rot || d_trans) && !image)
+            return fail(DPR_ERR_INVALID_ARG, "image is NULL (needed for ds_dpoints / ds_drotation / ds_dtranslation)");
+    }
+    if (int rc = check_alignment<T>(ws, {dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans})) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    if (d_rot) DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * n_out * n_in), st));
+    if (d_trans) DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * n_out), st));
+    if (d_img) DPR_HIP(hipMemsetAsync(d_img, 0, sizeof(T) * (size_t)(B * G), st));
+    if (d_pts && B == 0) DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * n_in), st));
+    if (P == 0 || B == 0) return DPR_OK;
+    int64_t slices = 1;
+    const int pps = pose_slices(P, B, &slices);
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        if (int rc = sample_smooth_bwd<T, NI, NO>(st, grid, G, P, B, dv, image, points, rot, trans,
+                                                  tiled ? nullptr : d_img, d_pts, d_rot, d_trans, pps, slices))
+            return rc;
+        stage_mark(st);
+        if (tiled && d_img) {
+            // plane b (zeroed above): the single-pose tiled smooth forward of weights ds_dvalues[:, b] (a contiguous
+            // column), out_weight 1 -- what dpr_raster_smooth_ex_*(DPR_ALGO_TILED) returns for them
+            for (int64_t b = 0; b < B; ++b)
+                if (int rc = smooth_fwd_tiled<T, NI, NO>(st, grid, G, P, 1, d_img + b * G, points, rot + b * (NO * NI),
+                                                         trans + b * NO, nullptr, dv + b * P, ws, ws_bytes))
+                    return rc;
+        }
+        return DPR_OK;
+    });
+}
+
+template <typename T>
+static size_t workspace_sample_smooth_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                           int64_t P, int64_t B) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (check_sample_smooth(op, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return (size_t)-1;
+    return need;
+}
+
 }  // namespace dpr
 
 extern "C" {
@@ -2001,5 +2136,40 @@ int dpr_resolve_algo_smooth(int op, int n_in, int n_out, const int64_t* grid, in
 DPR_DEFINE_SMOOTH(f32, float)
 DPR_DEFINE_SMOOTH(f64, double)
 #undef DPR_DEFINE_SMOOTH
+
+int dpr_resolve_algo_sample_smooth(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
+    int64_t G = 0;
+    if (int rc = dpr::check_smooth_dims(n_in, n_out)) return rc;
+    if (int rc = dpr::check_common(n_in, n_out, grid, P, B, &G)) return rc;
+    if (int rc = dpr::check_sample_smooth_op(op, 0u)) return rc;
+    return dpr::resolve_algo_sample_smooth(DPR_ALGO_AUTO, op, n_out, grid, P);
+}
+
+#define DPR_DEFINE_SAMPLE_SMOOTH(SUF, T)                                                                       \
+    size_t dpr_workspace_bytes_sample_smooth_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,   \
+                                                      const int64_t* grid, int64_t P, int64_t B) {             \
+        return dpr::workspace_sample_smooth_impl<T>(op, algo, flags, n_in, n_out, grid, P, B);                 \
+    }                                                                                                          \
+    int dpr_sample_smooth_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,                \
+                                   const int64_t* grid, int64_t P, int64_t B, T* values, const T* image,       \
+                                   const T* points, const T* rotation, const T* translation, void* workspace,  \
+                                   size_t workspace_bytes) {                                                   \
+        return dpr::sample_smooth_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, values, image, points, \
+                                          rotation, translation, workspace, workspace_bytes);                  \
+    }                                                                                                          \
+    int dpr_sample_smooth_pullback_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,       \
+                                            const int64_t* grid, int64_t P, int64_t B, const T* ds_dvalues,    \
+                                            const T* image, const T* points, const T* rotation,                \
+                                            const T* translation, T* ds_dimage, T* ds_dpoints,                 \
+                                            T* ds_drotation, T* ds_dtranslation, void* workspace,              \
+                                            size_t workspace_bytes) {                                          \
+        return dpr::sample_smooth_pullback_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, ds_dvalues,   \
+                                                   image, points, rotation, translation, ds_dimage,            \
+                                                   ds_dpoints, ds_drotation, ds_dtranslation, workspace,       \
+                                                   workspace_bytes);                                           \
+    }
+DPR_DEFINE_SAMPLE_SMOOTH(f32, float)
+DPR_DEFINE_SAMPLE_SMOOTH(f64, double)
+#undef DPR_DEFINE_SAMPLE_SMOOTH
 
 }  // extern "C"

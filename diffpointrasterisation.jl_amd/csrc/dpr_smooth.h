@@ -65,4 +65,16 @@ int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
                       const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts, T* d_rot,
                       T* d_trans, T* d_ow, T* d_pw, int poses_per_slice, int64_t slices);
 
+// Smooth sampling (include/dpr.h, "SMOOTH SAMPLING"), with the same pose slicing.  Forward: values (P x B, point
+// index fastest) are stored, no atomics.  Pullback: any of d_img, d_pts, d_rot, d_trans may be NULL (none: nothing
+// is launched); d_img, d_rot and d_trans are zeroed by the caller, d_pts here when there is more than one slice;
+// `image` is read only for d_pts / d_rot / d_trans.
+template <typename T, int NI, int NO>
+int sample_smooth_fwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* values, const T* image,
+                      const T* points, const T* rot, const T* trans, int poses_per_slice, int64_t slices);
+template <typename T, int NI, int NO>
+int sample_smooth_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* dv,
+                      const T* image, const T* points, const T* rot, const T* trans, T* d_img, T* d_pts, T* d_rot,
+                      T* d_trans, int poses_per_slice, int64_t slices);
+
 }  // namespace dpr

@@ -14,6 +14,8 @@
 //                             + halo of f64 cells (ds_add_f64) and adds every non-zero cell inside the grid onto
 //                             `out` with one global atomic in T, rows of axis 0 on consecutive lanes.  No global
 //                             atomic per point; a cell receives at most 3^N tile partials.
+//   smooth sampling           k_sample_smooth_fwd / k_sample_smooth_bwd (include/dpr.h, "SMOOTH SAMPLING"): the same
+//                             cell, weights and gathers read the other way round -- an image at the points
 #include <hip/hip_runtime.h>
 
 #include "../../include/dpr.h"
@@ -279,6 +281,159 @@ __global__ __launch_bounds__(kSmBlock) void k_smooth_bwd(
     }
 }
 
+// ---------------------------------------------------------------- smooth sampling (include/dpr.h, "SMOOTH SAMPLING")
+//   values[p, b] = W of smooth_point_backward for g = image_b: the transpose of the splat in the point weights.
+//   values, ds_dvalues   P x B, point index fastest: pose b is the contiguous column at b * P
+//   image, ds_dimage     (n_1, .., n_N, B) column-major, as `out`
+// Both kernels hold a point in registers and loop over a slice of the poses (k_smooth_bwd's shape).
+
+// Forward: one thread per point, the gathers issued plane by plane (smooth_point_backward), the value stored with a
+// plain coalesced store into column b.  A rejected point gives 0.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_sample_smooth_fwd(GridDesc<NO> gd, int64_t P, int64_t B,
+                                                                T* __restrict__ values, const T* __restrict__ image,
+                                                                const T* __restrict__ points,
+                                                                const T* __restrict__ rot,
+                                                                const T* __restrict__ trans, int poses_per_slice) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (p >= P) return;
+    T pt[NI];
+    load_point<T, NI>(points, p, pt);
+    const int64_t b_lo = (int64_t)blockIdx.y * poses_per_slice;
+    const int64_t b_hi = (b_lo + poses_per_slice < B) ? b_lo + poses_per_slice : B;
+    for (int64_t b = b_lo; b < b_hi; ++b) {
+        const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, nullptr, b);
+        int j0[NO];
+        T u[NO];
+        T v = T(0);
+        if (smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) {
+            const T* img = image + b * gd.G;
+            T dcoord[NO];  // (only W is kept; the compiler drops the derivative sums)
+            smooth_point_backward<T, NO>(j0, u, gd, [&](int off) { return img[off]; }, dcoord, v);
+        }
+        values[b * P + p] = v;
+    }
+}
+
+// Pullback over the pose range of the slice for dv = ds_dvalues[p, b]:
+//   ds_dpoints, ds_drotation, ds_dtranslation: k_smooth_bwd's terms with ds_dout = image_b, out_weight = 1 and
+//                                              point_weight = dv
+//   ds_dimage[.., b] += dv * prod_d w_d(s_d)   (k_smooth_fwd_atomic's contribution for point weight dv), when non-NULL
+// Any output may be NULL (uniform branches; the image is read only for the three geometric gradients).  Pre-zeroed:
+// ds_drotation, ds_dtranslation, ds_dimage; ds_dpoints is stored (accumulate_points == 0) or added atomically onto
+// a zeroed buffer.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_sample_smooth_bwd(
+    GridDesc<NO> gd, int64_t P, int64_t B, const T* __restrict__ ds_dvalues, const T* __restrict__ image,
+    const T* __restrict__ points, const T* __restrict__ rot, const T* __restrict__ trans,
+    T* __restrict__ ds_dimage, T* __restrict__ ds_dpoints, T* __restrict__ ds_drotation,
+    T* __restrict__ ds_dtranslation, int poses_per_slice, int accumulate_points) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    constexpr int NV = NO * NI + NO;  // dR | dt
+    constexpr int NW = kSmBlock / kWave;
+    __shared__ T red[NW][NV];
+
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    const bool live = p < P;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const bool geom = ds_dpoints || ds_drotation || ds_dtranslation;
+    const bool pose_sums = ds_drotation || ds_dtranslation;
+    T pt[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) pt[j] = T(0);
+    if (live) load_point<T, NI>(points, p, pt);
+
+    T acc_pt[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) acc_pt[j] = T(0);
+
+    const int64_t b_lo = (int64_t)blockIdx.y * poses_per_slice;
+    const int64_t b_hi = (b_lo + poses_per_slice < B) ? b_lo + poses_per_slice : B;
+    for (int64_t b = b_lo; b < b_hi; ++b) {
+        const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, nullptr, b);
+        T vals[NV];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) vals[k] = T(0);
+        int j0[NO];
+        T u[NO];
+        if (live && smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) {
+            const T dv = ds_dvalues[b * P + p];
+            if (ds_dimage) {
+                const SmoothAxes<T, NO> ax = smooth_axes<T, NO>(j0, u, gd);
+                T* o = ds_dimage + b * gd.G;
+#pragma unroll
+                for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+                    const bool in2 = NO == 3 ? ax.in[NO - 1][k2] : true;
+                    const int off2 = NO == 3 ? ax.off[NO - 1][k2] : 0;
+                    const T w2 = NO == 3 ? ax.w[NO - 1][k2] * dv : dv;
+#pragma unroll
+                    for (int k1 = 0; k1 < 3; ++k1) {
+                        const T w12 = ax.w[1][k1] * w2;
+#pragma unroll
+                        for (int k0 = 0; k0 < 3; ++k0)
+                            if (in2 && ax.in[1][k1] && ax.in[0][k0])
+                                atomic_add<T>(o + (off2 + ax.off[1][k1] + ax.off[0][k0]), ax.w[0][k0] * w12);
+                    }
+                }
+            }
+            if (geom) {
+                const T* img = image + b * gd.G;
+                T dcoord[NO], W;
+                smooth_point_backward<T, NO>(j0, u, gd, [&](int off) { return img[off]; }, dcoord, W);
+                T scaled[NO];
+#pragma unroll
+                for (int n = 0; n < NO; ++n) scaled[n] = (dcoord[n] * dv) * (T(gd.n[n]) / T(2));
+#pragma unroll
+                for (int n = 0; n < NO; ++n) {
+#pragma unroll
+                    for (int j = 0; j < NI; ++j) vals[n + j * NO] = scaled[n] * pt[j];
+                    vals[NO * NI + n] = scaled[n];
+                }
+#pragma unroll
+                for (int j = 0; j < NI; ++j) {  // rotation' * scaled
+                    T v = ps.R[0 + j * NO] * scaled[0];
+#pragma unroll
+                    for (int n = 1; n < NO; ++n) v = v + ps.R[n + j * NO] * scaled[n];
+                    acc_pt[j] += v;
+                }
+            }
+        }
+        if (!pose_sums) continue;
+        // per-pose sums: wave -> block -> one atomic per scalar per block
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const T s = wave_sum<T>(vals[k]);
+            if (lane == 0) red[wave][k] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < NV) {
+            T s = red[0][threadIdx.x];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) s += red[w][threadIdx.x];
+            const int k = threadIdx.x;
+            if (s != T(0)) {
+                if (k < NO * NI) {
+                    if (ds_drotation) atomic_add<T>(ds_drotation + b * (NO * NI) + k, s);
+                } else if (ds_dtranslation) {
+                    atomic_add<T>(ds_dtranslation + b * NO + (k - NO * NI), s);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (live && ds_dpoints) {
+        if (accumulate_points) {
+#pragma unroll
+            for (int j = 0; j < NI; ++j) atomic_add<T>(ds_dpoints + p * NI + j, acc_pt[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NI; ++j) ds_dpoints[p * NI + j] = acc_pt[j];
+        }
+    }
+}
+
 // ---------------------------------------------------------------- DPR_ALGO_TILED forward
 // key = id of the tile (column-major over the tiles, axis 0 fastest) that holds cell j0 clamped into the grid
 template <typename T, int NI, int NO>
@@ -508,7 +663,39 @@ int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
     return DPR_OK;
 }
 
+template <typename T, int NI, int NO>
+int sample_smooth_fwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* values, const T* image,
+                      const T* points, const T* rot, const T* trans, int poses_per_slice, int64_t slices) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)slices);
+    hipLaunchKernelGGL((k_sample_smooth_fwd<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, values, image, points,
+                       rot, trans, poses_per_slice);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+template <typename T, int NI, int NO>
+int sample_smooth_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* dv,
+                      const T* image, const T* points, const T* rot, const T* trans, T* d_img, T* d_pts, T* d_rot,
+                      T* d_trans, int poses_per_slice, int64_t slices) {
+    if (P <= 0 || B <= 0 || !(d_img || d_pts || d_rot || d_trans)) return DPR_OK;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    const int accumulate = slices > 1;
+    if (accumulate && d_pts) DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
+    dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)slices);
+    hipLaunchKernelGGL((k_sample_smooth_bwd<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, dv, image, points, rot,
+                       trans, d_img, d_pts, d_rot, d_trans, poses_per_slice, accumulate);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
 #define DPR_SMOOTH_INSTANTIATE(T, NI, NO)                                                                           \
+    template int sample_smooth_fwd<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, T*, const T*, \
+                                              const T*, const T*, const T*, int, int64_t);                         \
+    template int sample_smooth_bwd<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, const T*,     \
+                                              const T*, const T*, const T*, const T*, T*, T*, T*, T*, int,         \
+                                              int64_t);                                                            \
     template int smooth_fwd_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, T*, const T*, \
                                               const T*, const T*, const T*, const T*);                             \
     template int smooth_fwd_tiled<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, T*, const T*,  \

@@ -884,6 +884,80 @@ int dpr_raster_pullback_smooth_ex_f64(void *stream, int algo, unsigned flags, in
                                       double *ds_dout_weight, double *ds_dpoint_weight, void *workspace,
                                       size_t workspace_bytes);
 
+/* ---- SMOOTH SAMPLING: quadratic B-spline interpolation of images at the transformed points, C1 -----------------
+ * The transpose of dpr_raster_smooth_* with respect to the point weights, as SAMPLING is of dpr_raster_*.  With
+ * coord_d, j0_d, u_d, w_d and w'_d of SMOOTH SPLAT and its acceptance rule (-1 <= coord_d < n_d + 1 on every axis,
+ * tested in floating point; NaN / Inf rejected), for pose b:
+ *     values[p, b] = sum over s in {-1, 0, +1}^n_out with j0 + s inside the grid of
+ *                    image[j0 + s, b] * prod_d w_d(s_d)
+ *     values[p, b] = 0 for a rejected point
+ * So
+ *     sum_v (raster_smooth(pw) - background)[v, b] * image[v, b] = out_weight[b] * sum_p pw[p] * values[p, b],
+ * for B = 1 `values` is the ds_dpoint_weight of dpr_raster_pullback_smooth_ex_* with ds_dout = image and
+ * out_weight = 1, and a constant image samples to that constant wherever all 3^N cells are in the grid (coord_d in
+ * [1, n_d - 1): the weights sum to 1).  `values` is C1 in the point position.
+ * The pullback takes ds_dvalues (P x B) and writes
+ *   ds_dimage[.., b]    dpr_raster_smooth_ex_* of pose b with point_weight = ds_dvalues[:, b], background 0,
+ *                       out_weight 1
+ *   and, with scaled_k = ds_dvalues[p, b] * n_k / 2 * sum_s image[j0 + s, b] * w'_k(s_k) * prod_{d != k} w_d(s_d),
+ *   ds_dtranslation[b] = sum_p scaled,   ds_drotation[b] = sum_p scaled * p^T,   ds_dpoints[p] = sum_b R_b^T * scaled
+ * -- the exact derivative; no cell is held fixed.
+ * Layouts: values, ds_dvalues   P x B, point index fastest (pose b is the contiguous column at b * P);
+ *          image, ds_dimage     (n_1, .., n_N, B) as `out` of dpr_raster_ex_*;
+ *          everything else      as for dpr_sample_ex_* / dpr_sample_pullback_ex_*.
+ * (n_in, n_out): (2,2), (3,3) and (3,2); every other pair DPR_ERR_UNSUPPORTED_DIMS.  op: DPR_OP_RASTER (the forward)
+ * or DPR_OP_PULLBACK.  Outputs are overwritten, not accumulated.  Any pullback output may be NULL (not wanted, no
+ * work done for it); at least one must be given; `image` may be NULL when only ds_dimage is wanted.
+ * Algorithms (DPR_ALGO_CHUNKED, DPR_ALGO_ORDERED: DPR_ERR_UNSUPPORTED_ALGO).
+ *   Forward  DPR_ALGO_ATOMIC (= AUTO; DPR_ALGO_TILED: DPR_ERR_UNSUPPORTED_ALGO): one thread per point, the point in
+ *            registers across a slice of the poses, the 3^N gathers issued one 3^(N-1) plane at a time, a dropped
+ *            cell replaced by 0 with a select, the value stored coalesced; no atomics, workspace 0.
+ *   Pullback DPR_ALGO_ATOMIC: one fused kernel per (point, pose slice), sliced as the smooth pullback slices the
+ *            poses: from one set of gathers the point gradient (stored with one slice, added atomically with
+ *            several) and the per-pose sums (wave -> block -> one atomic per scalar per block), and
+ *            ds_dvalues * prod w into ds_dimage with global atomics; workspace 0.
+ *   Pullback DPR_ALGO_TILED: the same kernel without the image atomics, then ds_dimage pose by pose: the planes
+ *            zeroed, then the tiled smooth forward with B = 1, point_weight = ds_dvalues[:, b], out_weight NULL --
+ *            plane b is what dpr_raster_smooth_ex_*(DPR_ALGO_TILED) returns for those weights.  Workspace: that of
+ *            dpr_raster_smooth_ex_*(DPR_ALGO_TILED) for (grid, P), independent of B; its LIMITS and COST apply.
+ * AUTO (dpr_resolve_algo_sample_smooth), from the shape alone: the forward DPR_ALGO_ATOMIC; the pullback
+ * DPR_ALGO_TILED exactly where dpr_resolve_algo_smooth(DPR_OP_RASTER, .., P, 1) returns it, DPR_ALGO_ATOMIC
+ * otherwise (that threshold was measured for the smooth forward; profiles/sample_smooth_probe.txt has this
+ * pullback's own times on either path).
+ * Flags: KEEP / REUSE are refused (DPR_ERR_UNSUPPORTED_ALGO), the others accepted and ignored.
+ * Summation order.  values: plane by plane in smooth_point_backward's order, as the ds_dpoint_weight of the smooth
+ * pullback.  Point gradients: summed over the poses of a slice in pose order, slices added atomically.  Per-pose
+ * sums and ds_dimage: atomics, unordered.
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): as for SMOOTH SPLAT; all outputs NULL
+ * DPR_ERR_INVALID_ARG; a workspace smaller than dpr_workspace_bytes_sample_smooth_ex_* or not 256-byte aligned
+ * DPR_ERR_WORKSPACE.  dpr_workspace_bytes_sample_smooth_ex_* returns (size_t)-1 for every refused combination;
+ * dpr_resolve_algo_sample_smooth a negative status. */
+int dpr_resolve_algo_sample_smooth(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_sample_smooth_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_sample_smooth_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                const int64_t *grid, int64_t P, int64_t B);
+int dpr_sample_smooth_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                             int64_t P, int64_t B, float *values, const float *image, const float *points,
+                             const float *rotation, const float *translation, void *workspace,
+                             size_t workspace_bytes);
+int dpr_sample_smooth_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                             int64_t P, int64_t B, double *values, const double *image, const double *points,
+                             const double *rotation, const double *translation, void *workspace,
+                             size_t workspace_bytes);
+int dpr_sample_smooth_pullback_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, const float *ds_dvalues,
+                                      const float *image, const float *points, const float *rotation,
+                                      const float *translation, float *ds_dimage, float *ds_dpoints,
+                                      float *ds_drotation, float *ds_dtranslation, void *workspace,
+                                      size_t workspace_bytes);
+int dpr_sample_smooth_pullback_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, const double *ds_dvalues,
+                                      const double *image, const double *points, const double *rotation,
+                                      const double *translation, double *ds_dimage, double *ds_dpoints,
+                                      double *ds_drotation, double *ds_dtranslation, void *workspace,
+                                      size_t workspace_bytes);
+
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
  * not in the reference; every algorithm here is faster on coherent input and the sort only depends
