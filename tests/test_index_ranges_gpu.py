@@ -1,5 +1,5 @@
 """Launch-size cuts and offsets past 2^32 in the op families (channels, JVP, sampling, per-pose clouds, ORDERED, the
-smooth splat).
+smooth splat, smooth sampling).
 
 Part A: plane / pose counts across the cuts at 65535 (grid.y), 2^20 (k_ord_reduce blocks) and 256 (the LDS staging
 round of k_ord_reduce), on tiny grids.  Part B: a whole plane, pose or cloud past element 2^32 (fp32, 17 GB arrays:
@@ -36,6 +36,13 @@ What guards what (csrc/dpr_api.hip unless another file is named):
   b * G              ORDERED forward and pullback                    test_ordered_pose_past_2_pow_32
   b * G              smooth ATOMIC and TILED forward (k_smooth_fwd_atomic, k_smooth_tile), ATOMIC pullback
                      (k_smooth_bwd), (3, 3)                          test_smooth_pose_past_2_pow_32
+  k_sample_smooth_fwd, k_sample_smooth_bwd (dpr_smooth.hip) `b_lo = blockIdx.y * poses_per_slice`, 1010 slices of 65
+                     poses, the last of 15 (the b_hi clamp), B > 65535
+                                                                     test_sample_smooth_poses_across_the_launch_cuts
+  b * G              image (k_sample_smooth_fwd, k_sample_smooth_bwd), ds_dimage (k_sample_smooth_bwd; the driver's
+                     `d_img + b * G` for the TILED planes), (3, 3)   test_sample_smooth_image_past_2_pow_32
+  b * P              values (k_sample_smooth_fwd), ds_dvalues (k_sample_smooth_bwd; the driver's `dv + b * P` for the
+                     TILED planes), (3, 3)                           test_sample_smooth_values_past_2_pow_32
 
 Not reachable: the JVP's tangent offset k * P * NI stays below 2^32 at the 16-tangent limit even for P = 2^23,
 NI = 3 (15 * 2^23 * 3 = 1.4 * 2^28), so that second, small-grid call is left out; the (K, P, NI) tangents of
@@ -44,9 +51,16 @@ test_jvp_planes_past_2_pow_32 are read at their small offsets only.
 Part A selects planes / poses 0, 65534, 65535, 65536 and the last, and adds one device-side check of the whole
 tensor.  test_ordered_poses_across_the_launch_cut_and_the_reduce_stride gives only the five selected poses a
 sensitivity in its plain pullback (the serial oracle needs 6.6 s for all 70 000 poses); its residual pullback runs
-on a dense batch.  The eight *_past_2_pow_32 tests sit at the 2^32 floor: 17 GB arrays are their point.
+on a dense batch.  The ten *_past_2_pow_32 tests sit at the 2^32 floor: 17 GB arrays are their point.
 The smooth splat's TILED forward is left out of Part A: it launches four kernels per pose from the host (262 400
-launches at B = 65 600) and its per-pose loop has no cut; its `b * G` is in Part B.
+launches at B = 65 600) and its per-pose loop has no cut; its `b * G` is in Part B.  The TILED smooth sampling
+pullback is left out of Part A for the same reason (its planes are that forward, pose by pose); its `d_img + b * G`
+and `dv + b * P` are in Part B.  test_sample_smooth_values_past_2_pow_32 gives ds_dvalues[:, 256] a value at 100 000
+of its 2^24 points only: the numpy reference walks the 27 cells of every point with a sensitivity, far beyond a
+test's seconds for all of them, and a wrapped offset reads the zeros of an earlier column at those points as well.
+Wall time on an MI355X (2026-10-19): test_sample_smooth_image_past_2_pow_32 1.5 s (test_sample_image_past_2_pow_32
+0.7 s, test_smooth_pose_past_2_pow_32 0.9 s); test_sample_smooth_values_past_2_pow_32 2.4 s
+(test_sample_values_past_2_pow_32, forward only, 0.1 s after it and 1.0 s when it runs first).
 
 Mutation record (scratch builds of libdpr, one MI355X run each; every mutant keeps its accesses inside the buffers,
 a truncated offset wraps DOWN).  Each line: the mutant, the test it failed, the first assertion that fired.
@@ -79,6 +93,7 @@ a truncated offset wraps DOWN).  Each line: the mutant, the test it failed, the 
   32-bit b * G (out) in k_smooth_fwd_atomic    smooth_pose_past: atomic: out[.., 256]
   32-bit b * G (out) in k_smooth_tile          smooth_pose_past: tiled: out[.., 256] (ATOMIC passes before)
   32-bit b * G (ds_dout) in k_smooth_bwd       smooth_pose_past: ds_dpoints (100 % off; both forwards pass before)
+(The smooth sampling mutants: tests/test_sample_smooth_hard_gpu.py.)
 Argued from the code, not run: the `out + k0 * G` / `d_bg + k0` halves of the two driver cuts, k_clouds_bwd_tile's
 `b0` and the strides of k_clouds_fwd_atomic / k_clouds_bwd_atomic (the idioms above, in kernels whose wrong pose
 would show in the same assertions), and every mutant that moves an access past its allocation."""
@@ -91,6 +106,7 @@ import torch
 
 import dpr_amd
 from tests import data as D
+from tests import sample_smooth_reference as SSR
 from tests import smooth_reference as SR
 from tests.test_channels_gpu import tol as channels_tol
 from tests.test_clouds_gpu import check_against_oracle as clouds_check_against_oracle
@@ -132,6 +148,9 @@ B_CLOUDS_OUT = dict(B=257, grid=(256,) * 3, P=20_000)
 B_CLOUDS_POINTS = dict(B=343, grid=(16, 16), P=2 ** 22, n_in=3)
 B_ORDERED = dict(B=257, grid=(256,) * 3, P=100_000)
 B_SMOOTH = dict(B=257, grid=(256,) * 3, P=100_000)
+A_SAMPLE_SMOOTH = dict(B=65_600, P=300, grid=(8, 8))
+B_SAMPLE_SMOOTH_IMAGE = dict(B=257, grid=(256,) * 3, P=100_000)
+B_SAMPLE_SMOOTH_VALUES = dict(B=257, grid=(16,) * 3, P=2 ** 24)
 
 
 @pytest.fixture(scope="module")
@@ -586,6 +605,65 @@ def test_smooth_poses_across_the_launch_cuts(dev, npdt, tdt, n_in, n_out):
     assert bool((pb.background[isel] != 0).all())
 
 
+# ------------------------------------------------------------------ A.8 smooth sampling: B poses
+@gpu
+@pytest.mark.parametrize("npdt,tdt", DTYPES)
+@pytest.mark.parametrize("n_in,n_out", [(2, 2), (3, 2)])
+def test_sample_smooth_poses_across_the_launch_cuts(dev, npdt, tdt, n_in, n_out):
+    """k_sample_smooth_fwd and k_sample_smooth_bwd (ATOMIC) take their poses from blockIdx.y: 2 blocks of points,
+    1010 slices of 65 poses, the last of 15, B past 65535.  The image (forward) and ds_dvalues (pullback) are non-zero
+    only in the five poses around the cut, so every other column, plane and per-pose sum is exactly 0 and ds_dpoints
+    is the reference's over those five.  Against tests/sample_smooth_reference.py in fp64 on the inputs of the working
+    type; the pullback writes into NaN-filled buffers.  (The TILED pullback: see the module docstring.)"""
+    s = A_SAMPLE_SMOOTH
+    B, P, grid = s["B"], s["P"], s["grid"]
+    assert B > LAUNCH
+    d = D.make(n_points=P, n_in=n_in, n_out=n_out, batch=B, grid_n=grid, seed=80 + n_in, dtype=npdt)
+    r = lambda a: np.asarray(a, dtype=npdt).astype(np.float64)
+    pts, R, t = r(d.points), r(d.rotations), r(d.translations)
+    pts[::25] *= 3.0  # some outside the grid
+    pts = r(pts)
+    sel = around_the_cut(B)
+    rest = np.ones(B, dtype=bool)
+    rest[sel] = False
+    to = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev).to(tdt)
+    dpts, dR, dt = (to(a) for a in (pts, R, t))
+    isel, irest = T(np.asarray(sel), dev), T(rest, dev)
+    gen = torch.Generator(device=dev).manual_seed(81)
+    img_mem = torch.zeros((B,) + grid[::-1], dtype=tdt, device=dev)
+    img_mem[isel] = torch.randn((len(sel),) + grid[::-1], generator=gen, dtype=tdt, device=dev)
+    img = img_mem.permute(2, 1, 0)
+    image = img[..., isel].cpu().numpy().astype(np.float64)
+    # forward
+    v = dpr_amd.sample_smooth(img, dpts, dR, dt)
+    assert tuple(v.shape) == (P, B) and v.dtype == tdt and v.t().is_contiguous()
+    ref = SSR.sample_smooth(image, pts, R[sel], t[sel])
+    for i, b in enumerate(sel):
+        assert float(np.abs(ref[:, i]).max()) > 0.1
+        assert_close(v[:, b], ref[:, i].astype(npdt), smooth_tol(npdt, "points"), f"values[:, {b}]")
+    assert not bool((v.t()[irest] != 0).any()), "the column of a zero image is not 0"
+    # pullback
+    dv_mem = torch.zeros((B, P), dtype=tdt, device=dev)
+    dv_mem[isel] = torch.randn((len(sel), P), generator=gen, dtype=tdt, device=dev)
+    nan = float("nan")
+    bufs = dict(ds_dimage=dpr_amd.empty_grid(grid, B, tdt, dev).fill_(nan),
+                ds_dpoints=torch.full((P, n_in), nan, dtype=tdt, device=dev),
+                ds_drotation=torch.full((B, n_in, n_out), nan, dtype=tdt, device=dev).transpose(1, 2),
+                ds_dtranslation=torch.full((B, n_out), nan, dtype=tdt, device=dev))
+    pb = dpr_amd.sample_smooth_pullback_(dv_mem.t(), img, dpts, dR, dt, algo="atomic", **bufs)
+    torch.cuda.synchronize()
+    assert pb.image is bufs["ds_dimage"] and pb.points is bufs["ds_dpoints"]
+    want = SSR.sample_smooth_pullback(dv_mem[isel].t().cpu().numpy().astype(np.float64), image, pts, R[sel], t[sel])
+    assert_close(pb.points, want[1].astype(npdt), smooth_tol(npdt, "points"), "ds_dpoints")
+    for name, kind, got, e in (("ds_dimage", "out", pb.image.permute(2, 0, 1), np.moveaxis(want[0], -1, 0)),
+                               ("ds_drotation", "pose", pb.rotation, want[2]),
+                               ("ds_dtranslation", "pose", pb.translation, want[3])):
+        for i, b in enumerate(sel):
+            assert float(np.abs(e[i]).max()) > 0
+            assert_close(got[b], e[i].astype(npdt), smooth_tol(npdt, kind), f"{name}[{b}]")
+        assert not bool((got[irest] != 0).any()), f"{name}: a pose without sensitivity is not 0"
+
+
 # =================================================================== Part B: a whole plane past element 2^32
 def host_plane(t):
     """A (n, n, n) plane of a grid-layout tensor -> numpy"""
@@ -989,6 +1067,126 @@ def test_smooth_pose_past_2_pow_32(dev):
     torch.cuda.empty_cache()
 
 
+# ------------------------------------------------------------------ B.7 smooth sampling
+def ssr_pose(image_plane, pts, R, t, b, dv=None):
+    """SSR in fp64 on fp32 inputs for pose b alone: the values, or with dv (P,) the pullback"""
+    r64 = lambda a: np.asarray(a, np.float64)
+    a = (r64(image_plane)[..., None], r64(pts), r64(R[b:b + 1]), r64(t[b:b + 1]))
+    return SSR.sample_smooth(*a)[:, 0] if dv is None else SSR.sample_smooth_pullback(r64(dv)[:, None], *a)
+
+
+@gpu
+def test_sample_smooth_image_past_2_pow_32(dev):
+    """257 images of 256^3: image 256 starts at element 2^32.  Forward with the images zero except 0 and 256;
+    pullback on ATOMIC and TILED with ds_dvalues zero except for poses 0 and 256, into a NaN-filled ds_dimage."""
+    s = B_SAMPLE_SMOOTH_IMAGE
+    B, grid, P = s["B"], s["grid"], s["P"]
+    G, last = cells(grid), B - 1
+    assert last * G >= 2 ** 32
+    rng = np.random.default_rng(54)
+    pts = cloud_f32(rng, P)
+    R, t = poses_f32(rng, B)
+    dv = only_first_and_last(rng.standard_normal(size=(B, P)).astype(F32))
+    gen = torch.Generator(device=dev).manual_seed(54)
+    img_mem = torch.zeros((B,) + grid, device=dev)
+    img_mem[0].normal_(generator=gen)
+    img_mem[last].normal_(generator=gen)
+    img = img_mem.permute(3, 2, 1, 0)
+    dpts, dR, dt = T(pts, dev), T(R, dev), T(t, dev)
+    v = dpr_amd.sample_smooth(img, dpts, dR, dt)
+    torch.cuda.synchronize()
+    planes = {b: host_plane(img[..., b]) for b in (0, last)}
+    for b in (last, 0):
+        assert_close(v[:, b], ssr_pose(planes[b], pts, R, t, b), smooth_tol(F32, "points"), f"values[:, {b}]")
+    assert not bool((v.t()[1:last] != 0).any()), "the column of a zero image is not 0"
+    del v
+    want = {b: ssr_pose(planes[b], pts, R, t, b, dv[b]) for b in (0, last)}
+    d_img = dpr_amd.empty_grid(grid, B, torch.float32, dev)
+    for algo in ("atomic", "tiled"):
+        d_img.fill_(float("nan"))
+        pb = dpr_amd.sample_smooth_pullback_(T(dv, dev).t(), img, dpts, dR, dt, ds_dimage=d_img, algo=algo)
+        torch.cuda.synchronize()
+        assert pb.image is d_img
+        for b in (last, 0):
+            ref = want[b]
+            assert_close(pb.image[..., b], ref[0][..., 0].astype(F32), smooth_tol(F32, "out"),
+                         f"{algo}: ds_dimage[.., {b}]")
+            assert_close(pb.rotation[b], ref[2][0], smooth_tol(F32, "pose"), f"{algo}: ds_drotation[{b}]")
+            assert_close(pb.translation[b], ref[3][0], smooth_tol(F32, "pose"), f"{algo}: ds_dtranslation[{b}]")
+        assert_close(pb.points, want[0][1] + want[last][1], smooth_tol(F32, "points"), f"{algo}: ds_dpoints")
+        mem = d_img.permute(3, 2, 1, 0)
+        assert_planes_equal(mem[1:last], torch.zeros(B, device=dev)[1:last], f"{algo}: ds_dimage of a middle pose")
+        assert not bool((pb.rotation[1:last] != 0).any()) and not bool((pb.translation[1:last] != 0).any())
+    del img, img_mem, d_img, pb, mem
+    torch.cuda.empty_cache()
+
+
+@gpu
+def test_sample_smooth_values_past_2_pow_32(dev):
+    """2^24 points x 257 poses on 16^3 images: column 256 of `values` and of ds_dvalues starts at element 2^32.
+    Forward with the images zero except 0 and 256; then, `values` freed, the pullback on both algorithms with
+    ds_dvalues zero except in column 256 (there: at 100 000 points drawn from all 2^24, see the module docstring).
+    The cloud is wide (2 N(0, 1): one point in thirteen is accepted under a pose): the tiled planes of 2^24 accepted
+    points on the four tiles of 16^3, 257 times, and the image atomics of as many, would take 17 s."""
+    s = B_SAMPLE_SMOOTH_VALUES
+    B, grid, P = s["B"], s["grid"], s["P"]
+    last = B - 1
+    assert last * P >= 2 ** 32
+    rng = np.random.default_rng(55)
+    R, t = poses_f32(rng, B)
+    gen = torch.Generator(device=dev).manual_seed(55)
+    dpts = 2.0 * torch.randn((P, 3), generator=gen, device=dev)
+    img_mem = torch.zeros((B,) + grid, device=dev)  # the middle images are zero: their columns must be
+    img_mem[0].normal_(generator=gen)
+    img_mem[last].normal_(generator=gen)
+    img = img_mem.permute(3, 2, 1, 0)
+    dR, dt = T(R, dev), T(t, dev)
+    v = dpr_amd.sample_smooth(img, dpts, dR, dt)
+    torch.cuda.synchronize()
+    assert tuple(v.shape) == (P, B) and v.t().is_contiguous()
+    chosen = np.sort(rng.choice(P, 100_000, replace=False))
+    assert chosen[0] < P // 100 and chosen[-1] > P - P // 100
+    sub = T(chosen, dev)
+    spts = dpts[sub].cpu().numpy()
+    for b in (last, 0):
+        ref = ssr_pose(host_plane(img[..., b]), spts, R, t, b)
+        assert 5000 < np.count_nonzero(ref) < 12_000  # (accepted and rejected points in the subsample)
+        assert_close(v[sub, b], ref, smooth_tol(F32, "points"), f"values[subsample, {b}]")
+        # the whole column: the same kernel on the pose alone, value by value (no sum is involved)
+        alone = dpr_amd.sample_smooth(img[..., b:b + 1], dpts, dR[b:b + 1], dt[b:b + 1])
+        assert torch.equal(v[:, b], alone[:, 0]), f"values[:, {b}] is not the column of the pose alone"
+        del alone
+    assert_planes_equal(v.t()[1:last], torch.zeros(B, device=dev)[1:last], "the column of a zero image")
+    del v
+    torch.cuda.empty_cache()
+    # pullback
+    dv_mem = torch.zeros((B, P), device=dev)
+    dv_mem[last, sub] = torch.randn(len(chosen), generator=gen, device=dev)
+    ref = ssr_pose(host_plane(img[..., last]), spts, R, t, last, dv_mem[last, sub].cpu().numpy())
+    assert np.count_nonzero(ref[1].any(axis=1)) > 5000
+    others = torch.ones(P, dtype=torch.bool, device=dev)
+    others[sub] = False
+    for algo in ("atomic", "tiled"):
+        d_img = dpr_amd.empty_grid(grid, B, torch.float32, dev).fill_(float("nan"))
+        d_pts = torch.full((P, 3), float("nan"), device=dev)
+        pb = dpr_amd.sample_smooth_pullback_(dv_mem.t(), img, dpts, dR, dt, ds_dimage=d_img, ds_dpoints=d_pts,
+                                             algo=algo)
+        torch.cuda.synchronize()
+        assert pb.image is d_img and pb.points is d_pts
+        assert_close(pb.image[..., last], ref[0][..., 0].astype(F32), smooth_tol(F32, "out"),
+                     f"{algo}: ds_dimage[.., {last}]")
+        assert_close(pb.rotation[last], ref[2][0], smooth_tol(F32, "pose"), f"{algo}: ds_drotation[{last}]")
+        assert_close(pb.translation[last], ref[3][0], smooth_tol(F32, "pose"), f"{algo}: ds_dtranslation[{last}]")
+        assert_close(pb.points[sub], ref[1], smooth_tol(F32, "points"), f"{algo}: ds_dpoints[subsample]")
+        assert not bool((pb.points[others] != 0).any()), f"{algo}: ds_dpoints of a point without sensitivity is not 0"
+        assert not bool((d_img.permute(3, 2, 1, 0)[:last] != 0).any()), f"{algo}: ds_dimage before pose {last} is not 0"
+        assert not bool((pb.rotation[:last] != 0).any()) and not bool((pb.translation[:last] != 0).any()), \
+            f"{algo}: a per-pose sum before pose {last} is not 0"
+        del pb, d_img, d_pts
+    del dv_mem, img, img_mem, dpts
+    torch.cuda.empty_cache()
+
+
 # =================================================================== the CPU side
 def test_shapes_cross_the_limit_they_name_and_no_other():
     """Recomputed from DPR_ORDERED_POINT_CHUNK / DPR_ORDERED_CELL_CHUNK of include/dpr.h and the literals 65535,
@@ -996,7 +1194,7 @@ def test_shapes_cross_the_limit_they_name_and_no_other():
     GB = 2 ** 30
     # Part A: one limit each, tiny planes (at most 1 MB in fp64), small arrays
     for s in (A_CHANNELS_PLANES, A_CHANNELS_POSES, A_JVP_PLANES, A_JVP_POSES, A_CLOUDS, A_ORDERED, A_ORD_POINTS,
-              A_SMOOTH):
+              A_SMOOTH, A_SAMPLE_SMOOTH):
         assert cells(s["grid"]) * 8 <= 2 ** 20, s
         assert cells(s["grid"]) * s["B"] * s.get("C", s.get("K", 1)) < 2 ** 31, s  # no offset near 2^32
     for s, per_pose in ((A_CHANNELS_PLANES, "C"), (A_JVP_PLANES, "K")):
@@ -1020,13 +1218,17 @@ def test_shapes_cross_the_limit_they_name_and_no_other():
     assert s["B"] <= LAUNCH and s["B"] * 15 <= REDUCE_BLOCKS and cells(s["grid"]) * s["B"] < 2 ** 31
     # the smooth splat: the pose stride of the forward, and pose_slices (csrc/dpr_api.hip) for the pullback: 2 blocks of
     # 256 points, 1024 slices wanted, 65 poses per slice, 1010 slices; the poses around the cut lie in three of them
-    s = A_SMOOTH
-    assert LAUNCH < s["B"] <= 2 * LAUNCH
-    pblocks = -(-s["P"] // 256)
-    wanted = min(s["B"], -(-2048 // pblocks), LAUNCH)
-    per_slice = -(-s["B"] // wanted)
-    assert (pblocks, wanted, per_slice, -(-s["B"] // per_slice)) == (2, 1024, 65, 1010)
-    assert sorted({b // per_slice for b in around_the_cut(s["B"])}) == [0, 1008, 1009]
+    # smooth sampling: the same slices for the forward and the pullback; values and ds_dvalues stay far below 2^32;
+    # the last slice is partial (15 poses: the b_hi clamp) and the second block of points has idle threads
+    for s in (A_SMOOTH, A_SAMPLE_SMOOTH):
+        assert LAUNCH < s["B"] <= 2 * LAUNCH
+        pblocks = -(-s["P"] // 256)
+        wanted = min(s["B"], -(-2048 // pblocks), LAUNCH)
+        per_slice = -(-s["B"] // wanted)
+        assert (pblocks, wanted, per_slice, -(-s["B"] // per_slice)) == (2, 1024, 65, 1010)
+        assert sorted({b // per_slice for b in around_the_cut(s["B"])}) == [0, 1008, 1009]
+    s = A_SAMPLE_SMOOTH
+    assert s["P"] * s["B"] < 2 ** 31 and s["P"] % 256 != 0 and 0 < s["B"] - 1009 * 65 < 65
     # Part B: the last plane / pose / cloud starts at or past element 2^32 and the one before it below; no launch
     # cut; within the entry points' own limits (check_common: grid[d] <= 32768, G <= 2^31 - 1; C, K <= 16;
     # check_sample_sizes / check_clouds_sizes: products below 2^60; ORDERED: prod (n_d + 1) <= 2^32 - 1) and
@@ -1040,7 +1242,9 @@ def test_shapes_cross_the_limit_they_name_and_no_other():
             ("clouds out", B_CLOUDS_OUT, cells(B_CLOUDS_OUT["grid"]), 1),
             ("clouds points", B_CLOUDS_POINTS, B_CLOUDS_POINTS["P"] * B_CLOUDS_POINTS["n_in"], 2),  # and ds_dpoints
             ("ordered", B_ORDERED, cells(B_ORDERED["grid"]), 1),
-            ("smooth", B_SMOOTH, cells(B_SMOOTH["grid"]), 1)):
+            ("smooth", B_SMOOTH, cells(B_SMOOTH["grid"]), 1),
+            ("sample_smooth image", B_SAMPLE_SMOOTH_IMAGE, cells(B_SAMPLE_SMOOTH_IMAGE["grid"]), 2),  # and ds_dimage
+            ("sample_smooth values", B_SAMPLE_SMOOTH_VALUES, B_SAMPLE_SMOOTH_VALUES["P"], 1)):  # then ds_dvalues
         B = s["B"]
         assert (B - 1) * stride >= 2 ** 32 > (B - 2) * stride, name
         assert B * s.get("C", s.get("K", 1)) <= LAUNCH, name
@@ -1054,3 +1258,12 @@ def test_shapes_cross_the_limit_they_name_and_no_other():
     assert B_ORDERED["B"] * 15 <= REDUCE_BLOCKS and -(-B_ORDERED["P"] // POINT_CHUNK) <= STAGE
     # the smooth TILED forward takes the call: 16 x 32 x 32 tiles (3-D 16 x 8 x 8), far below its 2^31 - 1 limit
     assert int(np.prod([-(-n // e) for n, e in zip(B_SMOOTH["grid"], (16, 8, 8))])) == 16384
+    # smooth sampling: the image test crosses 2^32 in b * G only (values: 257 * 100 000), the values test in b * P
+    # only (images: 257 * 16^3); neither has a pose slice (one slice from 2048 blocks of points on; below, B = 257
+    # poses on grid.y) nor a launch cut; the TILED planes: 16384 and 4 tiles
+    assert B_SAMPLE_SMOOTH_IMAGE["B"] * B_SAMPLE_SMOOTH_IMAGE["P"] < 2 ** 31
+    assert B_SAMPLE_SMOOTH_VALUES["B"] * cells(B_SAMPLE_SMOOTH_VALUES["grid"]) < 2 ** 31
+    assert -(-B_SAMPLE_SMOOTH_VALUES["P"] // 256) >= 2048 > -(-B_SAMPLE_SMOOTH_IMAGE["P"] // 256)
+    assert min(B_SAMPLE_SMOOTH_IMAGE["B"], -(-2048 // -(-B_SAMPLE_SMOOTH_IMAGE["P"] // 256))) <= LAUNCH
+    for s, tiles in ((B_SAMPLE_SMOOTH_IMAGE, 16384), (B_SAMPLE_SMOOTH_VALUES, 4)):
+        assert int(np.prod([-(-n // e) for n, e in zip(s["grid"], (16, 8, 8))])) == tiles

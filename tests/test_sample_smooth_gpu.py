@@ -136,7 +136,8 @@ def test_tiled_image_planes_are_the_tiled_smooth_forward(dev, npdt, tdt, n_in, n
 @pytest.mark.parametrize("npdt,tdt", DTYPES)
 @pytest.mark.parametrize("n_in,n_out", PAIRS)
 def test_many_poses_of_a_small_cloud(dev, npdt, tdt, n_in, n_out):
-    """B = 70, P = 300 on an 8^N grid: the launch cuts the poses into slices (two blocks of points)."""
+    """B = 70, P = 300 on an 8^N grid: two blocks of points, so the launch cuts the poses into 70 slices of one pose
+    each (tests/test_sample_smooth_hard_gpu.py has several poses per slice)."""
     rng = np.random.default_rng(7)
     B, P, grid = 70, 300, (8,) * n_out
     pts = rng.uniform(-1.15, 1.15, size=(P, n_in))
