@@ -22,6 +22,8 @@ from .smooth import (raster_pullback_smooth_, raster_smooth, raster_smooth_, ras
                      workspace_bytes_smooth)
 from .sample_smooth import (resolve_algo_sample_smooth, sample_smooth, sample_smooth_, sample_smooth_ad,
                             sample_smooth_pullback_, workspace_bytes_sample_smooth)
+from .smooth_jvp import (raster_smooth_jvp, raster_smooth_jvp_, resolve_algo_smooth_jvp,
+                         workspace_bytes_smooth_jvp)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -42,4 +44,5 @@ __all__ = [
     "workspace_bytes_smooth",
     "sample_smooth", "sample_smooth_", "sample_smooth_pullback_", "sample_smooth_ad", "resolve_algo_sample_smooth",
     "workspace_bytes_sample_smooth",
+    "raster_smooth_jvp", "raster_smooth_jvp_", "resolve_algo_smooth_jvp", "workspace_bytes_smooth_jvp",
 ]

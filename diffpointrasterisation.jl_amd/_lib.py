@@ -70,6 +70,8 @@ EXPORTS = [
     "dpr_resolve_algo_sample_smooth", "dpr_workspace_bytes_sample_smooth_ex_f32",
     "dpr_workspace_bytes_sample_smooth_ex_f64", "dpr_sample_smooth_ex_f32", "dpr_sample_smooth_ex_f64",
     "dpr_sample_smooth_pullback_ex_f32", "dpr_sample_smooth_pullback_ex_f64",
+    "dpr_resolve_algo_smooth_jvp", "dpr_workspace_bytes_smooth_jvp_ex_f32", "dpr_workspace_bytes_smooth_jvp_ex_f64",
+    "dpr_raster_smooth_jvp_ex_f32", "dpr_raster_smooth_jvp_ex_f64",
 ]
 
 _lib = None
@@ -233,6 +235,16 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, f"dpr_sample_smooth_pullback_ex_{suf}")
         f.restype = i
         f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64] + [vp] * 9 + [vp, sz]
+    L.dpr_resolve_algo_smooth_jvp.restype = i
+    L.dpr_resolve_algo_smooth_jvp.argtypes = [i, i, vp, i64, i64, i64]
+    for suf in ("f32", "f64"):
+        f = getattr(L, f"dpr_workspace_bytes_smooth_jvp_ex_{suf}")
+        f.restype = sz
+        f.argtypes = [i, ctypes.c_uint, i, i, vp, i64, i64, i64]
+        # the argument list of dpr_raster_jvp_ex_*
+        f = getattr(L, f"dpr_raster_smooth_jvp_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 12 + [vp, sz]
     L.dpr_comm_unique_id.restype = i
     L.dpr_comm_unique_id.argtypes = [vp, sz]
     L.dpr_comm_init.restype = i

@@ -1817,6 +1817,95 @@ static size_t workspace_sample_smooth_impl(int op, int algo, unsigned flags, int
     return need;
 }
 
+// ---------------------------------------------------------------- smooth splat, forward mode
+// dpr_raster_smooth_jvp_ex_* (include/dpr.h, "SMOOTH SPLAT, FORWARD MODE"; kernels: dpr_smooth.hip).  k_jvp_fill
+// writes the background tangent into every plane, then DPR_ALGO_ATOMIC (k_smooth_jvp_atomic) or DPR_ALGO_TILED
+// (the tiled smooth forward's binning once per pose, k_smooth_tile_jvp over (tiles, K)) adds the deposits.
+// AUTO (dpr_resolve_algo_smooth_jvp), from the shape and K alone (profiles/smooth_jvp_probe.txt, fp32, uniform clouds
+// in generation order).  The tiled path pays the key, sort and start table once per pose, whatever K; the atomic one
+// 3^N atomics per (point, tangent).  So the point count from which DPR_ALGO_TILED pays falls with K: the rule is the
+// smooth forward's with P * K in the place of P, and for 2-D grids a lower constant.
+//  - 3-D grids, P * K >= 1e5 (the forward's constant): 1e5 -> 256^3, K = 1 0.183 against 0.169 ms ATOMIC (1.08x, the
+//    one row where the rule loses), K = 4 0.378 / 0.503, K = 12 0.98 / 1.43; 1e7 -> 256^3, K = 12 7.8 against 119 ms.
+//  - 2-D grids, P * K >= 4e5.  The forward's 5e5 with P alone broke two rows: 1e5 x 16 poses -> 128^2 at K = 4, 1.59
+//    against 2.57 ms ATOMIC (1.61x), and at K = 12, 1.65 against 7.29 (4.4x).  At K = 1 the same shape is 1.53
+//    against 0.68 ATOMIC, and 1e6 -> 512^2 is 0.268 against 0.435: the constant lies between P * K = 1e5 and 4e5,
+//    and 4e5 is the measured row.  Nothing was measured between.
+constexpr int64_t kSmoothJvpTiledMinWork3D = 100000;
+constexpr int64_t kSmoothJvpTiledMinWork2D = 400000;
+static int resolve_algo_smooth_jvp(int algo, int n_out, const int64_t* grid, int64_t P, int64_t K) {
+    if (algo != DPR_ALGO_AUTO) return algo;
+    const int64_t min_work = n_out == 3 ? kSmoothJvpTiledMinWork3D : kSmoothJvpTiledMinWork2D;
+    if (P * K >= min_work && smooth_tile_count(n_out, grid, P) != 0) return DPR_ALGO_TILED;
+    return DPR_ALGO_ATOMIC;
+}
+
+// the checks every smooth JVP entry point and query shares, in the smooth entry points' order; *need: workspace
+static int check_smooth_jvp(int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
+                            int64_t B, int64_t K, int64_t* G, size_t* need) {
+    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
+    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
+    if (int rc = check_jvp(K, flags)) return rc;
+    if (int rc = check_sample_sizes(P, B, *G)) return rc;
+    if (B > 0 && *G * K > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "output too large");
+    *algo = resolve_algo_smooth_jvp(*algo, n_out, grid, P, K);
+    *need = smooth_workspace_bytes(DPR_OP_RASTER, *algo, n_out, grid, P);
+    return *need == (size_t)-1 ? DPR_ERR_UNSUPPORTED_ALGO : DPR_OK;
+}
+
+template <typename T>
+static int raster_smooth_jvp_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                  int64_t P, int64_t B, int64_t K, T* out_dot, const T* points, const T* rot,
+                                  const T* trans, const T* ow, const T* pw, JvpTangents<T> tan, const T* bg_dot,
+                                  void* ws, size_t ws_bytes) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_smooth_jvp(&algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
+    if (B == 0) return DPR_OK;
+    if (!out_dot) return fail(DPR_ERR_INVALID_ARG, "out_dot is NULL");
+    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
+        return fail(DPR_ERR_WORKSPACE, "smooth JVP (algorithm %d) needs %zu workspace bytes, got %zu", algo, need,
+                    ws ? ws_bytes : (size_t)0);
+    if (int rc = check_alignment<T>(ws, {out_dot, points, rot, trans, ow, pw, tan.points, tan.rot, tan.trans, tan.ow,
+                                         tan.pw, bg_dot}))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    // the background tangent (or 0) into every plane; then the deposits, where any other tangent is given
+    const int k = (int)K;
+    const int64_t planes = B * K;
+    const int64_t want = (G + kBlock - 1) / kBlock;
+    dim3 g((unsigned)(want < 4096 ? want : 4096), 1);
+    for (int64_t q0 = 0; q0 < planes; q0 += 65535) {
+        const int64_t nq = (planes - q0 < 65535) ? planes - q0 : 65535;
+        g.y = (unsigned)nq;
+        hipLaunchKernelGGL(k_jvp_fill<T>, g, dim3(kBlock), 0, st, out_dot, G, k, B, q0, bg_dot);
+    }
+    stage_mark(st);
+    DPR_HIP(hipGetLastError());
+    if (P == 0 || !(tan.points || tan.rot || tan.trans || tan.ow || tan.pw)) return DPR_OK;
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        const int rc = algo == DPR_ALGO_TILED
+                           ? smooth_jvp_tiled<T, NI, NO>(st, grid, G, P, B, k, out_dot, points, rot, trans, ow, pw, tan,
+                                                         ws, ws_bytes)
+                           : smooth_jvp_atomic<T, NI, NO>(st, grid, G, P, B, k, out_dot, points, rot, trans, ow, pw,
+                                                          tan);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+static size_t workspace_smooth_jvp_impl(int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
+                                        int64_t B, int64_t K) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (check_smooth_jvp(&algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return (size_t)-1;
+    return need;
+}
+
 }  // namespace dpr
 
 extern "C" {
@@ -2171,5 +2260,34 @@ int dpr_resolve_algo_sample_smooth(int op, int n_in, int n_out, const int64_t* g
 DPR_DEFINE_SAMPLE_SMOOTH(f32, float)
 DPR_DEFINE_SAMPLE_SMOOTH(f64, double)
 #undef DPR_DEFINE_SAMPLE_SMOOTH
+
+int dpr_resolve_algo_smooth_jvp(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t K) {
+    int64_t G = 0;
+    size_t need = 0;
+    int algo = DPR_ALGO_AUTO;
+    if (int rc = dpr::check_smooth_jvp(&algo, 0u, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
+    return algo;
+}
+
+#define DPR_DEFINE_SMOOTH_JVP(SUF, T)                                                                          \
+    size_t dpr_workspace_bytes_smooth_jvp_ex_##SUF(int algo, unsigned flags, int n_in, int n_out,              \
+                                                   const int64_t* grid, int64_t P, int64_t B, int64_t K) {     \
+        return dpr::workspace_smooth_jvp_impl(algo, flags, n_in, n_out, grid, P, B, K);                        \
+    }                                                                                                          \
+    int dpr_raster_smooth_jvp_ex_##SUF(                                                                        \
+        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, \
+        int64_t K, T* out_dot, const T* points, const T* rotation, const T* translation, const T* out_weight,  \
+        const T* point_weight, const T* points_dot, const T* rotation_dot, const T* translation_dot,           \
+        const T* background_dot, const T* out_weight_dot, const T* point_weight_dot, void* workspace,          \
+        size_t workspace_bytes) {                                                                              \
+        return dpr::raster_smooth_jvp_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, K, out_dot, points, \
+                                              rotation, translation, out_weight, point_weight,                 \
+                                              dpr::JvpTangents<T>{points_dot, rotation_dot, translation_dot,   \
+                                                                  out_weight_dot, point_weight_dot},           \
+                                              background_dot, workspace, workspace_bytes);                     \
+    }
+DPR_DEFINE_SMOOTH_JVP(f32, float)
+DPR_DEFINE_SMOOTH_JVP(f64, double)
+#undef DPR_DEFINE_SMOOTH_JVP
 
 }  // extern "C"

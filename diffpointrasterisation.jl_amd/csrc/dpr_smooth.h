@@ -65,6 +65,17 @@ int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
                       const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts, T* d_rot,
                       T* d_trans, T* d_ow, T* d_pw, int poses_per_slice, int64_t slices);
 
+// Forward-mode derivative (include/dpr.h, "SMOOTH SPLAT, FORWARD MODE"): the deposits of K tangents added onto
+// out_dot, whose planes (b * K + k) hold the background tangent already (k_jvp_fill, launched by dpr_api.hip).
+// The tiled form takes smooth_fwd_tiled's workspace and bins every pose once for all K tangents.
+template <typename T, int NI, int NO>
+int smooth_jvp_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
+                      const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan);
+template <typename T, int NI, int NO>
+int smooth_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
+                     const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan,
+                     void* ws, size_t ws_bytes);
+
 // Smooth sampling (include/dpr.h, "SMOOTH SAMPLING"), with the same pose slicing.  Forward: values (P x B, point
 // index fastest) are stored, no atomics.  Pullback: any of d_img, d_pts, d_rot, d_trans may be NULL (none: nothing
 // is launched); d_img, d_rot and d_trans are zeroed by the caller, d_pts here when there is more than one slice;

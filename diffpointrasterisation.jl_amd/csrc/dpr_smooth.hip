@@ -16,6 +16,9 @@
 //                             atomic per point; a cell receives at most 3^N tile partials.
 //   smooth sampling           k_sample_smooth_fwd / k_sample_smooth_bwd (include/dpr.h, "SMOOTH SAMPLING"): the same
 //                             cell, weights and gathers read the other way round -- an image at the points
+//   forward-mode derivative   k_smooth_jvp_atomic / k_smooth_tile_jvp (include/dpr.h, "SMOOTH SPLAT, FORWARD MODE"):
+//                             the two forward shapes with the deposit of a tangent in the place of the weight
+//                             product; the tiled path bins a pose once for all K tangents
 #include <hip/hip_runtime.h>
 
 #include "../../include/dpr.h"
@@ -560,6 +563,243 @@ __global__ __launch_bounds__(kSmBlock) void k_smooth_tile(GridDesc<NO> gd, Smoot
     }
 }
 
+// ---------------------------------------------------------------- forward-mode derivative of the smooth splat
+// include/dpr.h, "SMOOTH SPLAT, FORWARD MODE".  For tangent k of an accepted (point, pose), with a and
+// bc_n = ow * pw * cdot_n of jvp_coeffs (dpr_jvp.h), e_d = w_d and f_d = bc_d * w'_d:
+//   deposit(s) = a * prod_d e_d + sum_n f_n * prod_{d != n} e_d = e_0 * X + f_0 * Y
+//   2-D: X = a * e_1 + f_1,                  Y = e_1
+//   3-D: X = e_1 * (a * e_2 + f_2) + f_1 * e_2,  Y = e_1 * e_2
+// X and Y are formed once per (k1, k2).  out_dot holds the background tangent already (k_jvp_fill); plane (b, k) is
+// at (b * K + k) * G.  These kernels are copies of k_smooth_fwd_atomic / k_smooth_tile, not shared bodies: the
+// forward kernels keep their registers.
+template <typename T, int NO> struct SmoothJvpRows {
+    T X[NO == 3 ? 3 : 1][3], Y[NO == 3 ? 3 : 1][3];
+};
+template <typename T, int NO>
+__device__ __forceinline__ SmoothJvpRows<T, NO> smooth_jvp_rows(T a, const T (&bc)[NO], const T (&w)[NO][3],
+                                                                const T (&dw)[NO][3]) {
+    SmoothJvpRows<T, NO> r;
+#pragma unroll
+    for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+        const T e2 = NO == 3 ? w[NO - 1][k2] : T(1);
+        const T a2 = NO == 3 ? a * e2 + bc[NO - 1] * dw[NO - 1][k2] : a;  // a * e_2 + f_2
+#pragma unroll
+        for (int k1 = 0; k1 < 3; ++k1) {
+            r.X[k2][k1] = w[1][k1] * a2 + (bc[1] * dw[1][k1]) * e2;
+            r.Y[k2][k1] = w[1][k1] * e2;
+        }
+    }
+    return r;
+}
+
+// One thread per point, the poses strided over gridDim.y (k_smooth_fwd_atomic's shape).  The cell, the weights and
+// their derivatives once per accepted (point, pose); the K tangents are a run-time loop of 3^N atomics each.  A
+// rejected point reads none of its tangents.
+//
+// Lanes of a wave that share a centre cell share all 3^N addresses.  A cloud with many points in a cell would send
+// every one of them to the same few cells as fp32 atomics in arrival order: slow (they serialise) and, with deposits
+// of both signs, noisy run to run.  So where a wave holds at least kSmJvpMinRun lanes whose neighbour lane has the
+// same cell, up to kSmJvpGroups groups of lanes with equal cells are found (ballots, wave-uniform), each group's
+// deposits are added across the wave in a fixed order (wave_sum) and its first lane issues one atomic per cell.
+// Lanes outside the groups, and every lane of a wave without such runs, issue their own atomics.  A wave of
+// a scattered cloud pays one shuffle per axis and one ballot per (point, pose) for the test.
+constexpr int kSmJvpGroups = 4;   // groups of equal cells combined per wave
+constexpr int kSmJvpTries = 8;    // cells looked at while searching for them
+constexpr int kSmJvpMinRun = 8;   // lanes equal to their neighbour before a wave searches at all
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_jvp_atomic(GridDesc<NO> gd, int64_t P, int64_t B, int K,
+                                                                T* __restrict__ out_dot,
+                                                                const T* __restrict__ points,
+                                                                const T* __restrict__ rot,
+                                                                const T* __restrict__ trans,
+                                                                const T* __restrict__ ow, const T* __restrict__ pw,
+                                                                JvpTangents<T> tan) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    const bool live = p < P;  // (no early return: the wave sums below need every lane of the wave)
+    const int lane = threadIdx.x & (kWave - 1);
+    T pt[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) pt[j] = T(0);
+    if (live) load_point<T, NI>(points, p, pt);
+    const T pwi = (live && pw) ? pw[p] : T(1);
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+        const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b);
+        int j0[NO];
+        T u[NO];
+        const bool ok = smooth_cell<T, NI, NO>(pt, ps, gd, j0, u) && live;
+        const uint64_t okm = __ballot(ok);
+        if (okm == 0) continue;  // (uniform)
+        // groups of accepted lanes with equal cells: masks gm*, first lanes gl*; `solo`: lanes on their own
+        uint64_t solo = okm, gm0 = 0, gm1 = 0, gm2 = 0, gm3 = 0;
+        int gl0 = 0, gl1 = 0, gl2 = 0, gl3 = 0, ng = 0;
+        {
+            bool run = ok && lane > 0 && __shfl_up((int)ok, 1, kWave) != 0;
+#pragma unroll
+            for (int d = 0; d < NO; ++d) run = run && j0[d] == __shfl_up(j0[d], 1, kWave);
+            if (__popcll(__ballot(run)) >= kSmJvpMinRun) {
+                uint64_t todo = okm;
+                for (int t = 0; t < kSmJvpTries && todo != 0 && ng < kSmJvpGroups; ++t) {
+                    const int lead = __ffsll((unsigned long long)todo) - 1;
+                    bool same = ok;
+#pragma unroll
+                    for (int d = 0; d < NO; ++d) same = same && j0[d] == __shfl(j0[d], lead, kWave);
+                    const uint64_t m = __ballot(same);
+                    todo &= ~m;
+                    if (__popcll(m) > 1) {
+                        solo &= ~m;
+                        if (ng == 0) { gm0 = m; gl0 = lead; }
+                        else if (ng == 1) { gm1 = m; gl1 = lead; }
+                        else if (ng == 2) { gm2 = m; gl2 = lead; }
+                        else { gm3 = m; gl3 = lead; }
+                        ++ng;
+                    }
+                }
+            }
+        }
+        const bool own = (solo >> lane) & 1;
+        const SmoothAxes<T, NO> ax = smooth_axes<T, NO>(j0, u, gd);
+        T dw[NO][3];
+#pragma unroll
+        for (int d = 0; d < NO; ++d) spline_derivatives<T>(u[d], dw[d]);
+        T* o = out_dot + b * K * gd.G;
+        for (int k = 0; k < K; ++k) {
+            const JvpPose<T, NI, NO> tp = load_jvp_pose<T, NI, NO>(tan.rot, tan.trans, tan.ow, (int64_t)k * B + b);
+            T pd[NI], pwd;
+            load_jvp_point<T, NI>(ok ? tan.points : nullptr, ok ? tan.pw : nullptr, (int64_t)k * P + p, pd, pwd);
+            T a, bc[NO];
+            jvp_coeffs<T, NI, NO>(pt, pwi, pd, pwd, ps, tp, gd, a, bc);
+            const SmoothJvpRows<T, NO> r = smooth_jvp_rows<T, NO>(a, bc, ax.w, dw);
+            T f0[3];
+#pragma unroll
+            for (int k0 = 0; k0 < 3; ++k0) f0[k0] = bc[0] * dw[0][k0];
+            T* ok_plane = o + (int64_t)k * gd.G;
+#pragma unroll
+            for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+                const bool in2 = NO == 3 ? ax.in[NO - 1][k2] : true;
+                const int off2 = NO == 3 ? ax.off[NO - 1][k2] : 0;
+#pragma unroll
+                for (int k1 = 0; k1 < 3; ++k1) {
+#pragma unroll
+                    for (int k0 = 0; k0 < 3; ++k0) {
+                        const bool in = ok && in2 && ax.in[1][k1] && ax.in[0][k0];
+                        T* addr = ok_plane + (off2 + ax.off[1][k1] + ax.off[0][k0]);
+                        const T dep = ax.w[0][k0] * r.X[k2][k1] + f0[k0] * r.Y[k2][k1];
+                        for (int g = 0; g < ng; ++g) {  // (uniform; none in a wave without runs)
+                            const uint64_t m = g == 0 ? gm0 : g == 1 ? gm1 : g == 2 ? gm2 : gm3;
+                            const int lead = g == 0 ? gl0 : g == 1 ? gl1 : g == 2 ? gl2 : gl3;
+                            const T s = wave_sum<T>(((m >> lane) & 1) ? dep : T(0));
+                            if (lane == lead && in) atomic_add<T>(addr, s);
+                        }
+                        if (own && in) atomic_add<T>(addr, dep);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Workgroup (tile, k) = (blockIdx.x, blockIdx.y): k_smooth_tile's walk over the tile's run of the sorted points,
+// its LDS array, clamped-centre rule and flush, with the deposit of tangent k in the place of the weight product.
+// Deposits have both signs; a cell whose sum is exactly 0 is skipped by the flush, which is right because the
+// plane holds the background tangent already.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_tile_jvp(GridDesc<NO> gd, SmoothTiles<NO> tl, int64_t P,
+                                                              int64_t B, int64_t b, int K, T* __restrict__ out_dot,
+                                                              const T* __restrict__ points,
+                                                              const T* __restrict__ rot, const T* __restrict__ trans,
+                                                              const T* __restrict__ ow, const T* __restrict__ pw,
+                                                              JvpTangents<T> tan, const uint32_t* __restrict__ start,
+                                                              const uint32_t* __restrict__ idx) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    constexpr int NC = smooth_lds_cells<NO>();
+    __shared__ double cells[NC];
+    uint32_t begin, end;
+    ord_cell_range(start, blockIdx.x, (uint32_t)P, begin, end);
+    if (begin >= end) return;  // (uniform: an empty tile adds nothing)
+    const int64_t k = blockIdx.y;
+    int org[NO];  // first cell of the tile
+    {
+        uint32_t t = blockIdx.x;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            org[d] = (int)(t % (uint32_t)tl.nt[d]) * SmoothTileShape<NO>::e[d];
+            t /= (uint32_t)tl.nt[d];
+        }
+    }
+    for (int i = threadIdx.x; i < NC; i += kSmBlock) cells[i] = 0.0;
+    __syncthreads();
+
+    const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b);
+    const JvpPose<T, NI, NO> tp = load_jvp_pose<T, NI, NO>(tan.rot, tan.trans, tan.ow, k * B + b);
+    for (uint32_t i = begin + threadIdx.x; i < end; i += kSmBlock) {
+        const uint32_t p = idx[i];
+        if ((int64_t)p >= P) continue;  // (never for an index k_smooth_keys wrote)
+        T pt[NI];
+        load_point<T, NI>(points, (int64_t)p, pt);
+        int j0[NO];
+        T u[NO];
+        if (!smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) continue;
+        T pd[NI], pwd;
+        load_jvp_point<T, NI>(tan.points, tan.pw, k * P + (int64_t)p, pd, pwd);
+        T a, bc[NO];
+        jvp_coeffs<T, NI, NO>(pt, pw ? pw[p] : T(1), pd, pwd, ps, tp, gd, a, bc);
+        // LDS cell l = (cell - org) + 1 per axis; only cells of the grid that lie on the tile + halo are added
+        T wt[NO][3], dw[NO][3];
+        int loff[NO][3];
+        bool in[NO][3];
+        int lstride = 1;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            spline_weights<T>(u[d], wt[d]);
+            spline_derivatives<T>(u[d], dw[d]);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int c = j0[d] + q - 1, l = c - org[d] + 1;
+                in[d][q] = c >= 0 && c < gd.n[d] && l >= 0 && l < SmoothTileShape<NO>::e[d] + 2;
+                loff[d][q] = in[d][q] ? l * lstride : 0;
+            }
+            lstride *= SmoothTileShape<NO>::e[d] + 2;
+        }
+        const SmoothJvpRows<T, NO> r = smooth_jvp_rows<T, NO>(a, bc, wt, dw);
+        T f0[3];
+#pragma unroll
+        for (int k0 = 0; k0 < 3; ++k0) f0[k0] = bc[0] * dw[0][k0];
+#pragma unroll
+        for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+            const bool in2 = NO == 3 ? in[NO - 1][k2] : true;
+            const int off2 = NO == 3 ? loff[NO - 1][k2] : 0;
+#pragma unroll
+            for (int k1 = 0; k1 < 3; ++k1) {
+#pragma unroll
+                for (int k0 = 0; k0 < 3; ++k0)
+                    if (in2 && in[1][k1] && in[0][k0])
+                        atomicAdd(&cells[off2 + loff[1][k1] + loff[0][k0]],
+                                  (double)(wt[0][k0] * r.X[k2][k1] + f0[k0] * r.Y[k2][k1]));
+            }
+        }
+    }
+    __syncthreads();
+
+    // flush: consecutive threads walk axis 0 of the tile + halo, so a wave's atomics cover rows of the plane
+    T* o = out_dot + (b * K + k) * gd.G;
+    for (int i = threadIdx.x; i < NC; i += kSmBlock) {
+        const double v = cells[i];
+        int rest = i, off = 0, stride = 1;
+        bool in_grid = true;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            const int ext = SmoothTileShape<NO>::e[d] + 2;
+            const int c = org[d] + (rest % ext) - 1;
+            rest /= ext;
+            in_grid = in_grid && c >= 0 && c < gd.n[d];
+            off += in_grid ? c * stride : 0;
+            stride *= gd.n[d];
+        }
+        if (in_grid && v != 0.0) atomic_add<T>(o + off, (T)v);
+    }
+}
+
 // ---------------------------------------------------------------- host
 int64_t smooth_tile_count(int n_out, const int64_t* grid, int64_t P) {
     if (P > (int64_t)0xfffffffeLL) return 0;
@@ -646,6 +886,63 @@ int smooth_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, 
 }
 
 template <typename T, int NI, int NO>
+int smooth_jvp_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
+                      const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    dim3 g((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)(B < 65535 ? B : 65535));
+    hipLaunchKernelGGL((k_smooth_jvp_atomic<T, NI, NO>), g, dim3(kSmBlock), 0, st, gd, P, B, K, out_dot, points, rot,
+                       trans, ow, pw, tan);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+// per pose: keys -> sort -> ranges as smooth_fwd_tiled (they depend on the primal only), then ONE launch over
+// (tiles, K): a binning serves all K tangents
+template <typename T, int NI, int NO>
+int smooth_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
+                     const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan,
+                     void* ws_, size_t ws_bytes) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const int64_t tiles = smooth_tile_count(NO, grid, P);
+    if (tiles == 0)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth DPR_ALGO_TILED: too many tiles for a 32-bit key or P > 2^32 - 2");
+    const SmoothPlan pl = smooth_plan(tiles, P);
+    if (!ws_ || ws_bytes < pl.total)
+        return fail(DPR_ERR_WORKSPACE, "smooth DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
+                    ws_ ? ws_bytes : (size_t)0);
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    const SmoothTiles<NO> tl = smooth_tiles<NO>(grid);
+    char* ws = (char*)ws_;
+    uint32_t* keys_in = (uint32_t*)(ws + pl.off_keys_in);
+    uint32_t* keys_out = (uint32_t*)(ws + pl.off_keys_out);
+    uint32_t* idx_in = (uint32_t*)(ws + pl.off_idx_in);
+    uint32_t* idx_out = (uint32_t*)(ws + pl.off_idx_out);
+    uint32_t* start = (uint32_t*)(ws + pl.off_start);
+    const int bits = ord_key_bits((uint64_t)tiles);
+    const dim3 blk(kSmBlock);
+    const dim3 pgrid((unsigned)((P + kSmBlock - 1) / kSmBlock));
+    const dim3 rgrid((unsigned)((tiles + 1 + kSmBlock - 1) / kSmBlock));
+    for (int64_t b = 0; b < B; ++b) {
+        hipLaunchKernelGGL((k_smooth_keys<T, NI, NO>), pgrid, blk, 0, st, gd, tl, P, b, points, rot, trans, keys_in,
+                           idx_in);
+        stage_mark(st);
+        DPR_HIP(radix_sort_pairs_u32(ws + pl.off_temp, pl.temp_bytes, keys_in, keys_out, idx_in, idx_out, (size_t)P,
+                                     0u, (unsigned)bits, st));
+        stage_mark(st);
+        hipLaunchKernelGGL(k_smooth_ranges, rgrid, blk, 0, st, (const uint32_t*)keys_out, (uint32_t)P,
+                           (uint64_t)(tiles + 1), bits, start);
+        stage_mark(st);
+        hipLaunchKernelGGL((k_smooth_tile_jvp<T, NI, NO>), dim3((unsigned)tiles, (unsigned)K), blk, 0, st, gd, tl, P,
+                           B, b, K, out_dot, points, rot, trans, ow, pw, tan, (const uint32_t*)start,
+                           (const uint32_t*)idx_out);
+        stage_mark(st);
+    }
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+template <typename T, int NI, int NO>
 int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* g,
                       const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts, T* d_rot,
                       T* d_trans, T* d_ow, T* d_pw, int poses_per_slice, int64_t slices) {
@@ -700,6 +997,11 @@ int sample_smooth_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
                                               const T*, const T*, const T*, const T*);                             \
     template int smooth_fwd_tiled<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, T*, const T*,  \
                                              const T*, const T*, const T*, const T*, void*, size_t);               \
+    template int smooth_jvp_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, int, T*,      \
+                                              const T*, const T*, const T*, const T*, const T*, JvpTangents<T>);   \
+    template int smooth_jvp_tiled<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, int, T*,       \
+                                             const T*, const T*, const T*, const T*, const T*, JvpTangents<T>,     \
+                                             void*, size_t);                                                       \
     template int smooth_bwd_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, const T*,     \
                                               const T*, const T*, const T*, const T*, const T*, T*, T*, T*, T*,    \
                                               T*, int, int64_t);

@@ -122,7 +122,9 @@ class _RasterSmoothFn(torch.autograd.Function):
     def forward(ctx, grid_size, algo, points, rotation, translation, background, out_weight, point_weight):
         out = raster_smooth(grid_size, _detach(points), _detach(rotation), _detach(translation),
                             _detach(background), _detach(out_weight), _detach(point_weight), algo=algo)
-        _save(ctx, (points, rotation, translation), (background, out_weight, point_weight))
+        saved = _save(ctx, (points, rotation, translation), (background, out_weight, point_weight))
+        ctx.save_for_forward(*saved)
+        ctx.grid_size, ctx.caller_algo = tuple(int(n) for n in grid_size), algo
         # the pullback has DPR_ALGO_ATOMIC only: a forward on "tiled" differentiates on "auto"
         ctx.algo = "auto" if algo == "tiled" else algo
         return out
@@ -136,11 +138,23 @@ class _RasterSmoothFn(torch.autograd.Function):
                                      point_weight_grad=bool(ctx.opt_is_tensor[2] and need[7]))
         return (None, None, *_cast_grads(need[2:], pb, (points, rotation, translation, *opt)))
 
+    @staticmethod
+    def jvp(ctx, _grid_t, _algo_t, points_t, rotation_t, translation_t, background_t, out_weight_t, point_weight_t):
+        from .smooth_jvp import raster_smooth_jvp  # (smooth_jvp imports this module)
+
+        (points, rotation, translation), opt = _restore(ctx, 3)
+        algo = ctx.caller_algo if ctx.caller_algo in ("atomic", "tiled") else "auto"
+        return raster_smooth_jvp(ctx.grid_size, _detach(points), _detach(rotation), _detach(translation),
+                                 *map(_detach, opt), points_dot=points_t, rotation_dot=rotation_t,
+                                 translation_dot=translation_t, background_dot=background_t,
+                                 out_weight_dot=out_weight_t, point_weight_dot=point_weight_t, algo=algo)
+
 
 def raster_smooth_ad(grid_size, points, rotation, translation, background=None, out_weight=None,
                      point_weight=None, *, algo: str = "auto") -> torch.Tensor:
     """Differentiable `raster_smooth` (torch autograd) in points, rotation, translation, background, out_weight
     and point_weight (whichever are tensors that require grad); the tangents are those of
-    `raster_pullback_smooth_`."""
+    `raster_pullback_smooth_`.  Forward mode (torch.autograd.forward_ad dual tensors, torch.func.jvp) goes through
+    `raster_smooth_jvp` with one tangent, on the caller's algorithm ("atomic" / "tiled") or AUTO."""
     return _RasterSmoothFn.apply(tuple(grid_size), algo, points, rotation, translation, background, out_weight,
                                  point_weight)

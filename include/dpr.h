@@ -266,6 +266,13 @@ extern "C" {
  *                        the background: rounding level, not
  *                        bit-reproducible
  *
+ *   smooth splat, forward mode (dpr_raster_smooth_jvp_ex_*, see SMOOTH SPLAT, FORWARD MODE below), out_dot:
+ *   DPR_ALGO_ATOMIC      global float atomics in T onto the background tangent, unordered: rounding level (lanes of
+ *                        a wave with the same centre cell are first added in T in a fixed order, one atomic per group)
+ *   DPR_ALGO_TILED       f64 LDS sums per (tile, tangent) in arrival order, rounded to T once per (tile, cell); a
+ *                        cell receives <= 3^N such partials as float atomics in T onto the background tangent:
+ *                        rounding level, not bit-reproducible
+ *
  * Note 1, pose slices.  A per-point kernel that would leave the device idle cuts the B poses into slices on
  * the second grid axis; every slice adds its share of ds_dpoints / ds_dpoint_weight with float atomics onto
  * zeroed buffers.  DPR_ALGO_ATOMIC and its channel form: fewer than 2048 blocks of 256 points (P <= 523 776)
@@ -957,6 +964,75 @@ int dpr_sample_smooth_pullback_ex_f64(void *stream, int algo, unsigned flags, in
                                       const double *translation, double *ds_dimage, double *ds_dpoints,
                                       double *ds_drotation, double *ds_dtranslation, void *workspace,
                                       size_t workspace_bytes);
+
+/* ---- SMOOTH SPLAT, FORWARD MODE: out_dot = J . v of dpr_raster_smooth_* for K = 1..16 tangents -----------------
+ * With coord_d, j0_d, u_d, w_d, w'_d and the acceptance rule of SMOOTH SPLAT (-1 <= coord_d < n_d + 1 on every axis,
+ * tested in floating point; NaN / Inf rejected), for tangent k, pose b and accepted point p:
+ *     cdot_n     = n_n / 2 * (sum_j Rdot_{k,b}[n, j] p_j + sum_j R_b[n, j] pdot_{k,p}[j] + tdot_{k,b}[n])
+ *     a          = owdot_{k,b} * pw_p + ow_b * pwdot_{k,p}
+ *     c          = ow_b * pw_p
+ *     deposit(s) = a * prod_d w_d(s_d) + c * sum_n cdot_n * w'_n(s_n) * prod_{d != n} w_d(s_d),  s in {-1, 0, +1}^n_out
+ *     out_dot[j0 + s, k, b] = bgdot_{k,b} + sum over (p, s) that land on the cell
+ * Target cells outside the grid are dropped one by one.  No cell is held fixed: `out` is C1 in every input, so this
+ * is the exact directional derivative, continuous across cell faces, and the exact transpose of
+ * dpr_raster_pullback_smooth_ex_*.  A rejected point deposits nothing and none of its tangents is read (NaN there
+ * leaves no trace).  out_weight / point_weight NULL = 1; the primal background does not enter.
+ * Layouts, as dpr_raster_jvp_ex_*: every tangent holds K copies of its primal's layout, tangent k at
+ * k * (primal size): points_dot K x P x n_in, rotation_dot K x B x (n_out x n_in column-major), translation_dot
+ * K x B x n_out, point_weight_dot K x P, background_dot and out_weight_dot K x B.  out_dot is the channel layout
+ * with C = K: plane (k, b) at (b * K + k) * G.  Any tangent may be NULL (= zero); with all of them NULL out_dot is
+ * zero-filled.  out_dot is overwritten.  (n_in, n_out): (2,2), (3,3) and (3,2).
+ * Algorithms (DPR_ALGO_CHUNKED, DPR_ALGO_ORDERED: DPR_ERR_UNSUPPORTED_ALGO).
+ *   DPR_ALGO_ATOMIC  background tangent fill, then one thread per point, pose loop inside: the cell, the weights and
+ *                    their derivatives once per accepted (point, pose), the K tangents a run-time loop of 3^N global
+ *                    float atomics each.  Lanes of a wave that share a centre cell share all 3^N addresses: where a
+ *                    wave holds runs of such lanes (a cloud with many points in a cell), up to four groups of equal
+ *                    cells add their deposits across the wave in a fixed order first and issue one atomic per
+ *                    (group, cell, tangent); every other lane issues its own.  Workspace 0.
+ *   DPR_ALGO_TILED   background tangent fill, then per pose the key, sort and start table of
+ *                    dpr_raster_smooth_ex_*(DPR_ALGO_TILED) ONCE -- they depend on the primal only -- and one launch
+ *                    of (tiles x K) workgroups: workgroup (tile, k) adds the deposits of tangent k of the tile's run
+ *                    of points into the LDS array of f64 cells (tile + halo) and adds every non-zero cell inside the
+ *                    grid onto plane (k, b) with one global atomic in T.  Workspace: that of
+ *                    dpr_raster_smooth_ex_*(DPR_ALGO_TILED) for (grid, P), independent of B and K; its LIMITS and
+ *                    COST apply.
+ * AUTO (dpr_resolve_algo_smooth_jvp), from the shape and K alone, never from the points: DPR_ALGO_TILED where
+ * P * K >= 100 000 for a 3-D grid and P * K >= 400 000 for a 2-D grid (and the LIMITS hold), DPR_ALGO_ATOMIC
+ * otherwise.  For K = 1 and a 3-D grid this is dpr_resolve_algo_smooth(DPR_OP_RASTER, .., P, 1), the rule this op
+ * started from; that threshold was measured for the smooth forward, and this op's own times
+ * (profiles/smooth_jvp_probe.txt, fp32, uniform clouds) moved it: the binning is paid once per pose whatever K, the
+ * atomics K times, so 1e5 points x 16 poses -> 128^2 is 1.6x faster TILED at K = 4 and 4.4x at K = 12 although the
+ * forward of that shape is faster ATOMIC.  Those two rows set the 2-D constant; between P * K = 1e5 and 4e5 nothing
+ * was measured.
+ * Summation order: the table in SUMMATION ORDER.  Both algorithms are at rounding level and agree at that level.
+ * Flags: KEEP / REUSE are refused (DPR_ERR_UNSUPPORTED_ALGO), the others accepted and ignored.
+ * P = 0 or B = 0: only the background tangent is written, DPR_OK.
+ * Errors (status, dpr_last_error text, nothing launched, out_dot untouched): a pair outside the three
+ * DPR_ERR_UNSUPPORTED_DIMS; a bad grid, negative P / B, K outside 1..16, a NULL required pointer (out_dot, points
+ * with P > 0, rotation, translation, grid), a misaligned data pointer DPR_ERR_INVALID_ARG; KEEP / REUSE,
+ * DPR_ALGO_CHUNKED / DPR_ALGO_ORDERED / an unknown algorithm and DPR_ALGO_TILED outside its LIMITS
+ * DPR_ERR_UNSUPPORTED_ALGO; a workspace smaller than dpr_workspace_bytes_smooth_jvp_ex_* or not 256-byte aligned
+ * DPR_ERR_WORKSPACE.  dpr_workspace_bytes_smooth_jvp_ex_* returns (size_t)-1 for every refused combination;
+ * dpr_resolve_algo_smooth_jvp a negative status. */
+int dpr_resolve_algo_smooth_jvp(int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B, int64_t K);
+size_t dpr_workspace_bytes_smooth_jvp_ex_f32(int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                                             int64_t P, int64_t B, int64_t K);
+size_t dpr_workspace_bytes_smooth_jvp_ex_f64(int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                                             int64_t P, int64_t B, int64_t K);
+int dpr_raster_smooth_jvp_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                                 int64_t P, int64_t B, int64_t K, float *out_dot, const float *points,
+                                 const float *rotation, const float *translation, const float *out_weight,
+                                 const float *point_weight, const float *points_dot, const float *rotation_dot,
+                                 const float *translation_dot, const float *background_dot,
+                                 const float *out_weight_dot, const float *point_weight_dot, void *workspace,
+                                 size_t workspace_bytes);
+int dpr_raster_smooth_jvp_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                                 int64_t P, int64_t B, int64_t K, double *out_dot, const double *points,
+                                 const double *rotation, const double *translation, const double *out_weight,
+                                 const double *point_weight, const double *points_dot, const double *rotation_dot,
+                                 const double *translation_dot, const double *background_dot,
+                                 const double *out_weight_dot, const double *point_weight_dot, void *workspace,
+                                 size_t workspace_bytes);
 
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
