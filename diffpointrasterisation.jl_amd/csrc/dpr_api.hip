@@ -1,4 +1,7 @@
-// C-ABI entry points of libdpr (declared in include/dpr.h) and host-side dispatch.
+// C-ABI entry points of libdpr (declared in include/dpr.h) and host-side dispatch: the core.  Raster, pullback and
+// residual pullback, the AUTO cost model, the error and stage-timing state, and the helpers of dpr_host.h that the
+// other op families share.  Every other family has its own unit: dpr_api_channels.hip, dpr_api_sample.hip,
+// dpr_api_jvp.hip, dpr_api_clouds.hip, dpr_api_smooth.hip.
 // Host checks mirror the reference's @argcheck's (src/raster.jl:14-23,
 // ext/DiffPointRasterisationCUDAExt.jl:246-262) but report through status codes.
 #include <hip/hip_runtime.h>
@@ -7,19 +10,11 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <initializer_list>
 #include <string>
-#include <type_traits>
 
-#include "../../include/dpr.h"
+#include "dpr_host.h"
 #include "dpr_kernels_atomic.h"
-#include "dpr_kernels_channels.h"
-#include "dpr_kernels_clouds.h"
-#include "dpr_kernels_jvp.h"
-#include "dpr_kernels_sample.h"
 #include "dpr_ordered.h"
-#include "dpr_smooth.h"
-#include "dpr_tiled.h"
 
 namespace dpr {
 
@@ -200,35 +195,10 @@ constexpr int kMaxDim = 4;
 static bool dims_supported(int n_in, int n_out) {
     return n_out >= 1 && n_out <= kMaxDim && n_in >= 1 && n_in <= kMaxDim;
 }
-// (constexpr: `if constexpr` keeps the other algorithms' templates to these three pairs)
-static constexpr bool dims_have_all_algos(int n_in, int n_out) {
-    return (n_in == 2 && n_out == 2) || (n_in == 3 && n_out == 3) || (n_in == 3 && n_out == 2);
-}
+// (dims_have_all_algos, the three pairs with every algorithm, and with_dims: dpr_host.h)
 
-// f(std::integral_constant<int, NI>{}, std::integral_constant<int, NO>{}) for the runtime pair: the one place
-// that maps (n_in, n_out) to template arguments.  Callers have passed check_common, so the pair is supported.
-template <int NI, class F> static int with_out_dim(int n_out, F& f) {
-    using NIc = std::integral_constant<int, NI>;
-    switch (n_out) {
-        case 1: return f(NIc{}, std::integral_constant<int, 1>{});
-        case 2: return f(NIc{}, std::integral_constant<int, 2>{});
-        case 3: return f(NIc{}, std::integral_constant<int, 3>{});
-        case 4: return f(NIc{}, std::integral_constant<int, 4>{});
-    }
-    return fail(DPR_ERR_UNSUPPORTED_DIMS, "unsupported (n_in, n_out) = (%d, %d)", NI, n_out);
-}
-template <class F> static int with_dims(int n_in, int n_out, F&& f) {
-    switch (n_in) {
-        case 1: return with_out_dim<1>(n_out, f);
-        case 2: return with_out_dim<2>(n_out, f);
-        case 3: return with_out_dim<3>(n_out, f);
-        case 4: return with_out_dim<4>(n_out, f);
-    }
-    return fail(DPR_ERR_UNSUPPORTED_DIMS, "unsupported (n_in, n_out) = (%d, %d)", n_in, n_out);
-}
-
-static int check_common(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
-                        int64_t* G_out) {
+int check_common(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
+                 int64_t* G_out) {
     if (!dims_supported(n_in, n_out))
         return fail(DPR_ERR_UNSUPPORTED_DIMS,
                     "unsupported (n_in, n_out) = (%d, %d); supported: 1 <= n_in, n_out <= 4", n_in,
@@ -258,8 +228,8 @@ static int check_common(int n_in, int n_out, const int64_t* grid, int64_t P, int
 // op == DPR_OP_RESIDUAL_PULLBACK: a pullback that forms its sensitivity from (out, target).  The 3-D
 // DPR_ALGO_CHUNKED pullback (direct gathers) has no such variant, so AUTO never picks it for this op -- the
 // rules that would are skipped and a KEEP / REUSE pair keeps its flags (the tiled pair shares as usual).
-static int resolve_algo(int algo, int op, int n_in, int n_out, const int64_t* grid, int64_t P,
-                        int64_t B, int64_t G, unsigned* flags) {
+int resolve_algo(int algo, int op, int n_in, int n_out, const int64_t* grid, int64_t P,
+                 int64_t B, int64_t G, unsigned* flags) {
     const bool residual = op == DPR_OP_RESIDUAL_PULLBACK;
     if (residual) op = DPR_OP_PULLBACK;
     if (!dims_have_all_algos(n_in, n_out)) {
@@ -338,7 +308,7 @@ void stage_mark(hipStream_t st) {
 // ---------------------------------------------------------------- launch helpers
 // Pose slices (grid.y) of the per-point kernels: enough blocks to fill 256 CUs x 8 when P is small.
 // Returns the poses per slice; *slices_out: the slices that cover the B poses.
-static int pose_slices(int64_t P, int64_t B, int64_t* slices_out) {
+int pose_slices(int64_t P, int64_t B, int64_t* slices_out) {
     const int64_t pblocks = (P + kBlock - 1) / kBlock;
     int64_t slices = 1;
     if (pblocks < 2048 && B > 1) {
@@ -353,7 +323,7 @@ static int pose_slices(int64_t P, int64_t B, int64_t* slices_out) {
 
 // k_fill_background: plane k of `out` (G voxels each) = bg[k] (0 without bg), in launches of at most 65535 planes
 template <typename T>
-static void fill_background(hipStream_t st, T* out, int64_t G, int64_t planes, const T* bg) {
+void fill_background(hipStream_t st, T* out, int64_t G, int64_t planes, const T* bg) {
     const int64_t want = (G + kBlock - 1) / kBlock;
     dim3 g((unsigned)(want < 4096 ? want : 4096), 1);
     for (int64_t k0 = 0; k0 < planes; k0 += 65535) {
@@ -365,7 +335,7 @@ static void fill_background(hipStream_t st, T* out, int64_t G, int64_t planes, c
 
 // k_grid_sum: d_bg[k] = the sum of plane k of `g` (the residual's planes alike), in launches of at most 65535 planes
 template <typename T>
-static void grid_sum(hipStream_t st, const T* g, int64_t G, int64_t planes, T* d_bg, Residual<T> rs) {
+void grid_sum(hipStream_t st, const T* g, int64_t G, int64_t planes, T* d_bg, Residual<T> rs) {
     for (int64_t k0 = 0; k0 < planes; k0 += 65535) {
         const int64_t nk = (planes - k0 < 65535) ? planes - k0 : 65535;
         Residual<T> rk = rs;
@@ -375,6 +345,11 @@ static void grid_sum(hipStream_t st, const T* g, int64_t G, int64_t planes, T* d
                            g + k0 * G, G, d_bg + k0, rk);
     }
 }
+
+template void fill_background<float>(hipStream_t, float*, int64_t, int64_t, const float*);
+template void fill_background<double>(hipStream_t, double*, int64_t, int64_t, const double*);
+template void grid_sum<float>(hipStream_t, const float*, int64_t, int64_t, float*, Residual<float>);
+template void grid_sum<double>(hipStream_t, const double*, int64_t, int64_t, double*, Residual<double>);
 
 // ---------------------------------------------------------------- forward
 template <typename T, int NI, int NO>
@@ -391,19 +366,6 @@ static int raster_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t
     }
     stage_mark(st);
     DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-
-// The kernels move records as 16/32-byte vectors and scalars as T: a misaligned pointer
-// would fault on the device, so it is refused here.
-template <typename T>
-static int check_alignment(const void* ws, std::initializer_list<const void*> data) {
-    if (ws && ((uintptr_t)ws & 255))
-        return fail(DPR_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    uintptr_t bits = 0;
-    for (const void* p : data) bits |= (uintptr_t)p;  // NULL (optional argument) adds nothing
-    if (bits & (sizeof(T) - 1))
-        return fail(DPR_ERR_INVALID_ARG, "a data pointer is not aligned to its element type");
     return DPR_OK;
 }
 
@@ -746,1166 +708,6 @@ static size_t workspace_impl(int op, int algo, unsigned flags, int n_in, int n_o
     return (size_t)-1;
 }
 
-// ---------------------------------------------------------------- C weight channels
-// dpr_raster_channels_ex_* / dpr_raster_pullback_channels_ex_* (include/dpr.h, "MULTI-CHANNEL").
-// Forward: DPR_ALGO_ATOMIC for every (n_in, n_out); DPR_ALGO_TILED for (2,2), (3,3), (3,2) on the
-// per-pose binning path of single-slab grids.  Pullback: DPR_ALGO_ATOMIC.
-static int check_channels(int64_t C, unsigned flags, bool residual = false) {
-    if (C < 1 || C > kMaxChannels)
-        return fail(DPR_ERR_INVALID_ARG, "channels C = %lld out of range [1, %d]", (long long)C, kMaxChannels);
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "the channel entry points keep / reuse no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    if (residual)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the channel entry points have no residual pullback");
-    return DPR_OK;
-}
-
-// AUTO: the forward takes DPR_ALGO_TILED where the single-channel rule prefers it for the shape and the
-// channel path supports it; everything else (and every pullback) runs on DPR_ALGO_ATOMIC
-static int resolve_algo_channels(int algo, int op, int n_in, int n_out, const int64_t* grid, int64_t P,
-                                 int64_t B, int64_t G) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    if (op == DPR_OP_RASTER && dims_have_all_algos(n_in, n_out) && tiled_channels_supported(n_out, grid, P) &&
-        tiled_preferred(DPR_OP_RASTER, n_out, grid, P, B, G))
-        return DPR_ALGO_TILED;
-    return DPR_ALGO_ATOMIC;
-}
-
-template <typename T, int NI, int NO>
-static int raster_atomic_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C,
-                                  T* out, const T* points, const T* rot, const T* trans, const T* bg,
-                                  const T* ow, const T* pw) {
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    // B * C planes, plane k = b * C + c, background[k] (C x B, channel fastest)
-    fill_background(st, out, G, B * C, bg);
-    stage_mark(st);
-    if (P > 0) {
-        dim3 g((unsigned)((P + kBlock - 1) / kBlock), (unsigned)(B < 65535 ? B : 65535));
-        if (C <= 4)
-            hipLaunchKernelGGL((k_fwd_atomic_ch<T, NI, NO, 4>), g, dim3(kBlock), 0, st, gd, P, B, C, out, points,
-                               rot, trans, ow, pw);
-        else
-            hipLaunchKernelGGL((k_fwd_atomic_ch<T, NI, NO, kMaxChannels>), g, dim3(kBlock), 0, st, gd, P, B, C,
-                               out, points, rot, trans, ow, pw);
-    }
-    stage_mark(st);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-
-template <typename T>
-static int raster_channels_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                int64_t P, int64_t B, int64_t C, T* out, const T* points, const T* rot,
-                                const T* trans, const T* bg, const T* ow, const T* pw, void* ws,
-                                size_t ws_bytes) {
-    int64_t G = 0;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_channels(C, flags)) return rc;
-    if (B == 0) return DPR_OK;
-    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
-    if (G * C * B / B != G * C || G * C > ((int64_t)1 << 62) / (B > 0 ? B : 1))
-        return fail(DPR_ERR_INVALID_ARG, "output too large");
-    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    algo = resolve_algo_channels(algo, DPR_OP_RASTER, n_in, n_out, grid, P, B, G);
-    if (algo == DPR_ALGO_TILED && !dims_have_all_algos(n_in, n_out))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only", n_in, n_out);
-    if (algo == DPR_ALGO_TILED && !tiled_channels_supported(n_out, grid, P))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "DPR_ALGO_TILED with channels: per-pose binning of single-slab grids and P < 2^32 only");
-    if (algo != DPR_ALGO_ATOMIC && algo != DPR_ALGO_TILED)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the channel forward runs on DPR_ALGO_ATOMIC or DPR_ALGO_TILED "
-                                              "(algorithm %d)", algo);
-    stage_mark(st);
-    const int c = (int)C;
-    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        // (algo is ATOMIC, or TILED on a pair that has it)
-        if constexpr (dims_have_all_algos(NI, NO)) {
-            if (algo == DPR_ALGO_TILED)
-                return raster_tiled_channels<T, NI, NO>(st, grid, G, P, B, c, out, points, rot, trans, bg, ow, pw,
-                                                        ws, ws_bytes);
-        }
-        return raster_atomic_channels<T, NI, NO>(st, grid, G, P, B, c, out, points, rot, trans, bg, ow, pw);
-    });
-}
-
-template <typename T, int NI, int NO>
-static int pullback_atomic_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C,
-                                    const T* g, const T* points, const T* rot, const T* trans, const T* ow,
-                                    const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw) {
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    const int64_t planes = B * C;
-    DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * NO * NI), st));
-    DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * NO), st));
-    DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
-    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)planes, st));
-    // ds_dbackground[c, b] = sum of plane b * C + c: the single-channel grid sum over B * C planes
-    grid_sum(st, g, G, planes, d_bg, Residual<T>{nullptr, T(0), nullptr});
-    stage_mark(st);
-    if (P > 0) {
-        const int64_t pblocks = (P + kBlock - 1) / kBlock;
-        int64_t slices = 1;
-        const int poses_per_slice = pose_slices(P, B, &slices);
-        const int accumulate = slices > 1;
-        if (accumulate) {
-            DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
-            if (d_pw) DPR_HIP(hipMemsetAsync(d_pw, 0, sizeof(T) * (size_t)(P * C), st));
-        }
-        dim3 gg((unsigned)pblocks, (unsigned)slices);
-        if (C <= 4)
-            hipLaunchKernelGGL((k_bwd_gather_ch<T, NI, NO, 4>), gg, dim3(kBlock), 0, st, gd, P, B, C, g, points,
-                               rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice, accumulate);
-        else
-            hipLaunchKernelGGL((k_bwd_gather_ch<T, NI, NO, kMaxChannels>), gg, dim3(kBlock), 0, st, gd, P, B, C,
-                               g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice,
-                               accumulate);
-    }
-    stage_mark(st);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-
-template <typename T>
-static int pullback_channels_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
-                                  const int64_t* grid, int64_t P, int64_t B, int64_t C, const T* g,
-                                  const T* points, const T* rot, const T* trans, const T* ow, const T* pw,
-                                  T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw, void* ws,
-                                  size_t ws_bytes) {
-    (void)ws_bytes;
-    int64_t G = 0;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_channels(C, flags)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
-    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
-        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    algo = resolve_algo_channels(algo, DPR_OP_PULLBACK, n_in, n_out, grid, P, B, G);
-    if (algo != DPR_ALGO_ATOMIC)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the channel pullback runs on DPR_ALGO_ATOMIC only (algorithm %d)",
-                    algo);
-    if (B == 0) {
-        if (P > 0) {
-            DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * n_in), st));
-            if (d_pw) DPR_HIP(hipMemsetAsync(d_pw, 0, sizeof(T) * (size_t)(P * C), st));
-        }
-        return DPR_OK;
-    }
-    if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (!d_rot || !d_trans || !d_bg || !d_ow)
-        return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
-    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
-        return rc;
-    stage_mark(st);
-    const int c = (int)C;
-    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        return pullback_atomic_channels<T, decltype(ni)::value, decltype(no)::value>(
-            st, grid, G, P, B, c, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw);
-    });
-}
-
-template <typename T>
-static size_t workspace_channels_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                      int64_t P, int64_t B, int64_t C) {
-    int64_t G = 0;
-    if (check_common(n_in, n_out, grid, P, B, &G)) return (size_t)-1;
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK) {
-        fail(op == DPR_OP_RESIDUAL_PULLBACK ? DPR_ERR_UNSUPPORTED_ALGO : DPR_ERR_INVALID_ARG,
-             op == DPR_OP_RESIDUAL_PULLBACK ? "the channel entry points have no residual pullback" : "unknown op %d",
-             op);
-        return (size_t)-1;
-    }
-    if (check_channels(C, flags)) return (size_t)-1;
-    algo = resolve_algo_channels(algo, op, n_in, n_out, grid, P, B, G);
-    if (algo == DPR_ALGO_ATOMIC) return 0;
-    if (op == DPR_OP_RASTER && algo == DPR_ALGO_TILED && dims_have_all_algos(n_in, n_out)) {
-        const size_t n = tiled_channels_workspace_bytes(sizeof(T), n_in, n_out, grid, P, B, (int)C);
-        if (n == (size_t)-1)
-            fail(DPR_ERR_UNSUPPORTED_ALGO,
-                 "DPR_ALGO_TILED with channels: per-pose binning of single-slab grids and P < 2^32 only");
-        return n;
-    }
-    fail(DPR_ERR_UNSUPPORTED_ALGO, "algorithm %d has no channel %s", algo, op == DPR_OP_RASTER ? "forward" : "pullback");
-    return (size_t)-1;
-}
-
-// ---------------------------------------------------------------- point sampling
-// dpr_sample_ex_* / dpr_sample_pullback_ex_* (include/dpr.h, "SAMPLING").  Forward: k_sample_fwd
-// (DPR_ALGO_ATOMIC) for every (n_in, n_out).  Pullback: DPR_ALGO_ATOMIC, the fused k_sample_bwd with image
-// atomics; DPR_ALGO_TILED for (2,2), (3,3), (3,2): k_sample_bwd without the image atomics, then ds_dimage pose
-// by pose from the tiled forward (raster_tiled with B = 1, point weights ds_dvalues[:, b]).
-static int check_sample_op(int op, unsigned flags) {
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
-        return fail(DPR_ERR_INVALID_ARG, "sampling: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "sampling keeps / reuses no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    return DPR_OK;
-}
-
-// AUTO: the pullback takes DPR_ALGO_TILED where the single-pose forward of the same shape would
-// (dpr_resolve_algo(DPR_OP_RASTER, .., P, 1)), DPR_ALGO_ATOMIC otherwise; the forward is always ATOMIC
-static int resolve_algo_sample(int algo, int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t G) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    if (op == DPR_OP_PULLBACK && dims_have_all_algos(n_in, n_out)) {
-        unsigned f = 0;
-        if (resolve_algo(DPR_ALGO_AUTO, DPR_OP_RASTER, n_in, n_out, grid, P, 1, G, &f) == DPR_ALGO_TILED)
-            return DPR_ALGO_TILED;
-    }
-    return DPR_ALGO_ATOMIC;
-}
-
-// the pullback's ds_dimage on DPR_ALGO_TILED: one single-pose tiled forward per pose
-static size_t sample_tiled_workspace_bytes(size_t elem, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                           int64_t P) {
-    return tiled_workspace_bytes(elem, DPR_OP_RASTER, flags & DPR_FLAG_COHERENT_POINTS, n_in, n_out, grid, P, 1);
-}
-
-static int check_sample_sizes(int64_t P, int64_t B, int64_t G) {
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
-    if (B > 0 && (P > ((int64_t)1 << 62) / B || G > ((int64_t)1 << 62) / B))
-        return fail(DPR_ERR_INVALID_ARG, "P * B or the image (G * B) too large");
-    if (B > (int64_t)65535 * 0x7fffffff) return fail(DPR_ERR_INVALID_ARG, "B too large");
-    return DPR_OK;
-}
-
-template <typename T, int NI, int NO>
-static int sample_direct(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* values,
-                         const T* image, const T* points, const T* rot, const T* trans) {
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    int64_t slices = 1;
-    const int pps = pose_slices(P, B, &slices);
-    dim3 gg((unsigned)((P + kBlock - 1) / kBlock), (unsigned)slices);
-    hipLaunchKernelGGL((k_sample_fwd<T, NI, NO>), gg, dim3(kBlock), 0, st, gd, P, B, values, image, points, rot,
-                       trans, pps);
-    stage_mark(st);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-
-template <typename T>
-static int sample_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                       int64_t B, T* values, const T* image, const T* points, const T* rot, const T* trans,
-                       void* ws, size_t ws_bytes) {
-    (void)ws_bytes;
-    int64_t G = 0;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_sample_op(DPR_OP_RASTER, flags)) return rc;
-    algo = resolve_algo_sample(algo, DPR_OP_RASTER, n_in, n_out, grid, P, G);
-    if (algo != DPR_ALGO_ATOMIC)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the sampling forward runs on DPR_ALGO_ATOMIC only (algorithm %d)",
-                    algo);
-    if (int rc = check_sample_sizes(P, B, G)) return rc;
-    if (P == 0 || B == 0) return DPR_OK;
-    if (!values) return fail(DPR_ERR_INVALID_ARG, "values is NULL");
-    if (!image) return fail(DPR_ERR_INVALID_ARG, "image is NULL");
-    if (!points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (int rc = check_alignment<T>(ws, {values, image, points, rot, trans})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        return sample_direct<T, decltype(ni)::value, decltype(no)::value>(st, grid, G, P, B, values, image, points,
-                                                                          rot, trans);
-    });
-}
-
-template <typename T, int NI, int NO>
-static int sample_pullback_run(hipStream_t st, int algo, unsigned flags, const int64_t* grid, int64_t G, int64_t P,
-                               int64_t B, const T* dv, const T* image, const T* points, const T* rot,
-                               const T* trans, T* d_img, T* d_pts, T* d_rot, T* d_trans, void* ws,
-                               size_t ws_bytes) {
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    const bool tiled = algo == DPR_ALGO_TILED;
-    if (d_rot) DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * NO * NI), st));
-    if (d_trans) DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * NO), st));
-    if (d_img && (!tiled || P == 0)) DPR_HIP(hipMemsetAsync(d_img, 0, sizeof(T) * (size_t)(B * G), st));
-    if (d_pts && B == 0) DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
-    if (P == 0 || B == 0) return DPR_OK;
-    T* const kernel_img = tiled ? nullptr : d_img;
-    if (kernel_img || d_pts || d_rot || d_trans) {
-        int64_t slices = 1;
-        const int pps = pose_slices(P, B, &slices);
-        const int accumulate = slices > 1;
-        if (accumulate && d_pts) DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
-        dim3 gg((unsigned)((P + kBlock - 1) / kBlock), (unsigned)slices);
-        hipLaunchKernelGGL((k_sample_bwd<T, NI, NO>), gg, dim3(kBlock), 0, st, gd, P, B, dv, image, points, rot,
-                           trans, kernel_img, d_pts, d_rot, d_trans, pps, accumulate);
-        DPR_HIP(hipGetLastError());
-    }
-    stage_mark(st);
-    if (tiled && d_img) {
-        if constexpr (dims_have_all_algos(NI, NO)) {
-            // pose b: the single-pose tiled forward of weights ds_dvalues[:, b] (a contiguous column),
-            // background 0, out_weight 1 -- plane b is what dpr_raster_ex_*(DPR_ALGO_TILED) returns for them
-            for (int64_t b = 0; b < B; ++b)
-                if (int rc = raster_tiled<T, NI, NO>(st, flags & DPR_FLAG_COHERENT_POINTS, grid, G, P, 1,
-                                                     d_img + b * G, points, rot + b * (NO * NI), trans + b * NO,
-                                                     nullptr, nullptr, dv + b * P, ws, ws_bytes))
-                    return rc;
-        } else {
-            return fail(DPR_ERR_UNSUPPORTED_ALGO, "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only", NI, NO);
-        }
-    }
-    return DPR_OK;
-}
-
-template <typename T>
-static int sample_pullback_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                int64_t P, int64_t B, const T* dv, const T* image, const T* points,
-                                const T* rot, const T* trans, T* d_img, T* d_pts, T* d_rot, T* d_trans,
-                                void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_sample_op(DPR_OP_PULLBACK, flags)) return rc;
-    if (!d_img && !d_pts && !d_rot && !d_trans)
-        return fail(DPR_ERR_INVALID_ARG, "sampling pullback: every output is NULL");
-    algo = resolve_algo_sample(algo, DPR_OP_PULLBACK, n_in, n_out, grid, P, G);
-    if (algo != DPR_ALGO_ATOMIC && algo != DPR_ALGO_TILED)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "the sampling pullback runs on DPR_ALGO_ATOMIC or DPR_ALGO_TILED (algorithm %d)", algo);
-    if (algo == DPR_ALGO_TILED) {
-        if (!dims_have_all_algos(n_in, n_out))
-            return fail(DPR_ERR_UNSUPPORTED_ALGO, "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only", n_in,
-                        n_out);
-        const size_t need = sample_tiled_workspace_bytes(sizeof(T), flags, n_in, n_out, grid, P);
-        if (need == (size_t)-1)
-            return fail(DPR_ERR_UNSUPPORTED_ALGO, "DPR_ALGO_TILED: grid needs too many tiles or P >= 2^32");
-        if (d_img && P > 0 && B > 0 && (!ws || ws_bytes < need))
-            return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_TILED sampling pullback needs %zu workspace bytes, got %zu",
-                        need, ws ? ws_bytes : (size_t)0);
-    }
-    if (int rc = check_sample_sizes(P, B, G)) return rc;
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && B > 0) {
-        if (!dv) return fail(DPR_ERR_INVALID_ARG, "ds_dvalues is NULL");
-        if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-        if ((d_pts || d_rot || d_trans) && !image)
-            return fail(DPR_ERR_INVALID_ARG, "image is NULL (needed for ds_dpoints / ds_drotation / ds_dtranslation)");
-    }
-    if (int rc = check_alignment<T>(ws, {dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        return sample_pullback_run<T, decltype(ni)::value, decltype(no)::value>(
-            st, algo, flags, grid, G, P, B, dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans, ws, ws_bytes);
-    });
-}
-
-template <typename T>
-static size_t workspace_sample_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                    int64_t P, int64_t B) {
-    int64_t G = 0;
-    if (check_common(n_in, n_out, grid, P, B, &G)) return (size_t)-1;
-    if (check_sample_op(op, flags)) return (size_t)-1;
-    algo = resolve_algo_sample(algo, op, n_in, n_out, grid, P, G);
-    if (algo == DPR_ALGO_ATOMIC) return 0;
-    if (op == DPR_OP_PULLBACK && algo == DPR_ALGO_TILED && dims_have_all_algos(n_in, n_out)) {
-        const size_t n = sample_tiled_workspace_bytes(sizeof(T), flags, n_in, n_out, grid, P);
-        if (n == (size_t)-1)
-            fail(DPR_ERR_UNSUPPORTED_ALGO, "DPR_ALGO_TILED: grid needs too many tiles or P >= 2^32");
-        return n;
-    }
-    fail(DPR_ERR_UNSUPPORTED_ALGO, "algorithm %d has no sampling %s", algo, op == DPR_OP_RASTER ? "forward" : "pullback");
-    return (size_t)-1;
-}
-
-// ---------------------------------------------------------------- forward-mode derivative
-// dpr_raster_jvp_ex_* (include/dpr.h, "FORWARD-MODE DERIVATIVE").  DPR_ALGO_ATOMIC: k_jvp_fill, then k_jvp_atomic,
-// every (n_in, n_out).  DPR_ALGO_TILED for (2,2), (3,3), (3,2) on single-slab grids: raster_tiled_jvp.
-static int check_jvp(int64_t K, unsigned flags) {
-    if (K < 1 || K > kMaxTangents)
-        return fail(DPR_ERR_INVALID_ARG, "tangents K = %lld out of range [1, %d]", (long long)K, kMaxTangents);
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "the JVP keeps / reuses no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    return DPR_OK;
-}
-
-// AUTO: DPR_ALGO_TILED where the pair and the grid support it and the single-pose forward of the shape would take
-// it (dpr_resolve_algo(DPR_OP_RASTER, .., P, 1)), DPR_ALGO_ATOMIC otherwise
-static int resolve_algo_jvp(int algo, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t G) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    if (dims_have_all_algos(n_in, n_out) && tiled_channels_supported(n_out, grid, P)) {
-        unsigned f = 0;
-        if (resolve_algo(DPR_ALGO_AUTO, DPR_OP_RASTER, n_in, n_out, grid, P, 1, G, &f) == DPR_ALGO_TILED)
-            return DPR_ALGO_TILED;
-    }
-    return DPR_ALGO_ATOMIC;
-}
-
-// workspace of an algorithm that is not AUTO, or (size_t)-1 with the error recorded
-static size_t jvp_workspace_bytes(size_t elem, int algo, int n_in, int n_out, const int64_t* grid, int64_t P) {
-    if (algo == DPR_ALGO_ATOMIC) return 0;
-    if (algo == DPR_ALGO_TILED) {
-        if (!dims_have_all_algos(n_in, n_out)) {
-            fail(DPR_ERR_UNSUPPORTED_ALGO, "(n_in, n_out) = (%d, %d): the JVP runs on DPR_ALGO_ATOMIC only", n_in,
-                 n_out);
-            return (size_t)-1;
-        }
-        const size_t n = tiled_jvp_workspace_bytes(elem, n_in, n_out, grid, P);
-        if (n == (size_t)-1)
-            fail(DPR_ERR_UNSUPPORTED_ALGO, "DPR_ALGO_TILED JVP: per-pose binning of single-slab grids and P < 2^32 only");
-        return n;
-    }
-    fail(DPR_ERR_UNSUPPORTED_ALGO, "the JVP runs on DPR_ALGO_ATOMIC or DPR_ALGO_TILED (algorithm %d)", algo);
-    return (size_t)-1;
-}
-
-template <typename T, int NI, int NO>
-static int raster_jvp_run(hipStream_t st, int algo, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K,
-                          T* out_dot, const T* points, const T* rot, const T* trans, const T* ow, const T* pw,
-                          JvpTangents<T> tan, const T* bg_dot, void* ws, size_t ws_bytes) {
-    const bool any = tan.points || tan.rot || tan.trans || tan.ow || tan.pw;
-    if (algo == DPR_ALGO_TILED && P > 0 && any) {
-        if constexpr (dims_have_all_algos(NI, NO))
-            return raster_tiled_jvp<T, NI, NO>(st, grid, G, P, B, K, out_dot, points, rot, trans, ow, pw, tan,
-                                               bg_dot, ws, ws_bytes);
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only", NI, NO);
-    }
-    // the background tangent (or 0) into every plane; then the deposits, where any other tangent is given
-    const int64_t planes = B * K;
-    const int64_t want = (G + kBlock - 1) / kBlock;
-    dim3 g((unsigned)(want < 4096 ? want : 4096), 1);
-    for (int64_t q0 = 0; q0 < planes; q0 += 65535) {
-        const int64_t nq = (planes - q0 < 65535) ? planes - q0 : 65535;
-        g.y = (unsigned)nq;
-        hipLaunchKernelGGL(k_jvp_fill<T>, g, dim3(kBlock), 0, st, out_dot, G, K, B, q0, bg_dot);
-    }
-    stage_mark(st);
-    if (P > 0 && any) {
-        const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-        int64_t slices = 1;
-        const int pps = pose_slices(P, B, &slices);
-        dim3 gg((unsigned)((P + kBlock - 1) / kBlock), (unsigned)slices);
-        hipLaunchKernelGGL((k_jvp_atomic<T, NI, NO>), gg, dim3(kBlock), 0, st, gd, P, B, K, out_dot, points, rot,
-                           trans, ow, pw, tan, pps);
-        stage_mark(st);
-    }
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-
-template <typename T>
-static int raster_jvp_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                           int64_t P, int64_t B, int64_t K, T* out_dot, const T* points, const T* rot,
-                           const T* trans, const T* ow, const T* pw, JvpTangents<T> tan, const T* bg_dot, void* ws,
-                           size_t ws_bytes) {
-    int64_t G = 0;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_jvp(K, flags)) return rc;
-    algo = resolve_algo_jvp(algo, n_in, n_out, grid, P, G);
-    const size_t need = jvp_workspace_bytes(sizeof(T), algo, n_in, n_out, grid, P);
-    if (need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;  // (the message is recorded)
-    if (B == 0) return DPR_OK;
-    if (!out_dot) return fail(DPR_ERR_INVALID_ARG, "out_dot is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (int rc = check_sample_sizes(P, B, G)) return rc;
-    if (G * K > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "output too large");
-    if (need > 0 && P > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_TILED JVP needs %zu workspace bytes, got %zu", need,
-                    ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out_dot, points, rot, trans, ow, pw, tan.points, tan.rot, tan.trans, tan.ow,
-                                         tan.pw, bg_dot}))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    const int k = (int)K;
-    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        return raster_jvp_run<T, decltype(ni)::value, decltype(no)::value>(st, algo, grid, G, P, B, k, out_dot, points,
-                                                                           rot, trans, ow, pw, tan, bg_dot, ws,
-                                                                           ws_bytes);
-    });
-}
-
-template <typename T>
-static size_t workspace_jvp_impl(int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                                 int64_t B, int64_t K) {
-    int64_t G = 0;
-    if (check_common(n_in, n_out, grid, P, B, &G)) return (size_t)-1;
-    if (check_jvp(K, flags)) return (size_t)-1;
-    algo = resolve_algo_jvp(algo, n_in, n_out, grid, P, G);
-    return jvp_workspace_bytes(sizeof(T), algo, n_in, n_out, grid, P);
-}
-
-// ---------------------------------------------------------------- per-pose clouds
-// dpr_raster_clouds_ex_* / dpr_raster_pullback_clouds_ex_* (include/dpr.h, "PER-POSE CLOUDS").  DPR_ALGO_ATOMIC:
-// k_clouds_fwd_atomic / k_clouds_bwd_atomic, every (n_in, n_out).  For (2,2), (3,3), (3,2): DPR_ALGO_TILED runs the
-// single-pose tiled path pose by pose on the offset pointers (workspace reused), DPR_ALGO_CHUNKED the pose-owned LDS
-// tiles of dpr_kernels_clouds.h.
-static int check_clouds_op(int op, unsigned flags) {
-    if (op == DPR_OP_RESIDUAL_PULLBACK)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "per-pose clouds have no residual pullback");
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
-        return fail(DPR_ERR_INVALID_ARG, "clouds: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "per-pose clouds keep / reuse no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    return DPR_OK;
-}
-
-// 64-bit offsets: cloud b starts at b * P * n_in, plane b at b * G
-static int check_clouds_sizes(int n_in, int64_t P, int64_t B, int64_t G) {
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
-    if (B > 0 && (P > ((int64_t)1 << 60) / B / n_in || G > ((int64_t)1 << 62) / B))
-        return fail(DPR_ERR_INVALID_ARG, "B * P * n_in or the image (G * B) too large");
-    return DPR_OK;
-}
-
-template <int NO> static CloudTiles<NO> clouds_tiles(const int64_t* grid) {
-    CloudTiles<NO> ct;
-    ct.tiles = 1;
-    for (int d = 0; d < NO; ++d) {
-        const int e = CloudTileShape<NO>::e[d];
-        ct.nt[d] = (int)((grid[d] + e - 1) / e);
-        ct.tiles *= ct.nt[d];
-    }
-    return ct;
-}
-static int64_t clouds_tile_count(int n_out, const int64_t* grid) {
-    return n_out == 2 ? clouds_tiles<2>(grid).tiles : clouds_tiles<3>(grid).tiles;
-}
-
-// Slices of each cloud on DPR_ALGO_CHUNKED: enough workgroups (pose x tile x slice) to fill 256 CUs with two
-// resident workgroups four times over, and no slice under 2048 points.
-struct CloudsPlan {
-    int64_t tiles, slices, slice_len;
-};
-static CloudsPlan clouds_plan(int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    CloudsPlan pl;
-    pl.tiles = clouds_tile_count(n_out, grid);
-    const int64_t items = pl.tiles * (B > 0 ? B : 1);
-    int64_t s = (2048 + items - 1) / items;
-    const int64_t by_points = (P + 2047) / 2048;
-    if (s > by_points) s = by_points;
-    if (s > 64) s = 64;
-    if (s < 1) s = 1;
-    pl.slice_len = (P + s - 1) / s;
-    if (pl.slice_len < 1) pl.slice_len = 1;
-    pl.slices = (P + pl.slice_len - 1) / pl.slice_len;
-    if (pl.slices < 1) pl.slices = 1;
-    return pl;
-}
-
-// AUTO (dpr_resolve_algo_clouds), host arithmetic on the shape and the element size (profiles/clouds_probe.txt):
-//  - the forward: DPR_ALGO_CHUNKED while a pose's grid is at most kCloudsChunkedMaxTiles tiles (every tile re-reads
-//    its slices of the cloud; 128^2 x 256 poses of 2e4 points: 0.14 ms against 1.0 ms ATOMIC, 64^3 x 32 of 1e5:
-//    0.51 against 1.5 ms TILED);
-//  - the pullback: DPR_ALGO_CHUNKED on 2-D grids of fp32 data within the same bound (128^2 x 256: 0.14 against
-//    0.16 ms ATOMIC); on 3-D grids (64^3 x 32: 0.77 against 0.25 ms) and for fp64 data (128^2 x 256: 0.27 against
-//    0.20 ms) the direct gathers of DPR_ALGO_ATOMIC are faster;
-//  - then DPR_ALGO_TILED where the single-pose rule prefers it (256^3 x 4 of 2e6: 0.44 / 0.46 ms against 3.1 / 0.63
-//    ATOMIC), DPR_ALGO_ATOMIC otherwise and for the other pairs.
-constexpr int64_t kCloudsChunkedMaxTiles = 32;
-static int resolve_algo_clouds(int algo, int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t G,
-                               size_t elem) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    if (!dims_have_all_algos(n_in, n_out)) return DPR_ALGO_ATOMIC;
-    if (clouds_tile_count(n_out, grid) <= kCloudsChunkedMaxTiles &&
-        (op == DPR_OP_RASTER || (n_out == 2 && elem == 4)))
-        return DPR_ALGO_CHUNKED;
-    if (tiled_preferred(op, n_out, grid, P, 1, G) &&
-        tiled_workspace_bytes(elem, op, 0u, n_in, n_out, grid, P, 1) != (size_t)-1)
-        return DPR_ALGO_TILED;
-    return DPR_ALGO_ATOMIC;
-}
-
-// bytes of workspace, or (size_t)-1 (message recorded) when the algorithm cannot run the shape
-static size_t clouds_workspace_bytes(size_t elem, int op, int algo, int n_in, int n_out, const int64_t* grid,
-                                     int64_t P, int64_t B) {
-    if (algo == DPR_ALGO_ATOMIC) return 0;
-    if (algo != DPR_ALGO_TILED && algo != DPR_ALGO_CHUNKED) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "unknown algorithm %d", algo);
-        return (size_t)-1;
-    }
-    if (!dims_have_all_algos(n_in, n_out)) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "(n_in, n_out) = (%d, %d): per-pose clouds run on DPR_ALGO_ATOMIC only",
-             n_in, n_out);
-        return (size_t)-1;
-    }
-    if (algo == DPR_ALGO_TILED) {
-        // the single-pose tiled workspace, reused from pose to pose
-        const size_t n = tiled_workspace_bytes(elem, op, 0u, n_in, n_out, grid, P, 1);
-        if (n == (size_t)-1)
-            fail(DPR_ERR_UNSUPPORTED_ALGO, "DPR_ALGO_TILED: grid needs too many tiles or P >= 2^32");
-        return n;
-    }
-    if (op == DPR_OP_RASTER) return elem == 4 ? align_up(sizeof(uint32_t) * (size_t)B) : 0;  // per-pose weight keys
-    const CloudsPlan pl = clouds_plan(n_out, grid, P, B);
-    return align_up(sizeof(double) * (size_t)(n_out * n_in + n_out + 1) * (size_t)B * (size_t)(pl.tiles * pl.slices));
-}
-
-template <typename T, int NI, int NO>
-static int raster_clouds_run(hipStream_t st, int algo, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out,
-                             const T* points, const T* rot, const T* trans, const T* bg, const T* ow, const T* pw,
-                             void* ws, size_t ws_bytes) {
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    if (algo == DPR_ALGO_ATOMIC || P == 0) {
-        fill_background(st, out, G, B, bg);
-        stage_mark(st);
-        if (P > 0) {
-            dim3 g((unsigned)((P + kBlock - 1) / kBlock), (unsigned)(B < 65535 ? B : 65535));
-            hipLaunchKernelGGL((k_clouds_fwd_atomic<T, NI, NO>), g, dim3(kBlock), 0, st, gd, P, B, out, points, rot,
-                               trans, ow, pw);
-        }
-        stage_mark(st);
-        DPR_HIP(hipGetLastError());
-        return DPR_OK;
-    }
-    if constexpr (!dims_have_all_algos(NI, NO)) {
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only", NI, NO);
-    } else {
-        if (algo == DPR_ALGO_TILED) {
-            // plane b: exactly dpr_raster_ex_*(DPR_ALGO_TILED) of (cloud b, pose b)
-            for (int64_t b = 0; b < B; ++b)
-                if (int rc = raster_tiled<T, NI, NO>(st, 0u, grid, G, P, 1, out + b * G, points + b * P * NI,
-                                                     rot + b * (NO * NI), trans + b * NO, bg ? bg + b : nullptr,
-                                                     ow ? ow + b : nullptr, pw ? pw + b * P : nullptr, ws, ws_bytes))
-                    return rc;
-            return DPR_OK;
-        }
-        const CloudTiles<NO> ct = clouds_tiles<NO>(grid);
-        const CloudsPlan pl = clouds_plan(NO, grid, P, B);
-        const uint32_t* keys = nullptr;
-        if constexpr (sizeof(T) == 4) {  // the per-pose weight ranges of the fixed-point scale
-            if (pw) {
-                hipLaunchKernelGGL(k_clouds_wrange<T>, dim3((unsigned)B), dim3(256), 0, st, pw, P, (int64_t)0,
-                                   (uint32_t*)ws);
-                keys = (const uint32_t*)ws;
-            }
-        }
-        const int atomic_flush = pl.slices > 1;
-        if (atomic_flush) fill_background(st, out, G, B, bg);
-        stage_mark(st);
-        for (int64_t b0 = 0; b0 < B; b0 += 65535) {
-            const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
-            hipLaunchKernelGGL((k_clouds_fwd_tile<T, NI, NO>), dim3((unsigned)(pl.tiles * pl.slices), (unsigned)nb),
-                               dim3(kCLThreads), 0, st, gd, ct, (int)pl.slices, pl.slice_len, P, b0, out, points, rot,
-                               trans, bg, ow, pw, keys, atomic_flush);
-        }
-        stage_mark(st);
-        DPR_HIP(hipGetLastError());
-        return DPR_OK;
-    }
-}
-
-template <typename T>
-static int raster_clouds_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                              int64_t P, int64_t B, T* out, const T* points, const T* rot, const T* trans,
-                              const T* bg, const T* ow, const T* pw, void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_clouds_op(DPR_OP_RASTER, flags)) return rc;
-    if (int rc = check_clouds_sizes(n_in, P, B, G)) return rc;
-    algo = resolve_algo_clouds(algo, DPR_OP_RASTER, n_in, n_out, grid, P, G, sizeof(T));
-    const size_t need = clouds_workspace_bytes(sizeof(T), DPR_OP_RASTER, algo, n_in, n_out, grid, P, B);
-    if (need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
-    if (B == 0) return DPR_OK;
-    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "per-pose clouds (algorithm %d) need %zu workspace bytes, got %zu", algo, need,
-                    ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        return raster_clouds_run<T, decltype(ni)::value, decltype(no)::value>(st, algo, grid, G, P, B, out, points,
-                                                                              rot, trans, bg, ow, pw, ws, ws_bytes);
-    });
-}
-
-template <typename T, int NI, int NO>
-static int pullback_clouds_run(hipStream_t st, int algo, unsigned flags, const int64_t* grid, int64_t G, int64_t P,
-                               int64_t B, const T* g, const T* points, const T* rot, const T* trans, const T* ow,
-                               const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw, void* ws,
-                               size_t ws_bytes) {
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    if constexpr (dims_have_all_algos(NI, NO)) {
-        if (algo == DPR_ALGO_TILED && P > 0) {
-            // pose b: exactly dpr_raster_pullback_ex_*(DPR_ALGO_TILED) of (cloud b, pose b)
-            const Residual<T> none{nullptr, T(0), nullptr};
-            for (int64_t b = 0; b < B; ++b)
-                if (int rc = pullback_tiled<T, NI, NO>(
-                        st, flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD, grid, G, P, 1, g + b * G, points + b * P * NI,
-                        rot + b * (NO * NI), trans + b * NO, ow ? ow + b : nullptr, pw ? pw + b * P : nullptr,
-                        d_pts + b * P * NI, d_rot + b * (NO * NI), d_trans + b * NO, d_bg + b, d_ow + b,
-                        d_pw ? d_pw + b * P : nullptr, ws, ws_bytes, none))
-                    return rc;
-            return DPR_OK;
-        }
-    }
-    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
-    grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
-    stage_mark(st);
-    if (algo == DPR_ALGO_ATOMIC || P == 0) {
-        DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * NO * NI), st));
-        DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * NO), st));
-        DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
-        if (P > 0) {
-            dim3 gg((unsigned)((P + kBlock - 1) / kBlock), (unsigned)(B < 65535 ? B : 65535));
-            hipLaunchKernelGGL((k_clouds_bwd_atomic<T, NI, NO>), gg, dim3(kBlock), 0, st, gd, P, B, g, points, rot,
-                               trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw);
-        }
-        stage_mark(st);
-        DPR_HIP(hipGetLastError());
-        return DPR_OK;
-    }
-    if constexpr (!dims_have_all_algos(NI, NO)) {
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "(n_in, n_out) = (%d, %d) runs on DPR_ALGO_ATOMIC only", NI, NO);
-    } else {
-        (void)ws_bytes;
-        const CloudTiles<NO> ct = clouds_tiles<NO>(grid);
-        const CloudsPlan pl = clouds_plan(NO, grid, P, B);
-        const int64_t parts = pl.tiles * pl.slices;
-        double* partials = (double*)ws;
-        for (int64_t b0 = 0; b0 < B; b0 += 65535) {
-            const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
-            hipLaunchKernelGGL((k_clouds_bwd_tile<T, NI, NO>), dim3((unsigned)parts, (unsigned)nb), dim3(kCLThreads),
-                               0, st, gd, ct, (int)pl.slices, pl.slice_len, P, B, b0, g, points, rot, trans, ow, pw,
-                               d_pts, d_pw, partials);
-        }
-        for (int64_t b0 = 0; b0 < B; b0 += 65535) {
-            const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
-            hipLaunchKernelGGL((k_clouds_reduce<T, NI, NO>), dim3(NO * NI + NO + 1, (unsigned)nb), dim3(256), 0, st,
-                               partials, B, b0, parts, d_rot, d_trans, d_ow);
-        }
-        stage_mark(st);
-        DPR_HIP(hipGetLastError());
-        return DPR_OK;
-    }
-}
-
-template <typename T>
-static int pullback_clouds_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                int64_t P, int64_t B, const T* g, const T* points, const T* rot, const T* trans,
-                                const T* ow, const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw,
-                                void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_clouds_op(DPR_OP_PULLBACK, flags)) return rc;
-    if (int rc = check_clouds_sizes(n_in, P, B, G)) return rc;
-    if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
-    algo = resolve_algo_clouds(algo, DPR_OP_PULLBACK, n_in, n_out, grid, P, G, sizeof(T));
-    const size_t need = clouds_workspace_bytes(sizeof(T), DPR_OP_PULLBACK, algo, n_in, n_out, grid, P, B);
-    if (need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
-    if (B == 0) return DPR_OK;  // (every output is empty)
-    if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (!d_rot || !d_trans || !d_bg || !d_ow) return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
-    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
-        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "per-pose clouds (algorithm %d) need %zu workspace bytes, got %zu", algo, need,
-                    ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    return with_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        return pullback_clouds_run<T, decltype(ni)::value, decltype(no)::value>(
-            st, algo, flags, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw, ws,
-            ws_bytes);
-    });
-}
-
-template <typename T>
-static size_t workspace_clouds_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                    int64_t P, int64_t B) {
-    int64_t G = 0;
-    if (check_common(n_in, n_out, grid, P, B, &G)) return (size_t)-1;
-    if (check_clouds_op(op, flags)) return (size_t)-1;
-    if (check_clouds_sizes(n_in, P, B, G)) return (size_t)-1;
-    algo = resolve_algo_clouds(algo, op, n_in, n_out, grid, P, G, sizeof(T));
-    return clouds_workspace_bytes(sizeof(T), op, algo, n_in, n_out, grid, P, B);
-}
-
-// ---------------------------------------------------------------- smooth splat
-// dpr_raster_smooth_ex_* / dpr_raster_pullback_smooth_ex_* (include/dpr.h, "SMOOTH SPLAT"; kernels: dpr_smooth.hip).
-// (2,2), (3,3), (3,2) only.  DPR_ALGO_ATOMIC: forward and pullback; DPR_ALGO_TILED: forward.
-// (before check_common: the grid of a pair without kernels is not looked at)
-static int check_smooth_dims(int n_in, int n_out) {
-    if (!smooth_dims_supported(n_in, n_out))
-        return fail(DPR_ERR_UNSUPPORTED_DIMS,
-                    "unsupported (n_in, n_out) = (%d, %d); the smooth splat supports (2,2), (3,3), (3,2)", n_in, n_out);
-    return DPR_OK;
-}
-static int check_smooth(int op, unsigned flags) {
-    if (op == DPR_OP_RESIDUAL_PULLBACK)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth splat has no residual pullback");
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
-        return fail(DPR_ERR_INVALID_ARG, "smooth splat: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "the smooth splat keeps / reuses no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    return DPR_OK;
-}
-
-// AUTO (dpr_resolve_algo_smooth), from the shape alone (profiles/smooth_probe.txt, fp32, uniform clouds in either
-// order, 1 and 16 poses).  The pullback is DPR_ALGO_ATOMIC.  The forward is DPR_ALGO_TILED from a point count on,
-// where the tile ids fit the sort key, and DPR_ALGO_ATOMIC below it: the tiled path pays a sort and four launches
-// per pose (0.07-0.1 ms), the atomic one 3^N atomics per point.
-//  - 3-D grids, from 1e5 points: 1e5 -> 128^3 0.113 against 0.145 ms (16 poses 1.24 / 1.70), -> 256^3 0.149 / 0.148
-//    (16 poses 1.98 / 1.84: the one row where the rule loses, 1.08x); 3e4 -> 128^3 0.091 against 0.071 ATOMIC;
-//    1e7 -> 256^3 0.64 against 9.9 ms.
-//  - 2-D grids, from 5e5 points (9 atomics per point, not 27): 3e5 -> 512^2 0.173 against 0.148 ms ATOMIC (16 poses
-//    2.21 / 1.82), 1e6 0.229 against 0.412 (3.14 / 5.98).  Between 3e5 and 1e6 nothing was measured.
-constexpr int64_t kSmoothTiledMinPoints3D = 100000;
-constexpr int64_t kSmoothTiledMinPoints2D = 500000;
-static int resolve_algo_smooth(int algo, int op, int n_out, const int64_t* grid, int64_t P) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    const int64_t min_points = n_out == 3 ? kSmoothTiledMinPoints3D : kSmoothTiledMinPoints2D;
-    if (op == DPR_OP_RASTER && P >= min_points && smooth_tile_count(n_out, grid, P) != 0) return DPR_ALGO_TILED;
-    return DPR_ALGO_ATOMIC;
-}
-
-// bytes of workspace, or (size_t)-1 (message recorded) when the algorithm cannot run the call
-static size_t smooth_workspace_bytes(int op, int algo, int n_out, const int64_t* grid, int64_t P) {
-    if (algo == DPR_ALGO_ATOMIC) return 0;  // (the pullback's per-pose partials leave their block as atomics)
-    if (algo != DPR_ALGO_TILED) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth splat runs on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d",
-             algo);
-        return (size_t)-1;
-    }
-    if (op != DPR_OP_RASTER) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth pullback runs on DPR_ALGO_ATOMIC only");
-        return (size_t)-1;
-    }
-    const size_t n = smooth_tiled_workspace_bytes(n_out, grid, P);
-    if (n == (size_t)-1)
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth DPR_ALGO_TILED: too many tiles for a 32-bit key or P > 2^32 - 2");
-    return n;
-}
-
-template <class F> static int with_smooth_dims(int n_in, int n_out, F&& f) {
-    if (n_in == 2 && n_out == 2) return f(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
-    if (n_in == 3 && n_out == 3) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
-    if (n_in == 3 && n_out == 2) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{});
-    return fail(DPR_ERR_UNSUPPORTED_DIMS, "smooth splat: unsupported (n_in, n_out) = (%d, %d)", n_in, n_out);
-}
-
-template <typename T>
-static int raster_smooth_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                              int64_t P, int64_t B, T* out, const T* points, const T* rot, const T* trans,
-                              const T* bg, const T* ow, const T* pw, void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_smooth(DPR_OP_RASTER, flags)) return rc;
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
-    algo = resolve_algo_smooth(algo, DPR_OP_RASTER, n_out, grid, P);
-    const size_t need = smooth_workspace_bytes(DPR_OP_RASTER, algo, n_out, grid, P);
-    if (need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
-    if (B == 0) return DPR_OK;
-    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "smooth splat (algorithm %d) needs %zu workspace bytes, got %zu", algo, need,
-                    ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    fill_background(st, out, G, B, bg);
-    stage_mark(st);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_fwd_tiled<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, ow, pw, ws, ws_bytes)
-                           : smooth_fwd_atomic<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, ow, pw);
-        stage_mark(st);
-        return rc;
-    });
-}
-
-template <typename T>
-static int pullback_smooth_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                int64_t P, int64_t B, const T* g, const T* points, const T* rot, const T* trans,
-                                const T* ow, const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw,
-                                void* ws, size_t ws_bytes) {
-    (void)ws_bytes;
-    int64_t G = 0;
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_smooth(DPR_OP_PULLBACK, flags)) return rc;
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
-    if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
-    algo = resolve_algo_smooth(algo, DPR_OP_PULLBACK, n_out, grid, P);
-    if (smooth_workspace_bytes(DPR_OP_PULLBACK, algo, n_out, grid, P) == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
-    if (B == 0) return DPR_OK;  // (every output is empty)
-    if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (!d_rot || !d_trans || !d_bg || !d_ow) return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
-    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
-        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * n_out * n_in), st));
-    DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * n_out), st));
-    DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
-    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
-    grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
-    stage_mark(st);
-    int64_t slices = 1;
-    const int poses_per_slice = pose_slices(P, B, &slices);  // (the linear atomic pullback's: SUMMATION ORDER, note 1)
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        const int rc = smooth_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
-            st, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice,
-            slices);
-        stage_mark(st);
-        return rc;
-    });
-}
-
-template <typename T>
-static size_t workspace_smooth_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                    int64_t P, int64_t B) {
-    int64_t G = 0;
-    if (check_smooth_dims(n_in, n_out)) return (size_t)-1;
-    if (check_common(n_in, n_out, grid, P, B, &G)) return (size_t)-1;
-    if (check_smooth(op, flags)) return (size_t)-1;
-    algo = resolve_algo_smooth(algo, op, n_out, grid, P);
-    return smooth_workspace_bytes(op, algo, n_out, grid, P);
-}
-
-// ---------------------------------------------------------------- smooth sampling
-// dpr_sample_smooth_ex_* / dpr_sample_smooth_pullback_ex_* (include/dpr.h, "SMOOTH SAMPLING"; kernels:
-// dpr_smooth.hip).  Forward: DPR_ALGO_ATOMIC.  Pullback: DPR_ALGO_ATOMIC, the fused kernel with image atomics;
-// DPR_ALGO_TILED, the same kernel without them, then ds_dimage pose by pose from the tiled smooth forward.
-static int check_sample_smooth_op(int op, unsigned flags) {
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
-        return fail(DPR_ERR_INVALID_ARG, "smooth sampling: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "smooth sampling keeps / reuses no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    return DPR_OK;
-}
-
-// AUTO: the forward is ATOMIC; the pullback is TILED where the smooth forward of one pose of the shape would be
-// (the measured rows: profiles/sample_smooth_probe.txt)
-static int resolve_algo_sample_smooth(int algo, int op, int n_out, const int64_t* grid, int64_t P) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    if (op == DPR_OP_PULLBACK) return resolve_algo_smooth(DPR_ALGO_AUTO, DPR_OP_RASTER, n_out, grid, P);
-    return DPR_ALGO_ATOMIC;
-}
-
-// bytes of workspace, or (size_t)-1 (message recorded) when the algorithm cannot run the call
-static size_t sample_smooth_workspace_bytes(int op, int algo, int n_out, const int64_t* grid, int64_t P) {
-    if (algo == DPR_ALGO_ATOMIC) return 0;
-    if (algo != DPR_ALGO_TILED) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO,
-             "smooth sampling runs on DPR_ALGO_ATOMIC and, the pullback, DPR_ALGO_TILED, not algorithm %d", algo);
-        return (size_t)-1;
-    }
-    if (op != DPR_OP_PULLBACK) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth sampling forward runs on DPR_ALGO_ATOMIC only");
-        return (size_t)-1;
-    }
-    const size_t n = smooth_tiled_workspace_bytes(n_out, grid, P);
-    if (n == (size_t)-1)
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth DPR_ALGO_TILED: too many tiles for a 32-bit key or P > 2^32 - 2");
-    return n;
-}
-
-// the host checks both entry points share; *G_out and the resolved *algo come back
-static int check_sample_smooth(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                               int64_t B, int64_t* G_out, size_t* need) {
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, G_out)) return rc;
-    if (int rc = check_sample_smooth_op(op, flags)) return rc;
-    *algo = resolve_algo_sample_smooth(*algo, op, n_out, grid, P);
-    *need = sample_smooth_workspace_bytes(op, *algo, n_out, grid, P);
-    if (*need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
-    return check_sample_sizes(P, B, *G_out);
-}
-
-template <typename T>
-static int sample_smooth_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                              int64_t P, int64_t B, T* values, const T* image, const T* points, const T* rot,
-                              const T* trans, void* ws, size_t ws_bytes) {
-    (void)ws_bytes;
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_sample_smooth(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return rc;
-    if (P == 0 || B == 0) return DPR_OK;
-    if (!values) return fail(DPR_ERR_INVALID_ARG, "values is NULL");
-    if (!image) return fail(DPR_ERR_INVALID_ARG, "image is NULL");
-    if (!points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (int rc = check_alignment<T>(ws, {values, image, points, rot, trans})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    int64_t slices = 1;
-    const int pps = pose_slices(P, B, &slices);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        const int rc = sample_smooth_fwd<T, decltype(ni)::value, decltype(no)::value>(
-            st, grid, G, P, B, values, image, points, rot, trans, pps, slices);
-        stage_mark(st);
-        return rc;
-    });
-}
-
-template <typename T>
-static int sample_smooth_pullback_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
-                                       const int64_t* grid, int64_t P, int64_t B, const T* dv, const T* image,
-                                       const T* points, const T* rot, const T* trans, T* d_img, T* d_pts, T* d_rot,
-                                       T* d_trans, void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_sample_smooth(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return rc;
-    if (!d_img && !d_pts && !d_rot && !d_trans)
-        return fail(DPR_ERR_INVALID_ARG, "smooth sampling pullback: every output is NULL");
-    const bool tiled = algo == DPR_ALGO_TILED;
-    if (tiled && d_img && P > 0 && B > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_TILED smooth sampling pullback needs %zu workspace bytes, got %zu",
-                    need, ws ? ws_bytes : (size_t)0);
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && B > 0) {
-        if (!dv) return fail(DPR_ERR_INVALID_ARG, "ds_dvalues is NULL");
-        if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-        if ((d_pts || d_rot || d_trans) && !image)
-            return fail(DPR_ERR_INVALID_ARG, "image is NULL (needed for ds_dpoints / ds_drotation / ds_dtranslation)");
-    }
-    if (int rc = check_alignment<T>(ws, {dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    if (d_rot) DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * n_out * n_in), st));
-    if (d_trans) DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * n_out), st));
-    if (d_img) DPR_HIP(hipMemsetAsync(d_img, 0, sizeof(T) * (size_t)(B * G), st));
-    if (d_pts && B == 0) DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * n_in), st));
-    if (P == 0 || B == 0) return DPR_OK;
-    int64_t slices = 1;
-    const int pps = pose_slices(P, B, &slices);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        if (int rc = sample_smooth_bwd<T, NI, NO>(st, grid, G, P, B, dv, image, points, rot, trans,
-                                                  tiled ? nullptr : d_img, d_pts, d_rot, d_trans, pps, slices))
-            return rc;
-        stage_mark(st);
-        if (tiled && d_img) {
-            // plane b (zeroed above): the single-pose tiled smooth forward of weights ds_dvalues[:, b] (a contiguous
-            // column), out_weight 1 -- what dpr_raster_smooth_ex_*(DPR_ALGO_TILED) returns for them
-            for (int64_t b = 0; b < B; ++b)
-                if (int rc = smooth_fwd_tiled<T, NI, NO>(st, grid, G, P, 1, d_img + b * G, points, rot + b * (NO * NI),
-                                                         trans + b * NO, nullptr, dv + b * P, ws, ws_bytes))
-                    return rc;
-        }
-        return DPR_OK;
-    });
-}
-
-template <typename T>
-static size_t workspace_sample_smooth_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                           int64_t P, int64_t B) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (check_sample_smooth(op, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return (size_t)-1;
-    return need;
-}
-
-// ---------------------------------------------------------------- smooth splat, forward mode
-// dpr_raster_smooth_jvp_ex_* (include/dpr.h, "SMOOTH SPLAT, FORWARD MODE"; kernels: dpr_smooth.hip).  k_jvp_fill
-// writes the background tangent into every plane, then DPR_ALGO_ATOMIC (k_smooth_jvp_atomic) or DPR_ALGO_TILED
-// (the tiled smooth forward's binning once per pose, k_smooth_tile_jvp over (tiles, K)) adds the deposits.
-// AUTO (dpr_resolve_algo_smooth_jvp), from the shape and K alone (profiles/smooth_jvp_probe.txt, fp32, uniform clouds
-// in generation order).  The tiled path pays the key, sort and start table once per pose, whatever K; the atomic one
-// 3^N atomics per (point, tangent).  So the point count from which DPR_ALGO_TILED pays falls with K: the rule is the
-// smooth forward's with P * K in the place of P, and for 2-D grids a lower constant.
-//  - 3-D grids, P * K >= 1e5 (the forward's constant): 1e5 -> 256^3, K = 1 0.183 against 0.169 ms ATOMIC (1.08x, the
-//    one row where the rule loses), K = 4 0.378 / 0.503, K = 12 0.98 / 1.43; 1e7 -> 256^3, K = 12 7.8 against 119 ms.
-//  - 2-D grids, P * K >= 4e5.  The forward's 5e5 with P alone broke two rows: 1e5 x 16 poses -> 128^2 at K = 4, 1.59
-//    against 2.57 ms ATOMIC (1.61x), and at K = 12, 1.65 against 7.29 (4.4x).  At K = 1 the same shape is 1.53
-//    against 0.68 ATOMIC, and 1e6 -> 512^2 is 0.268 against 0.435: the constant lies between P * K = 1e5 and 4e5,
-//    and 4e5 is the measured row.  Nothing was measured between.
-constexpr int64_t kSmoothJvpTiledMinWork3D = 100000;
-constexpr int64_t kSmoothJvpTiledMinWork2D = 400000;
-static int resolve_algo_smooth_jvp(int algo, int n_out, const int64_t* grid, int64_t P, int64_t K) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    const int64_t min_work = n_out == 3 ? kSmoothJvpTiledMinWork3D : kSmoothJvpTiledMinWork2D;
-    if (P * K >= min_work && smooth_tile_count(n_out, grid, P) != 0) return DPR_ALGO_TILED;
-    return DPR_ALGO_ATOMIC;
-}
-
-// the checks every smooth JVP entry point and query shares, in the smooth entry points' order; *need: workspace
-static int check_smooth_jvp(int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                            int64_t B, int64_t K, int64_t* G, size_t* need) {
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
-    if (int rc = check_jvp(K, flags)) return rc;
-    if (int rc = check_sample_sizes(P, B, *G)) return rc;
-    if (B > 0 && *G * K > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "output too large");
-    *algo = resolve_algo_smooth_jvp(*algo, n_out, grid, P, K);
-    *need = smooth_workspace_bytes(DPR_OP_RASTER, *algo, n_out, grid, P);
-    return *need == (size_t)-1 ? DPR_ERR_UNSUPPORTED_ALGO : DPR_OK;
-}
-
-template <typename T>
-static int raster_smooth_jvp_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                  int64_t P, int64_t B, int64_t K, T* out_dot, const T* points, const T* rot,
-                                  const T* trans, const T* ow, const T* pw, JvpTangents<T> tan, const T* bg_dot,
-                                  void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_jvp(&algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
-    if (B == 0) return DPR_OK;
-    if (!out_dot) return fail(DPR_ERR_INVALID_ARG, "out_dot is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "smooth JVP (algorithm %d) needs %zu workspace bytes, got %zu", algo, need,
-                    ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out_dot, points, rot, trans, ow, pw, tan.points, tan.rot, tan.trans, tan.ow,
-                                         tan.pw, bg_dot}))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    // the background tangent (or 0) into every plane; then the deposits, where any other tangent is given
-    const int k = (int)K;
-    const int64_t planes = B * K;
-    const int64_t want = (G + kBlock - 1) / kBlock;
-    dim3 g((unsigned)(want < 4096 ? want : 4096), 1);
-    for (int64_t q0 = 0; q0 < planes; q0 += 65535) {
-        const int64_t nq = (planes - q0 < 65535) ? planes - q0 : 65535;
-        g.y = (unsigned)nq;
-        hipLaunchKernelGGL(k_jvp_fill<T>, g, dim3(kBlock), 0, st, out_dot, G, k, B, q0, bg_dot);
-    }
-    stage_mark(st);
-    DPR_HIP(hipGetLastError());
-    if (P == 0 || !(tan.points || tan.rot || tan.trans || tan.ow || tan.pw)) return DPR_OK;
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_jvp_tiled<T, NI, NO>(st, grid, G, P, B, k, out_dot, points, rot, trans, ow, pw, tan,
-                                                         ws, ws_bytes)
-                           : smooth_jvp_atomic<T, NI, NO>(st, grid, G, P, B, k, out_dot, points, rot, trans, ow, pw,
-                                                          tan);
-        stage_mark(st);
-        return rc;
-    });
-}
-
-static size_t workspace_smooth_jvp_impl(int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                                        int64_t B, int64_t K) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (check_smooth_jvp(&algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return (size_t)-1;
-    return need;
-}
-
 }  // namespace dpr
 
 extern "C" {
@@ -2021,47 +823,6 @@ DPR_DEFINE(f32, float)
 DPR_DEFINE(f64, double)
 #undef DPR_DEFINE
 
-int dpr_resolve_algo_channels(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
-                              int64_t C) {
-    int64_t G = 0;
-    if (int rc = dpr::check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
-        return dpr::fail(op == DPR_OP_RESIDUAL_PULLBACK ? DPR_ERR_UNSUPPORTED_ALGO : DPR_ERR_INVALID_ARG,
-                         "channels: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
-    if (int rc = dpr::check_channels(C, 0u)) return rc;
-    return dpr::resolve_algo_channels(DPR_ALGO_AUTO, op, n_in, n_out, grid, P, B, G);
-}
-
-#define DPR_DEFINE_CHANNELS(SUF, T)                                                                   \
-    size_t dpr_workspace_bytes_channels_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out, \
-                                                 const int64_t* grid, int64_t P, int64_t B, int64_t C) { \
-        return dpr::workspace_channels_impl<T>(op, algo, flags, n_in, n_out, grid, P, B, C);          \
-    }                                                                                                 \
-    int dpr_raster_channels_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,     \
-                                     const int64_t* grid, int64_t P, int64_t B, int64_t C, T* out,    \
-                                     const T* points, const T* rotation, const T* translation,        \
-                                     const T* background, const T* out_weight, const T* point_weight, \
-                                     void* workspace, size_t workspace_bytes) {                       \
-        return dpr::raster_channels_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, C, out,     \
-                                            points, rotation, translation, background, out_weight,    \
-                                            point_weight, workspace, workspace_bytes);                \
-    }                                                                                                 \
-    int dpr_raster_pullback_channels_ex_##SUF(                                                        \
-        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,  \
-        int64_t B, int64_t C, const T* ds_dout, const T* points, const T* rotation,                   \
-        const T* translation, const T* out_weight, const T* point_weight, T* ds_dpoints,              \
-        T* ds_drotation, T* ds_dtranslation, T* ds_dbackground, T* ds_dout_weight,                    \
-        T* ds_dpoint_weight, void* workspace, size_t workspace_bytes) {                               \
-        return dpr::pullback_channels_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, C,        \
-                                              ds_dout, points, rotation, translation, out_weight,     \
-                                              point_weight, ds_dpoints, ds_drotation,                 \
-                                              ds_dtranslation, ds_dbackground, ds_dout_weight,        \
-                                              ds_dpoint_weight, workspace, workspace_bytes);          \
-    }
-DPR_DEFINE_CHANNELS(f32, float)
-DPR_DEFINE_CHANNELS(f64, double)
-#undef DPR_DEFINE_CHANNELS
-
 #define DPR_DEFINE_RESIDUAL(SUF, T)                                                               \
     int dpr_raster_residual_pullback_ex_##SUF(                                                    \
         void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,         \
@@ -2094,200 +855,5 @@ DPR_DEFINE_CHANNELS(f64, double)
 DPR_DEFINE_RESIDUAL(f32, float)
 DPR_DEFINE_RESIDUAL(f64, double)
 #undef DPR_DEFINE_RESIDUAL
-
-int dpr_resolve_algo_sample(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    int64_t G = 0;
-    if (int rc = dpr::check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = dpr::check_sample_op(op, 0u)) return rc;
-    return dpr::resolve_algo_sample(DPR_ALGO_AUTO, op, n_in, n_out, grid, P, G);
-}
-
-#define DPR_DEFINE_SAMPLE(SUF, T)                                                                          \
-    size_t dpr_workspace_bytes_sample_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,      \
-                                               const int64_t* grid, int64_t P, int64_t B) {                \
-        return dpr::workspace_sample_impl<T>(op, algo, flags, n_in, n_out, grid, P, B);                    \
-    }                                                                                                      \
-    int dpr_sample_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, \
-                            int64_t P, int64_t B, T* values, const T* image, const T* points,              \
-                            const T* rotation, const T* translation, void* workspace,                      \
-                            size_t workspace_bytes) {                                                      \
-        return dpr::sample_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, values, image, points,    \
-                                   rotation, translation, workspace, workspace_bytes);                     \
-    }                                                                                                      \
-    int dpr_sample_pullback_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,          \
-                                     const int64_t* grid, int64_t P, int64_t B, const T* ds_dvalues,       \
-                                     const T* image, const T* points, const T* rotation,                   \
-                                     const T* translation, T* ds_dimage, T* ds_dpoints, T* ds_drotation,   \
-                                     T* ds_dtranslation, void* workspace, size_t workspace_bytes) {        \
-        return dpr::sample_pullback_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, ds_dvalues,      \
-                                            image, points, rotation, translation, ds_dimage, ds_dpoints,   \
-                                            ds_drotation, ds_dtranslation, workspace, workspace_bytes);    \
-    }
-DPR_DEFINE_SAMPLE(f32, float)
-DPR_DEFINE_SAMPLE(f64, double)
-#undef DPR_DEFINE_SAMPLE
-
-int dpr_resolve_algo_jvp(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t K) {
-    int64_t G = 0;
-    if (int rc = dpr::check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = dpr::check_jvp(K, 0u)) return rc;
-    return dpr::resolve_algo_jvp(DPR_ALGO_AUTO, n_in, n_out, grid, P, G);
-}
-
-#define DPR_DEFINE_JVP(SUF, T)                                                                                 \
-    size_t dpr_workspace_bytes_jvp_ex_##SUF(int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, \
-                                            int64_t P, int64_t B, int64_t K) {                                 \
-        return dpr::workspace_jvp_impl<T>(algo, flags, n_in, n_out, grid, P, B, K);                            \
-    }                                                                                                          \
-    int dpr_raster_jvp_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, \
-                                int64_t P, int64_t B, int64_t K, T* out_dot, const T* points, const T* rotation, \
-                                const T* translation, const T* out_weight, const T* point_weight,              \
-                                const T* points_dot, const T* rotation_dot, const T* translation_dot,          \
-                                const T* background_dot, const T* out_weight_dot, const T* point_weight_dot,   \
-                                void* workspace, size_t workspace_bytes) {                                     \
-        return dpr::raster_jvp_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, K, out_dot, points,       \
-                                       rotation, translation, out_weight, point_weight,                        \
-                                       dpr::JvpTangents<T>{points_dot, rotation_dot, translation_dot,          \
-                                                           out_weight_dot, point_weight_dot},                  \
-                                       background_dot, workspace, workspace_bytes);                            \
-    }
-DPR_DEFINE_JVP(f32, float)
-DPR_DEFINE_JVP(f64, double)
-#undef DPR_DEFINE_JVP
-
-int dpr_resolve_algo_clouds(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    int64_t G = 0;
-    if (int rc = dpr::check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = dpr::check_clouds_op(op, 0u)) return rc;
-    return dpr::resolve_algo_clouds(DPR_ALGO_AUTO, op, n_in, n_out, grid, P, G, sizeof(float));
-}
-
-#define DPR_DEFINE_CLOUDS(SUF, T)                                                                              \
-    size_t dpr_workspace_bytes_clouds_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,          \
-                                               const int64_t* grid, int64_t P, int64_t B) {                    \
-        return dpr::workspace_clouds_impl<T>(op, algo, flags, n_in, n_out, grid, P, B);                        \
-    }                                                                                                          \
-    int dpr_raster_clouds_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,                \
-                                   const int64_t* grid, int64_t P, int64_t B, T* out, const T* points,         \
-                                   const T* rotation, const T* translation, const T* background,               \
-                                   const T* out_weight, const T* point_weight, void* workspace,                \
-                                   size_t workspace_bytes) {                                                   \
-        return dpr::raster_clouds_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, out, points, rotation, \
-                                          translation, background, out_weight, point_weight, workspace,        \
-                                          workspace_bytes);                                                    \
-    }                                                                                                          \
-    int dpr_raster_pullback_clouds_ex_##SUF(                                                                   \
-        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, \
-        const T* ds_dout, const T* points, const T* rotation, const T* translation, const T* out_weight,       \
-        const T* point_weight, T* ds_dpoints, T* ds_drotation, T* ds_dtranslation, T* ds_dbackground,          \
-        T* ds_dout_weight, T* ds_dpoint_weight, void* workspace, size_t workspace_bytes) {                     \
-        return dpr::pullback_clouds_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, ds_dout, points,     \
-                                            rotation, translation, out_weight, point_weight, ds_dpoints,       \
-                                            ds_drotation, ds_dtranslation, ds_dbackground, ds_dout_weight,     \
-                                            ds_dpoint_weight, workspace, workspace_bytes);                     \
-    }
-DPR_DEFINE_CLOUDS(f32, float)
-DPR_DEFINE_CLOUDS(f64, double)
-#undef DPR_DEFINE_CLOUDS
-
-int dpr_resolve_algo_smooth(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    int64_t G = 0;
-    if (int rc = dpr::check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = dpr::check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = dpr::check_smooth(op, 0u)) return rc;
-    return dpr::resolve_algo_smooth(DPR_ALGO_AUTO, op, n_out, grid, P);
-}
-
-#define DPR_DEFINE_SMOOTH(SUF, T)                                                                              \
-    size_t dpr_workspace_bytes_smooth_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,          \
-                                               const int64_t* grid, int64_t P, int64_t B) {                    \
-        return dpr::workspace_smooth_impl<T>(op, algo, flags, n_in, n_out, grid, P, B);                        \
-    }                                                                                                          \
-    int dpr_raster_smooth_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,                \
-                                   const int64_t* grid, int64_t P, int64_t B, T* out, const T* points,         \
-                                   const T* rotation, const T* translation, const T* background,               \
-                                   const T* out_weight, const T* point_weight, void* workspace,                \
-                                   size_t workspace_bytes) {                                                   \
-        return dpr::raster_smooth_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, out, points, rotation, \
-                                          translation, background, out_weight, point_weight, workspace,        \
-                                          workspace_bytes);                                                    \
-    }                                                                                                          \
-    int dpr_raster_pullback_smooth_ex_##SUF(                                                                   \
-        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, \
-        const T* ds_dout, const T* points, const T* rotation, const T* translation, const T* out_weight,       \
-        const T* point_weight, T* ds_dpoints, T* ds_drotation, T* ds_dtranslation, T* ds_dbackground,          \
-        T* ds_dout_weight, T* ds_dpoint_weight, void* workspace, size_t workspace_bytes) {                     \
-        return dpr::pullback_smooth_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, ds_dout, points,     \
-                                            rotation, translation, out_weight, point_weight, ds_dpoints,       \
-                                            ds_drotation, ds_dtranslation, ds_dbackground, ds_dout_weight,     \
-                                            ds_dpoint_weight, workspace, workspace_bytes);                     \
-    }
-DPR_DEFINE_SMOOTH(f32, float)
-DPR_DEFINE_SMOOTH(f64, double)
-#undef DPR_DEFINE_SMOOTH
-
-int dpr_resolve_algo_sample_smooth(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    int64_t G = 0;
-    if (int rc = dpr::check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = dpr::check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = dpr::check_sample_smooth_op(op, 0u)) return rc;
-    return dpr::resolve_algo_sample_smooth(DPR_ALGO_AUTO, op, n_out, grid, P);
-}
-
-#define DPR_DEFINE_SAMPLE_SMOOTH(SUF, T)                                                                       \
-    size_t dpr_workspace_bytes_sample_smooth_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,   \
-                                                      const int64_t* grid, int64_t P, int64_t B) {             \
-        return dpr::workspace_sample_smooth_impl<T>(op, algo, flags, n_in, n_out, grid, P, B);                 \
-    }                                                                                                          \
-    int dpr_sample_smooth_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,                \
-                                   const int64_t* grid, int64_t P, int64_t B, T* values, const T* image,       \
-                                   const T* points, const T* rotation, const T* translation, void* workspace,  \
-                                   size_t workspace_bytes) {                                                   \
-        return dpr::sample_smooth_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, values, image, points, \
-                                          rotation, translation, workspace, workspace_bytes);                  \
-    }                                                                                                          \
-    int dpr_sample_smooth_pullback_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,       \
-                                            const int64_t* grid, int64_t P, int64_t B, const T* ds_dvalues,    \
-                                            const T* image, const T* points, const T* rotation,                \
-                                            const T* translation, T* ds_dimage, T* ds_dpoints,                 \
-                                            T* ds_drotation, T* ds_dtranslation, void* workspace,              \
-                                            size_t workspace_bytes) {                                          \
-        return dpr::sample_smooth_pullback_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, ds_dvalues,   \
-                                                   image, points, rotation, translation, ds_dimage,            \
-                                                   ds_dpoints, ds_drotation, ds_dtranslation, workspace,       \
-                                                   workspace_bytes);                                           \
-    }
-DPR_DEFINE_SAMPLE_SMOOTH(f32, float)
-DPR_DEFINE_SAMPLE_SMOOTH(f64, double)
-#undef DPR_DEFINE_SAMPLE_SMOOTH
-
-int dpr_resolve_algo_smooth_jvp(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t K) {
-    int64_t G = 0;
-    size_t need = 0;
-    int algo = DPR_ALGO_AUTO;
-    if (int rc = dpr::check_smooth_jvp(&algo, 0u, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
-    return algo;
-}
-
-#define DPR_DEFINE_SMOOTH_JVP(SUF, T)                                                                          \
-    size_t dpr_workspace_bytes_smooth_jvp_ex_##SUF(int algo, unsigned flags, int n_in, int n_out,              \
-                                                   const int64_t* grid, int64_t P, int64_t B, int64_t K) {     \
-        return dpr::workspace_smooth_jvp_impl(algo, flags, n_in, n_out, grid, P, B, K);                        \
-    }                                                                                                          \
-    int dpr_raster_smooth_jvp_ex_##SUF(                                                                        \
-        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, \
-        int64_t K, T* out_dot, const T* points, const T* rotation, const T* translation, const T* out_weight,  \
-        const T* point_weight, const T* points_dot, const T* rotation_dot, const T* translation_dot,           \
-        const T* background_dot, const T* out_weight_dot, const T* point_weight_dot, void* workspace,          \
-        size_t workspace_bytes) {                                                                              \
-        return dpr::raster_smooth_jvp_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, K, out_dot, points, \
-                                              rotation, translation, out_weight, point_weight,                 \
-                                              dpr::JvpTangents<T>{points_dot, rotation_dot, translation_dot,   \
-                                                                  out_weight_dot, point_weight_dot},           \
-                                              background_dot, workspace, workspace_bytes);                     \
-    }
-DPR_DEFINE_SMOOTH_JVP(f32, float)
-DPR_DEFINE_SMOOTH_JVP(f64, double)
-#undef DPR_DEFINE_SMOOTH_JVP
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 namespace dpr {
 
 constexpr int kWave = 64;  // CDNA wavefront
+constexpr int kBlock = 256;  // threads per block of the per-point kernels (dpr_kernels_*.h) and of their host checks
 constexpr int kMaxChannels = 16;  // weight channels of the multi-channel entry points (dpr_raster_channels_ex_*)
 
 template <typename T> __device__ __forceinline__ T ceil_t(T x);

@@ -11,8 +11,6 @@
 
 namespace dpr {
 
-constexpr int kBlock = 256;
-
 // out[.., b] = background[b]   (src/raster.jl:27)
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_fill_background(T* __restrict__ out, int64_t G,

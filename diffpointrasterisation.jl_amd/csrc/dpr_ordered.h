@@ -1,4 +1,4 @@
-// DPR_ALGO_ORDERED entry points (dpr_ordered.hip) as dpr_api.hip calls them
+// DPR_ALGO_ORDERED entry points (dpr_ordered.hip) as dpr_api.hip, the core of the API layer, calls them
 #pragma once
 #include "dpr_tiled.h"
 

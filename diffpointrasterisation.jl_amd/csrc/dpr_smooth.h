@@ -1,5 +1,6 @@
 // The smooth splat (include/dpr.h, "SMOOTH SPLAT"): quadratic B-spline weights on 3^N cells per point.
-// Index arithmetic shared by the host plan and the kernels of dpr_smooth.hip, and the entry points dpr_api.hip calls.
+// Index arithmetic shared by the host plan and the kernels of dpr_smooth.hip, and the entry points
+// dpr_api_smooth.hip calls.
 #pragma once
 #include "dpr_tiled.h"
 
@@ -47,18 +48,20 @@ constexpr bool smooth_dims_supported(int n_in, int n_out) {
 // tiles of the grid, or 0 where DPR_ALGO_TILED cannot run the call: tile ids 0 .. tiles - 1 must stay below the
 // all-ones key and the index of a point must fit 32 bits (P <= 2^32 - 2)
 int64_t smooth_tile_count(int n_out, const int64_t* grid, int64_t P);
+// the message of every refusal that follows from smooth_tile_count == 0
+constexpr char kSmoothTiledRefused[] = "smooth DPR_ALGO_TILED: too many tiles for a 32-bit key or P > 2^32 - 2";
 // bytes of workspace of the tiled forward (0 for P = 0); independent of B
 size_t smooth_tiled_workspace_bytes(int n_out, const int64_t* grid, int64_t P);
 
 // The point kernels.  `out` holds the background already; the pullback's per-pose sums are zeroed and
-// ds_dbackground is done by the caller (dpr_api.hip).
+// ds_dbackground is done by the caller (dpr_api_smooth.hip).
 template <typename T, int NI, int NO>
 int smooth_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out, const T* points,
                       const T* rot, const T* trans, const T* ow, const T* pw);
 template <typename T, int NI, int NO>
 int smooth_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out, const T* points,
                      const T* rot, const T* trans, const T* ow, const T* pw, void* ws, size_t ws_bytes);
-// poses_per_slice / slices: the pose slicing of the linear atomic pullback (pose_slices of dpr_api.hip); with
+// poses_per_slice / slices: the pose slicing of the linear atomic pullback (pose_slices of dpr_host.h); with
 // more than one slice ds_dpoints / ds_dpoint_weight are zeroed here and added with atomics
 template <typename T, int NI, int NO>
 int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* g,
@@ -66,8 +69,8 @@ int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
                       T* d_trans, T* d_ow, T* d_pw, int poses_per_slice, int64_t slices);
 
 // Forward-mode derivative (include/dpr.h, "SMOOTH SPLAT, FORWARD MODE"): the deposits of K tangents added onto
-// out_dot, whose planes (b * K + k) hold the background tangent already (k_jvp_fill, launched by dpr_api.hip).
-// The tiled form takes smooth_fwd_tiled's workspace and bins every pose once for all K tangents.
+// out_dot, whose planes (b * K + k) hold the background tangent already (jvp_fill of dpr_host.h, called by
+// dpr_api_smooth.hip).  The tiled form takes smooth_fwd_tiled's workspace and bins every pose once for all K tangents.
 template <typename T, int NI, int NO>
 int smooth_jvp_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
                       const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan);

@@ -844,41 +844,69 @@ int smooth_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
     return DPR_OK;
 }
 
-template <typename T, int NI, int NO>
-int smooth_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out, const T* points,
-                     const T* rot, const T* trans, const T* ow, const T* pw, void* ws_, size_t ws_bytes) {
-    if (P <= 0 || B <= 0) return DPR_OK;
+// What the two tiled launchers share: the tiles and workspace pieces of a call (smooth_binning), and the binning of
+// one pose (smooth_bin_pose): keys -> sort -> ranges, which depend on the primal only.
+template <int NO> struct SmoothBinning {
+    GridDesc<NO> gd;
+    SmoothTiles<NO> tl;
+    int64_t tiles;
+    int bits;  // of a key
+    char* temp;
+    size_t temp_bytes;
+    uint32_t *keys_in, *keys_out, *idx_in, *idx_out, *start;
+};
+template <int NO>
+static int smooth_binning(const int64_t* grid, int64_t G, int64_t P, void* ws_, size_t ws_bytes,
+                          SmoothBinning<NO>* sb) {
     const int64_t tiles = smooth_tile_count(NO, grid, P);
-    if (tiles == 0)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth DPR_ALGO_TILED: too many tiles for a 32-bit key or P > 2^32 - 2");
+    if (tiles == 0) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
     const SmoothPlan pl = smooth_plan(tiles, P);
     if (!ws_ || ws_bytes < pl.total)
         return fail(DPR_ERR_WORKSPACE, "smooth DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
                     ws_ ? ws_bytes : (size_t)0);
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    const SmoothTiles<NO> tl = smooth_tiles<NO>(grid);
     char* ws = (char*)ws_;
-    uint32_t* keys_in = (uint32_t*)(ws + pl.off_keys_in);
-    uint32_t* keys_out = (uint32_t*)(ws + pl.off_keys_out);
-    uint32_t* idx_in = (uint32_t*)(ws + pl.off_idx_in);
-    uint32_t* idx_out = (uint32_t*)(ws + pl.off_idx_out);
-    uint32_t* start = (uint32_t*)(ws + pl.off_start);
-    const int bits = ord_key_bits((uint64_t)tiles);
+    sb->gd = make_grid_desc<NO>(grid, G);
+    sb->tl = smooth_tiles<NO>(grid);
+    sb->tiles = tiles;
+    sb->bits = ord_key_bits((uint64_t)tiles);
+    sb->temp = ws + pl.off_temp;
+    sb->temp_bytes = pl.temp_bytes;
+    sb->keys_in = (uint32_t*)(ws + pl.off_keys_in);
+    sb->keys_out = (uint32_t*)(ws + pl.off_keys_out);
+    sb->idx_in = (uint32_t*)(ws + pl.off_idx_in);
+    sb->idx_out = (uint32_t*)(ws + pl.off_idx_out);
+    sb->start = (uint32_t*)(ws + pl.off_start);
+    return DPR_OK;
+}
+template <typename T, int NI, int NO>
+static int smooth_bin_pose(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int64_t b, const T* points,
+                           const T* rot, const T* trans) {
     const dim3 blk(kSmBlock);
     const dim3 pgrid((unsigned)((P + kSmBlock - 1) / kSmBlock));
-    const dim3 rgrid((unsigned)((tiles + 1 + kSmBlock - 1) / kSmBlock));
+    const dim3 rgrid((unsigned)((sb.tiles + 1 + kSmBlock - 1) / kSmBlock));
+    hipLaunchKernelGGL((k_smooth_keys<T, NI, NO>), pgrid, blk, 0, st, sb.gd, sb.tl, P, b, points, rot, trans,
+                       sb.keys_in, sb.idx_in);
+    stage_mark(st);
+    DPR_HIP(radix_sort_pairs_u32(sb.temp, sb.temp_bytes, sb.keys_in, sb.keys_out, sb.idx_in, sb.idx_out, (size_t)P,
+                                 0u, (unsigned)sb.bits, st));
+    stage_mark(st);
+    hipLaunchKernelGGL(k_smooth_ranges, rgrid, blk, 0, st, (const uint32_t*)sb.keys_out, (uint32_t)P,
+                       (uint64_t)(sb.tiles + 1), sb.bits, sb.start);
+    stage_mark(st);
+    return DPR_OK;
+}
+
+template <typename T, int NI, int NO>
+int smooth_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out, const T* points,
+                     const T* rot, const T* trans, const T* ow, const T* pw, void* ws, size_t ws_bytes) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    SmoothBinning<NO> sb;
+    if (int rc = smooth_binning<NO>(grid, G, P, ws, ws_bytes, &sb)) return rc;
     for (int64_t b = 0; b < B; ++b) {
-        hipLaunchKernelGGL((k_smooth_keys<T, NI, NO>), pgrid, blk, 0, st, gd, tl, P, b, points, rot, trans, keys_in,
-                           idx_in);
-        stage_mark(st);
-        DPR_HIP(radix_sort_pairs_u32(ws + pl.off_temp, pl.temp_bytes, keys_in, keys_out, idx_in, idx_out, (size_t)P,
-                                     0u, (unsigned)bits, st));
-        stage_mark(st);
-        hipLaunchKernelGGL(k_smooth_ranges, rgrid, blk, 0, st, (const uint32_t*)keys_out, (uint32_t)P,
-                           (uint64_t)(tiles + 1), bits, start);
-        stage_mark(st);
-        hipLaunchKernelGGL((k_smooth_tile<T, NI, NO>), dim3((unsigned)tiles), blk, 0, st, gd, tl, P, b, out, points,
-                           rot, trans, ow, pw, (const uint32_t*)start, (const uint32_t*)idx_out);
+        if (int rc = smooth_bin_pose<T, NI, NO>(st, sb, P, b, points, rot, trans)) return rc;
+        hipLaunchKernelGGL((k_smooth_tile<T, NI, NO>), dim3((unsigned)sb.tiles), dim3(kSmBlock), 0, st, sb.gd, sb.tl,
+                           P, b, out, points, rot, trans, ow, pw, (const uint32_t*)sb.start,
+                           (const uint32_t*)sb.idx_out);
         stage_mark(st);
     }
     DPR_HIP(hipGetLastError());
@@ -897,45 +925,19 @@ int smooth_jvp_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
     return DPR_OK;
 }
 
-// per pose: keys -> sort -> ranges as smooth_fwd_tiled (they depend on the primal only), then ONE launch over
-// (tiles, K): a binning serves all K tangents
+// per pose: the binning of smooth_fwd_tiled, then ONE launch over (tiles, K): a binning serves all K tangents
 template <typename T, int NI, int NO>
 int smooth_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
                      const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan,
-                     void* ws_, size_t ws_bytes) {
+                     void* ws, size_t ws_bytes) {
     if (P <= 0 || B <= 0) return DPR_OK;
-    const int64_t tiles = smooth_tile_count(NO, grid, P);
-    if (tiles == 0)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth DPR_ALGO_TILED: too many tiles for a 32-bit key or P > 2^32 - 2");
-    const SmoothPlan pl = smooth_plan(tiles, P);
-    if (!ws_ || ws_bytes < pl.total)
-        return fail(DPR_ERR_WORKSPACE, "smooth DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
-                    ws_ ? ws_bytes : (size_t)0);
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    const SmoothTiles<NO> tl = smooth_tiles<NO>(grid);
-    char* ws = (char*)ws_;
-    uint32_t* keys_in = (uint32_t*)(ws + pl.off_keys_in);
-    uint32_t* keys_out = (uint32_t*)(ws + pl.off_keys_out);
-    uint32_t* idx_in = (uint32_t*)(ws + pl.off_idx_in);
-    uint32_t* idx_out = (uint32_t*)(ws + pl.off_idx_out);
-    uint32_t* start = (uint32_t*)(ws + pl.off_start);
-    const int bits = ord_key_bits((uint64_t)tiles);
-    const dim3 blk(kSmBlock);
-    const dim3 pgrid((unsigned)((P + kSmBlock - 1) / kSmBlock));
-    const dim3 rgrid((unsigned)((tiles + 1 + kSmBlock - 1) / kSmBlock));
+    SmoothBinning<NO> sb;
+    if (int rc = smooth_binning<NO>(grid, G, P, ws, ws_bytes, &sb)) return rc;
     for (int64_t b = 0; b < B; ++b) {
-        hipLaunchKernelGGL((k_smooth_keys<T, NI, NO>), pgrid, blk, 0, st, gd, tl, P, b, points, rot, trans, keys_in,
-                           idx_in);
-        stage_mark(st);
-        DPR_HIP(radix_sort_pairs_u32(ws + pl.off_temp, pl.temp_bytes, keys_in, keys_out, idx_in, idx_out, (size_t)P,
-                                     0u, (unsigned)bits, st));
-        stage_mark(st);
-        hipLaunchKernelGGL(k_smooth_ranges, rgrid, blk, 0, st, (const uint32_t*)keys_out, (uint32_t)P,
-                           (uint64_t)(tiles + 1), bits, start);
-        stage_mark(st);
-        hipLaunchKernelGGL((k_smooth_tile_jvp<T, NI, NO>), dim3((unsigned)tiles, (unsigned)K), blk, 0, st, gd, tl, P,
-                           B, b, K, out_dot, points, rot, trans, ow, pw, tan, (const uint32_t*)start,
-                           (const uint32_t*)idx_out);
+        if (int rc = smooth_bin_pose<T, NI, NO>(st, sb, P, b, points, rot, trans)) return rc;
+        hipLaunchKernelGGL((k_smooth_tile_jvp<T, NI, NO>), dim3((unsigned)sb.tiles, (unsigned)K), dim3(kSmBlock), 0,
+                           st, sb.gd, sb.tl, P, B, b, K, out_dot, points, rot, trans, ow, pw, tan,
+                           (const uint32_t*)sb.start, (const uint32_t*)sb.idx_out);
         stage_mark(st);
     }
     DPR_HIP(hipGetLastError());

@@ -1,5 +1,5 @@
-// DPR_ALGO_TILED / DPR_ALGO_CHUNKED entry points shared between dpr_api.hip, dpr_tiled.hip,
-// dpr_owner.hip, dpr_chunkown.hip and dpr_sort.hip
+// DPR_ALGO_TILED / DPR_ALGO_CHUNKED entry points shared between the API layer (dpr_api.hip and the
+// dpr_api_*.hip of the op families), dpr_tiled.hip, dpr_owner.hip, dpr_chunkown.hip and dpr_sort.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -377,6 +377,28 @@ def test_scratch_use_matches_the_allow_list():
             assert k["vgpr_spill"] == 0 and k["scratch"] == 0, short(k["demangled"])
 
 
+# Kernels two objects may both hold: dpr_chunkown.o launches the background fill and the grid sum itself, beside
+# the instantiations dpr_api.o keeps for every other caller (fill_background / grid_sum of csrc/dpr_host.h).
+TWICE_ALLOWED = {f"dpr::{k}<{t}>" for k in ("k_fill_background", "k_grid_sum") for t in ("float", "double")}
+
+
+def test_no_kernel_is_compiled_into_two_objects():
+    """Every kernel name occurs once among the code objects of libdpr.so (one per translation unit), TWICE_ALLOWED
+    excepted: a helper that launches a shared kernel is defined in one unit and declared in csrc/dpr_host.h, so a
+    new op family calls it and does not instantiate the kernel again (no GPU)."""
+    import collections
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from kernel_resources import kernel_resources, short
+
+    ks = kernel_resources()
+    count = collections.Counter(k["name"] for k in ks)
+    assert len(count) > 300, "libdpr.so should hold several hundred kernel instantiations"
+    demangled = {k["name"]: short(k["demangled"]) for k in ks}
+    twice = {demangled[n]: c for n, c in count.items() if c > 1}
+    assert twice == {name: 2 for name in TWICE_ALLOWED}, twice
+
+
 # ------------------------------------------------------------------ DPR_ALGO_AUTO, pinned
 def _auto_regret(rows, n_in):
     worst = {"raster": (1.0, None), "pullback": (1.0, None)}

@@ -416,7 +416,7 @@ def test_sample_pullback(dev, name, algo, npdt, tdt):
 
 @pytest.mark.parametrize("npdt,tdt", DTYPES)
 def test_pose_slices_of_the_direct_kernels(dev, npdt, tdt):
-    """k_sample_fwd, k_sample_bwd and k_jvp_atomic walk the poses in slices (pose_slices in csrc/dpr_api.hip):
+    """k_sample_fwd, k_sample_bwd and k_jvp_atomic walk the poses in slices (pose_slices of csrc/dpr_host.h):
     P = 40 000 is pblocks = ceil(40000 / 256) = 157 blocks of points, under 2048, so the poses are sliced:
     slices = ceil(2048 / 157) = 14 (not above B = 37), poses per slice = ceil(37 / 14) = 3, slices =
     ceil(37 / 3) = 13 -- twelve slices of three poses and a last slice of one."""

@@ -6,7 +6,7 @@ round of k_ord_reduce), on tiny grids.  Part B: a whole plane, pose or cloud pas
 the smallest size at which a 32-bit offset can show).  Each test asserts on its own shape that it crosses the limit it
 names; test_shapes_cross_the_limit_they_name_and_no_other recomputes that on the CPU from include/dpr.h.
 
-What guards what (csrc/dpr_api.hip unless another file is named):
+What guards what (csrc/dpr_api.hip, or the family's own csrc/dpr_api_*.hip, unless another file is named):
 
   fill_background    `out + k0 * G`, `bg + k0`, cut inside a pose    test_channels_planes_across_the_launch_cut
                      cut between poses                               test_channels_poses_across_the_pose_stride,
@@ -16,7 +16,7 @@ What guards what (csrc/dpr_api.hip unless another file is named):
                                                                      test_clouds_poses_across_the_launch_cuts,
                                                                      test_smooth_poses_across_the_launch_cuts
   k_fwd_atomic_ch    pose stride over gridDim.y = 65535              test_channels_poses_across_the_pose_stride
-  raster_jvp_run     `q0` loop; k_jvp_fill: q -> bg_dot[k * B + b]   test_jvp_planes_across_the_launch_cut
+  jvp_fill           `q0` loop; k_jvp_fill: q -> bg_dot[k * B + b]   test_jvp_planes_across_the_launch_cut
   k_clouds_fwd_atomic, k_clouds_bwd_atomic: pose stride              test_clouds_poses_across_the_launch_cuts
   k_clouds_fwd_tile, k_clouds_bwd_tile, k_clouds_reduce: `b0`        test_clouds_poses_across_the_launch_cuts
   pullback_ordered   (dpr_ordered.hip) `g + b0 * G`, `rk.target += b0 * G`, `part_grid + b0 * gchunks * 2`, and
@@ -1216,7 +1216,7 @@ def test_shapes_cross_the_limit_they_name_and_no_other():
     s = A_ORD_CELLS
     assert STAGE < -(-cells(s["grid"]) // CELL_CHUNK) <= 2 * STAGE and -(-s["P"] // POINT_CHUNK) <= STAGE
     assert s["B"] <= LAUNCH and s["B"] * 15 <= REDUCE_BLOCKS and cells(s["grid"]) * s["B"] < 2 ** 31
-    # the smooth splat: the pose stride of the forward, and pose_slices (csrc/dpr_api.hip) for the pullback: 2 blocks of
+    # the smooth splat: the pose stride of the forward, and pose_slices (csrc/dpr_host.h) for the pullback: 2 blocks of
     # 256 points, 1024 slices wanted, 65 poses per slice, 1010 slices; the poses around the cut lie in three of them
     # smooth sampling: the same slices for the forward and the pullback; values and ds_dvalues stay far below 2^32;
     # the last slice is partial (15 poses: the b_hi clamp) and the second block of points has idle threads

@@ -1,8 +1,8 @@
 """Smooth sampling (k_sample_smooth_fwd, k_sample_smooth_bwd and the TILED pullback's planes, csrc/dpr_smooth.hip and
-the driver in csrc/dpr_api.hip) in the regimes the other op families are held to: the clustered clouds with cell-face
-and NaN / Inf points, a bound per value in fp32, the TILED and AUTO pullback on heavy multi-tile planes, ds_dvalues of
-rejected points, the key-bit and thin-grid edges of the tiled planes, several poses per slice, the pose order of one
-slice, and sample_smooth_ad on both algorithms.
+the driver in csrc/dpr_api_smooth.hip) in the regimes the other op families are held to: the clustered clouds with
+cell-face and NaN / Inf points, a bound per value in fp32, the TILED and AUTO pullback on heavy multi-tile planes,
+ds_dvalues of rejected points, the key-bit and thin-grid edges of the tiled planes, several poses per slice, the pose
+order of one slice, and sample_smooth_ad on both algorithms.
 
 Every expectation is tests/sample_smooth_reference.py (`SSR`) in fp64 on inputs rounded to fp32 once and used for both
 dtypes.  The hard inputs are smooth_input("H3" | "H2_22" | "H2_32") of tests/test_smooth_hard_gpu.py (its table has

@@ -106,9 +106,9 @@ def test_resolve_algo_smooth_jvp_matches_the_recorded_table():
         assert dpr_amd.resolve_algo_smooth_jvp(row["grid"], row["P"], row["B"], row["n_in"], row["K"]) == row["auto"]
         t = row["ms"]
         assert t[row["auto"]] <= 1.15 * min(t.values()), row
-    # The rule the table decided (csrc/dpr_api.hip): TILED from P * K = 1e5 on a 3-D grid and 4e5 on a 2-D grid, where
-    # the tiled path can run the call; whatever B; never another algorithm.  For K = 1 on a 3-D grid that is the
-    # smooth forward's rule for one pose.
+    # The rule the table decided (csrc/dpr_api_smooth.hip): TILED from P * K = 1e5 on a 3-D grid and 4e5 on a 2-D grid,
+    # where the tiled path can run the call; whatever B; never another algorithm.  For K = 1 on a 3-D grid that is
+    # the smooth forward's rule for one pose.
     for n_in, n_out in PAIRS:
         work = 100_000 if n_out == 3 else 400_000
         for grid in ((8,) * n_out, (128,) * n_out, (1000,) * n_out if n_out == 2 else (512, 512, 512)):
