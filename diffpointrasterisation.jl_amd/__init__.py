@@ -24,6 +24,8 @@ from .sample_smooth import (resolve_algo_sample_smooth, sample_smooth, sample_sm
                             sample_smooth_pullback_, workspace_bytes_sample_smooth)
 from .smooth_jvp import (raster_smooth_jvp, raster_smooth_jvp_, resolve_algo_smooth_jvp,
                          workspace_bytes_smooth_jvp)
+from .smooth_clouds import (raster_pullback_smooth_clouds_, raster_smooth_clouds, raster_smooth_clouds_,
+                            raster_smooth_clouds_ad, resolve_algo_smooth_clouds, workspace_bytes_smooth_clouds)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -45,4 +47,6 @@ __all__ = [
     "sample_smooth", "sample_smooth_", "sample_smooth_pullback_", "sample_smooth_ad", "resolve_algo_sample_smooth",
     "workspace_bytes_sample_smooth",
     "raster_smooth_jvp", "raster_smooth_jvp_", "resolve_algo_smooth_jvp", "workspace_bytes_smooth_jvp",
+    "raster_smooth_clouds", "raster_smooth_clouds_", "raster_pullback_smooth_clouds_", "raster_smooth_clouds_ad",
+    "resolve_algo_smooth_clouds", "workspace_bytes_smooth_clouds",
 ]

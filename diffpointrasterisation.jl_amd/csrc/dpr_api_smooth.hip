@@ -1,5 +1,5 @@
-// The smooth entry points of libdpr -- splat, sampling and forward mode: host checks, AUTO rules and C ABI (core:
-// dpr_api.hip; kernels and their launches: dpr_smooth.hip).
+// The smooth entry points of libdpr -- splat, sampling, forward mode and per-pose clouds: host checks, AUTO rules and
+// C ABI (core: dpr_api.hip; kernels and their launches: dpr_smooth.hip).
 #include <hip/hip_runtime.h>
 
 #include "dpr_host.h"
@@ -375,6 +375,146 @@ static size_t workspace_smooth_jvp_impl(int algo, unsigned flags, int n_in, int 
     return need;
 }
 
+// ---------------------------------------------------------------- smooth splat, per-pose clouds
+// dpr_raster_smooth_clouds_ex_* / dpr_raster_pullback_smooth_clouds_ex_* (include/dpr.h, "SMOOTH SPLAT, PER-POSE
+// CLOUDS"; kernels: dpr_smooth.hip).  DPR_ALGO_ATOMIC: forward and pullback, one thread per (point, pose).
+// DPR_ALGO_TILED: forward, the poses binned in groups (smooth_clouds_group; DPR_FLAG_MAX_POSE_GROUP honoured).
+static int smooth_clouds_max_group(unsigned flags) { return (int)((flags >> 8) & 0xffu); }
+
+// AUTO (dpr_resolve_algo_smooth_clouds), from the shape alone (profiles/smooth_clouds_probe.txt, fp32, uniform clouds
+// in generation order, times in ms TILED / ATOMIC).  The pullback is DPR_ALGO_ATOMIC.  The forward is DPR_ALGO_TILED
+// where both hold, DPR_ALGO_ATOMIC otherwise:
+//  - the default GROUP holds enough points, bg * P >= 1e5 on a 3-D grid and 4e5 on a 2-D grid: the key pass, the
+//    sort, the start table and the tile launch are paid once per group of bg poses, so the smooth forward's rule is
+//    applied to bg * P in the place of P.  3-D, 128^3: 1e4 x 4 poses 0.115 / 0.091, 3e4 x 4 0.141 / 0.174, 1e4 x 16
+//    0.219 / 0.229, 1e5 x 16 0.357 / 1.71.  2-D, 128^2: 1e4 x 16 0.112 / 0.107, 1e4 x 32 0.171 / 0.169, 3e4 x 16
+//    0.182 / 0.232 (512^2: 0.194 / 0.230), 1e4 x 64 0.198 / 0.287, 1e5 x 64 0.347 / 2.46.  The smooth forward's 5e5
+//    would have lost the two 3e4 x 16 rows by 1.27x and 1.19x; between 3.2e5 and 4.8e5 nothing was measured.
+//  - a cloud holds at least 4 points per tile of its pose's grid, P >= 4 * tiles: every non-empty (pose, tile)
+//    workgroup zeroes and flushes its LDS tile whatever it holds.  256^3 (16 384 tiles): 1e4 x 16 poses 0.664 /
+//    0.386 and 3e4 x 4 0.285 / 0.202 (0.6 and 1.8 points per tile), 1e5 x 4 0.388 / 0.489 and 1e5 x 16 1.13 / 1.84
+//    (6.1); 128^3 (2048 tiles): 1e4 x 16 a tie at 4.9.  No 2-D row comes near this bound (512^2 has 256 tiles).
+constexpr int64_t kSmoothCloudsTiledMinWork3D = 100000;
+constexpr int64_t kSmoothCloudsTiledMinWork2D = 400000;
+constexpr int64_t kSmoothCloudsTiledMinPointsPerTile = 4;
+static int resolve_algo_smooth_clouds(int algo, int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
+    if (algo != DPR_ALGO_AUTO) return algo;
+    if (op != DPR_OP_RASTER) return DPR_ALGO_ATOMIC;
+    const int64_t bg = smooth_clouds_group(n_out, grid, P, B, 0);
+    if (bg == 0) return DPR_ALGO_ATOMIC;
+    const int64_t min_work = n_out == 3 ? kSmoothCloudsTiledMinWork3D : kSmoothCloudsTiledMinWork2D;
+    const int64_t tiles = smooth_tile_count(n_out, grid, P);
+    return bg * P >= min_work && P / kSmoothCloudsTiledMinPointsPerTile >= tiles ? DPR_ALGO_TILED : DPR_ALGO_ATOMIC;
+}
+
+// bytes of workspace, or (size_t)-1 (message recorded) when the algorithm cannot run the call
+static size_t smooth_clouds_workspace_bytes(int op, int algo, unsigned flags, int n_out, const int64_t* grid,
+                                            int64_t P, int64_t B) {
+    if (algo == DPR_ALGO_ATOMIC) return 0;
+    if (algo != DPR_ALGO_TILED) {
+        fail(DPR_ERR_UNSUPPORTED_ALGO,
+             "the smooth splat of per-pose clouds runs on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d", algo);
+        return (size_t)-1;
+    }
+    if (op != DPR_OP_RASTER) {
+        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth pullback runs on DPR_ALGO_ATOMIC only");
+        return (size_t)-1;
+    }
+    const size_t n = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, smooth_clouds_max_group(flags));
+    if (n == (size_t)-1)
+        fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
+    return n;
+}
+
+// the checks every entry point and query of the family shares, in the order of the two parent families; *G and the
+// resolved *algo come back, *need: workspace
+static int check_smooth_clouds(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
+                               int64_t B, int64_t* G, size_t* need) {
+    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
+    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
+    if (int rc = check_smooth(op, flags)) return rc;
+    // 64-bit offsets: cloud b starts at b * P * n_in, plane b at b * G
+    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (B > 0 && (P > ((int64_t)1 << 60) / B / n_in || *G > ((int64_t)1 << 62) / B))
+        return fail(DPR_ERR_INVALID_ARG, "B * P * n_in or the image (G * B) too large");
+    *algo = resolve_algo_smooth_clouds(*algo, op, n_out, grid, P, B);
+    *need = smooth_clouds_workspace_bytes(op, *algo, flags, n_out, grid, P, B);
+    return *need == (size_t)-1 ? DPR_ERR_UNSUPPORTED_ALGO : DPR_OK;
+}
+
+template <typename T>
+static int raster_smooth_clouds_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                     int64_t P, int64_t B, T* out, const T* points, const T* rot, const T* trans,
+                                     const T* bg, const T* ow, const T* pw, void* ws, size_t ws_bytes) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_smooth_clouds(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return rc;
+    if (B == 0) return DPR_OK;
+    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
+    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
+        return fail(DPR_ERR_WORKSPACE, "smooth splat of per-pose clouds (algorithm %d) needs %zu workspace bytes, got %zu",
+                    algo, need, ws ? ws_bytes : (size_t)0);
+    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    fill_background(st, out, G, B, bg);
+    stage_mark(st);
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        const int rc = algo == DPR_ALGO_TILED
+                           ? smooth_clouds_fwd_tiled<T, NI, NO>(st, grid, G, P, B, smooth_clouds_max_group(flags), out,
+                                                                points, rot, trans, ow, pw, ws, ws_bytes)
+                           : smooth_clouds_fwd_atomic<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, ow, pw);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+template <typename T>
+static int pullback_smooth_clouds_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
+                                       const int64_t* grid, int64_t P, int64_t B, const T* g, const T* points,
+                                       const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts, T* d_rot,
+                                       T* d_trans, T* d_bg, T* d_ow, T* d_pw, void* ws, size_t ws_bytes) {
+    (void)ws_bytes;
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_smooth_clouds(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return rc;
+    if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
+    if (B == 0) return DPR_OK;  // (every output is empty)
+    if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
+    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+    if (!d_rot || !d_trans || !d_bg || !d_ow) return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
+    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
+        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * n_out * n_in), st));
+    DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * n_out), st));
+    DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
+    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
+    grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
+    stage_mark(st);
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        const int rc = smooth_clouds_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
+            st, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+static size_t workspace_smooth_clouds_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                           int64_t P, int64_t B) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (check_smooth_clouds(op, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return (size_t)-1;
+    return need;
+}
+
 }  // namespace dpr
 
 extern "C" {
@@ -478,5 +618,42 @@ int dpr_resolve_algo_smooth_jvp(int n_in, int n_out, const int64_t* grid, int64_
 DPR_DEFINE_SMOOTH_JVP(f32, float)
 DPR_DEFINE_SMOOTH_JVP(f64, double)
 #undef DPR_DEFINE_SMOOTH_JVP
+
+int dpr_resolve_algo_smooth_clouds(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
+    int64_t G = 0;
+    size_t need = 0;
+    int algo = DPR_ALGO_AUTO;
+    if (int rc = dpr::check_smooth_clouds(op, &algo, 0u, n_in, n_out, grid, P, B, &G, &need)) return rc;
+    return algo;
+}
+
+#define DPR_DEFINE_SMOOTH_CLOUDS(SUF, T)                                                                       \
+    size_t dpr_workspace_bytes_smooth_clouds_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,   \
+                                                      const int64_t* grid, int64_t P, int64_t B) {             \
+        return dpr::workspace_smooth_clouds_impl(op, algo, flags, n_in, n_out, grid, P, B);                    \
+    }                                                                                                          \
+    int dpr_raster_smooth_clouds_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,         \
+                                          const int64_t* grid, int64_t P, int64_t B, T* out, const T* points,  \
+                                          const T* rotation, const T* translation, const T* background,        \
+                                          const T* out_weight, const T* point_weight, void* workspace,         \
+                                          size_t workspace_bytes) {                                            \
+        return dpr::raster_smooth_clouds_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, out, points,    \
+                                                 rotation, translation, background, out_weight, point_weight,  \
+                                                 workspace, workspace_bytes);                                  \
+    }                                                                                                          \
+    int dpr_raster_pullback_smooth_clouds_ex_##SUF(                                                            \
+        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, \
+        const T* ds_dout, const T* points, const T* rotation, const T* translation, const T* out_weight,       \
+        const T* point_weight, T* ds_dpoints, T* ds_drotation, T* ds_dtranslation, T* ds_dbackground,          \
+        T* ds_dout_weight, T* ds_dpoint_weight, void* workspace, size_t workspace_bytes) {                     \
+        return dpr::pullback_smooth_clouds_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, ds_dout,      \
+                                                   points, rotation, translation, out_weight, point_weight,    \
+                                                   ds_dpoints, ds_drotation, ds_dtranslation, ds_dbackground,  \
+                                                   ds_dout_weight, ds_dpoint_weight, workspace,                \
+                                                   workspace_bytes);                                           \
+    }
+DPR_DEFINE_SMOOTH_CLOUDS(f32, float)
+DPR_DEFINE_SMOOTH_CLOUDS(f64, double)
+#undef DPR_DEFINE_SMOOTH_CLOUDS
 
 }  // extern "C"

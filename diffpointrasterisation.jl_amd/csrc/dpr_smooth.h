@@ -68,6 +68,31 @@ int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
                       const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts, T* d_rot,
                       T* d_trans, T* d_ow, T* d_pw, int poses_per_slice, int64_t slices);
 
+// Per-pose clouds (include/dpr.h, "SMOOTH SPLAT, PER-POSE CLOUDS"): cloud b at points + b * P * NI, its weights at
+// pw + b * P, and ds_dpoints / ds_dpoint_weight likewise.  The same contract with the caller as above.
+// The tiled forward bins a GROUP of poses with one key pass, one sort, one start table and one tile launch.
+// Poses per group: the largest bg <= B with bg * max(P, tiles) <= kSmoothCloudsGroupWork, at least 1, at most
+// max_group where that is > 0 (DPR_FLAG_MAX_POSE_GROUP); 0 where smooth_tile_count refuses the shape.  With bg > 1
+// the keys b_local * tiles + tile stay below 2^24 and the flat indices b_local * P + p too.  (The value and the
+// reason for it: include/dpr.h.)
+constexpr int64_t kSmoothCloudsGroupWork = (int64_t)1 << 24;
+int64_t smooth_clouds_group(int n_out, const int64_t* grid, int64_t P, int64_t B, int max_group);
+// bytes of workspace of the tiled forward: smooth_tiled_workspace_bytes' layout for (bg * tiles, bg * P), reused from
+// group to group; equal to smooth_tiled_workspace_bytes(n_out, grid, P) for a group of one; (size_t)-1 where refused
+size_t smooth_clouds_tiled_workspace_bytes(int n_out, const int64_t* grid, int64_t P, int64_t B, int max_group);
+template <typename T, int NI, int NO>
+int smooth_clouds_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out,
+                             const T* points, const T* rot, const T* trans, const T* ow, const T* pw);
+template <typename T, int NI, int NO>
+int smooth_clouds_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int max_group,
+                            T* out, const T* points, const T* rot, const T* trans, const T* ow, const T* pw,
+                            void* ws, size_t ws_bytes);
+// one thread per (point, pose): no pose slices, every point gradient one plain store
+template <typename T, int NI, int NO>
+int smooth_clouds_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* g,
+                             const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts,
+                             T* d_rot, T* d_trans, T* d_ow, T* d_pw);
+
 // Forward-mode derivative (include/dpr.h, "SMOOTH SPLAT, FORWARD MODE"): the deposits of K tangents added onto
 // out_dot, whose planes (b * K + k) hold the background tangent already (jvp_fill of dpr_host.h, called by
 // dpr_api_smooth.hip).  The tiled form takes smooth_fwd_tiled's workspace and bins every pose once for all K tangents.

@@ -19,6 +19,10 @@
 //   forward-mode derivative   k_smooth_jvp_atomic / k_smooth_tile_jvp (include/dpr.h, "SMOOTH SPLAT, FORWARD MODE"):
 //                             the two forward shapes with the deposit of a tangent in the place of the weight
 //                             product; the tiled path bins a pose once for all K tangents
+//   per-pose clouds           k_smooth_clouds_fwd_atomic / k_smooth_clouds_bwd / k_smooth_clouds_keys /
+//                             k_smooth_clouds_tile (include/dpr.h, "SMOOTH SPLAT, PER-POSE CLOUDS"): pose b reads
+//                             cloud b; a thread per (point, pose); the tiled forward bins a GROUP of poses with one
+//                             key pass, one sort, one start table and one launch of (poses x tiles) workgroups
 #include <hip/hip_runtime.h>
 
 #include "../../include/dpr.h"
@@ -800,6 +804,269 @@ __global__ __launch_bounds__(kSmBlock) void k_smooth_tile_jvp(GridDesc<NO> gd, S
     }
 }
 
+// ---------------------------------------------------------------- per-pose clouds
+// include/dpr.h, "SMOOTH SPLAT, PER-POSE CLOUDS": pose b reads cloud b (points at b * P * NI, weights at b * P).
+// Plane b and the gradients of pose b are those of the single-pose kernels above for (cloud b, pose b).  These are
+// copies of k_smooth_fwd_atomic / k_smooth_bwd / k_smooth_keys / k_smooth_tile, not shared bodies: the single-pose
+// kernels keep their registers.
+
+// One thread per (point, pose): a block lies inside one pose, the poses strided over gridDim.y.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_clouds_fwd_atomic(GridDesc<NO> gd, int64_t P, int64_t B,
+                                                                       T* __restrict__ out,
+                                                                       const T* __restrict__ points,
+                                                                       const T* __restrict__ rot,
+                                                                       const T* __restrict__ trans,
+                                                                       const T* __restrict__ ow,
+                                                                       const T* __restrict__ pw) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (p >= P) return;
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+        T pt[NI];
+        load_point<T, NI>(points + b * P * NI, p, pt);
+        const T pwi = pw ? pw[b * P + p] : T(1);
+        const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b);
+        int j0[NO];
+        T u[NO];
+        if (!smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) continue;
+        const T w = ps.ow * pwi;
+        const SmoothAxes<T, NO> ax = smooth_axes<T, NO>(j0, u, gd);
+        T* o = out + b * gd.G;
+#pragma unroll
+        for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+            const bool in2 = NO == 3 ? ax.in[NO - 1][k2] : true;
+            const int off2 = NO == 3 ? ax.off[NO - 1][k2] : 0;
+            const T w2 = NO == 3 ? ax.w[NO - 1][k2] * w : w;
+#pragma unroll
+            for (int k1 = 0; k1 < 3; ++k1) {
+                const T w12 = ax.w[1][k1] * w2;
+#pragma unroll
+                for (int k0 = 0; k0 < 3; ++k0)
+                    if (in2 && ax.in[1][k1] && ax.in[0][k0])
+                        atomic_add<T>(o + (off2 + ax.off[1][k1] + ax.off[0][k0]), ax.w[0][k0] * w12);
+            }
+        }
+    }
+}
+
+// Pullback, one thread per (point, pose), a block inside one pose: the point gradients are one plain store each
+// (a rejected point stores 0), the per-pose sums go wave -> block -> one atomic per scalar per block.  Pre-zeroed:
+// ds_drotation, ds_dtranslation, ds_dout_weight.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_clouds_bwd(
+    GridDesc<NO> gd, int64_t P, int64_t B, const T* __restrict__ g, const T* __restrict__ points,
+    const T* __restrict__ rot, const T* __restrict__ trans, const T* __restrict__ ow, const T* __restrict__ pw,
+    T* __restrict__ ds_dpoints, T* __restrict__ ds_drotation, T* __restrict__ ds_dtranslation,
+    T* __restrict__ ds_dout_weight, T* __restrict__ ds_dpoint_weight) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    constexpr int NV = NO * NI + NO + 1;  // dR | dt | d out_weight
+    constexpr int NW = kSmBlock / kWave;
+    __shared__ T red[NW][NV];
+
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    const bool live = p < P;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {  // (uniform over the block)
+        const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b);
+        const int64_t q = b * P + p;  // (point, pose) index of the point gradients
+        T pt[NI];
+#pragma unroll
+        for (int j = 0; j < NI; ++j) pt[j] = T(0);
+        if (live) load_point<T, NI>(points + b * P * NI, p, pt);
+        const T pwi = (live && pw) ? pw[q] : T(1);
+        T vals[NV], gpt[NI], gpw = T(0);
+#pragma unroll
+        for (int k = 0; k < NV; ++k) vals[k] = T(0);
+#pragma unroll
+        for (int j = 0; j < NI; ++j) gpt[j] = T(0);
+        int j0[NO];
+        T u[NO];
+        if (live && smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) {
+            const T* gb = g + b * gd.G;
+            T dcoord[NO], W;
+            smooth_point_backward<T, NO>(j0, u, gd, [&](int off) { return gb[off]; }, dcoord, W);
+            const T opw = ps.ow * pwi;
+            T scaled[NO];
+#pragma unroll
+            for (int n = 0; n < NO; ++n) scaled[n] = (dcoord[n] * opw) * (T(gd.n[n]) / T(2));
+#pragma unroll
+            for (int n = 0; n < NO; ++n) {
+#pragma unroll
+                for (int j = 0; j < NI; ++j) vals[n + j * NO] = scaled[n] * pt[j];
+                vals[NO * NI + n] = scaled[n];
+            }
+            vals[NO * NI + NO] = W * pwi;
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {  // rotation' * scaled
+                T v = ps.R[0 + j * NO] * scaled[0];
+#pragma unroll
+                for (int n = 1; n < NO; ++n) v = v + ps.R[n + j * NO] * scaled[n];
+                gpt[j] += v;
+            }
+            gpw += W * ps.ow;
+        }
+        if (live) {
+#pragma unroll
+            for (int j = 0; j < NI; ++j) ds_dpoints[q * NI + j] = gpt[j];
+            if (ds_dpoint_weight) ds_dpoint_weight[q] = gpw;
+        }
+        // per-pose sums: wave -> block -> one atomic per scalar per block
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const T s = wave_sum<T>(vals[k]);
+            if (lane == 0) red[wave][k] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < NV) {
+            T s = red[0][threadIdx.x];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) s += red[w][threadIdx.x];
+            const int k = threadIdx.x;
+            if (s != T(0)) {
+                if (k < NO * NI)
+                    atomic_add<T>(ds_drotation + b * (NO * NI) + k, s);
+                else if (k < NO * NI + NO)
+                    atomic_add<T>(ds_dtranslation + b * NO + (k - NO * NI), s);
+                else
+                    atomic_add<T>(ds_dout_weight + b, s);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// DPR_ALGO_TILED, the binning of a GROUP of nb poses b0 .. b0 + nb - 1 at once.  `points` / `pw` are those of the
+// group's first cloud; the flat index q = b_local * P + p addresses them directly (consecutive clouds are
+// contiguous).  key = b_local * tiles + (tile of the clamped centre cell, as k_smooth_keys), all ones for a rejected
+// point; value = q.  Block blockIdx.x covers points (blockIdx.x % blocks_per_pose) * 256 .. of pose
+// blockIdx.x / blocks_per_pose: a block lies inside one pose.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_clouds_keys(GridDesc<NO> gd, SmoothTiles<NO> tl, uint32_t tiles,
+                                                                 int64_t P, uint32_t blocks_per_pose, int64_t b0,
+                                                                 const T* __restrict__ points,
+                                                                 const T* __restrict__ rot,
+                                                                 const T* __restrict__ trans,
+                                                                 uint32_t* __restrict__ keys,
+                                                                 uint32_t* __restrict__ idx) {
+    const uint32_t bl = blockIdx.x / blocks_per_pose;
+    const int64_t p = (int64_t)(blockIdx.x % blocks_per_pose) * kSmBlock + threadIdx.x;
+    if (p >= P) return;
+    const int64_t q = (int64_t)bl * P + p;
+    T pt[NI];
+    load_point<T, NI>(points, q, pt);
+    const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, nullptr, b0 + bl);
+    int j0[NO];
+    T u[NO];
+    uint32_t key = kSmoothNoKey;
+    if (smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) {
+        uint32_t stride = 1;
+        key = bl * tiles;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            const int c = j0[d] < 0 ? 0 : (j0[d] >= gd.n[d] ? gd.n[d] - 1 : j0[d]);
+            key += (uint32_t)(c / SmoothTileShape<NO>::e[d]) * stride;
+            stride *= (uint32_t)tl.nt[d];
+        }
+    }
+    keys[q] = key;
+    idx[q] = (uint32_t)q;
+}
+
+// Workgroup blockIdx.x = b_local * tiles + tile: k_smooth_tile's body for the (pose, tile)'s run of the group's
+// sorted flat indices (`count` of them: nb * P), flushed onto plane b0 + b_local.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_clouds_tile(GridDesc<NO> gd, SmoothTiles<NO> tl, uint32_t tiles,
+                                                                 uint32_t count, int64_t b0, T* __restrict__ out,
+                                                                 const T* __restrict__ points,
+                                                                 const T* __restrict__ rot,
+                                                                 const T* __restrict__ trans,
+                                                                 const T* __restrict__ ow, const T* __restrict__ pw,
+                                                                 const uint32_t* __restrict__ start,
+                                                                 const uint32_t* __restrict__ idx) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    constexpr int NC = smooth_lds_cells<NO>();
+    __shared__ double cells[NC];
+    // the run of the sorted indices, clamped: a damaged table can shorten a walk, never leave idx[0 .. count)
+    uint32_t begin, end;
+    ord_cell_range(start, blockIdx.x, count, begin, end);
+    if (begin >= end) return;  // (uniform: an empty (pose, tile) adds nothing)
+    const int64_t b = b0 + (int64_t)(blockIdx.x / tiles);
+    int org[NO];  // first cell of the tile
+    {
+        uint32_t t = blockIdx.x % tiles;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            org[d] = (int)(t % (uint32_t)tl.nt[d]) * SmoothTileShape<NO>::e[d];
+            t /= (uint32_t)tl.nt[d];
+        }
+    }
+    for (int i = threadIdx.x; i < NC; i += kSmBlock) cells[i] = 0.0;
+    __syncthreads();
+
+    const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b);
+    for (uint32_t i = begin + threadIdx.x; i < end; i += kSmBlock) {
+        const uint32_t q = idx[i];
+        if (q >= count) continue;  // (never for an index k_smooth_clouds_keys wrote)
+        T pt[NI];
+        load_point<T, NI>(points, (int64_t)q, pt);
+        int j0[NO];
+        T u[NO];
+        if (!smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) continue;
+        const T w = ps.ow * (pw ? pw[q] : T(1));
+        // LDS cell l = (cell - org) + 1 per axis; only cells of the grid that lie on the tile + halo are added
+        T wt[NO][3];
+        int loff[NO][3];
+        bool in[NO][3];
+        int lstride = 1;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            spline_weights<T>(u[d], wt[d]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int c = j0[d] + k - 1, l = c - org[d] + 1;
+                in[d][k] = c >= 0 && c < gd.n[d] && l >= 0 && l < SmoothTileShape<NO>::e[d] + 2;
+                loff[d][k] = in[d][k] ? l * lstride : 0;
+            }
+            lstride *= SmoothTileShape<NO>::e[d] + 2;
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+            const bool in2 = NO == 3 ? in[NO - 1][k2] : true;
+            const int off2 = NO == 3 ? loff[NO - 1][k2] : 0;
+            const T w2 = NO == 3 ? wt[NO - 1][k2] * w : w;
+#pragma unroll
+            for (int k1 = 0; k1 < 3; ++k1) {
+                const T w12 = wt[1][k1] * w2;
+#pragma unroll
+                for (int k0 = 0; k0 < 3; ++k0)
+                    if (in2 && in[1][k1] && in[0][k0])
+                        atomicAdd(&cells[off2 + loff[1][k1] + loff[0][k0]], (double)(wt[0][k0] * w12));
+            }
+        }
+    }
+    __syncthreads();
+
+    // flush: consecutive threads walk axis 0 of the tile + halo, so a wave's atomics cover rows of the plane
+    T* o = out + b * gd.G;
+    for (int i = threadIdx.x; i < NC; i += kSmBlock) {
+        const double v = cells[i];
+        int rest = i, off = 0, stride = 1;
+        bool in_grid = true;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            const int ext = SmoothTileShape<NO>::e[d] + 2;
+            const int c = org[d] + (rest % ext) - 1;
+            rest /= ext;
+            in_grid = in_grid && c >= 0 && c < gd.n[d];
+            off += in_grid ? c * stride : 0;
+            stride *= gd.n[d];
+        }
+        if (in_grid && v != 0.0) atomic_add<T>(o + off, (T)v);
+    }
+}
+
 // ---------------------------------------------------------------- host
 int64_t smooth_tile_count(int n_out, const int64_t* grid, int64_t P) {
     if (P > (int64_t)0xfffffffeLL) return 0;
@@ -810,7 +1077,8 @@ int64_t smooth_tile_count(int n_out, const int64_t* grid, int64_t P) {
 struct SmoothPlan {
     size_t off_keys_in, off_keys_out, off_idx_in, off_idx_out, off_temp, temp_bytes, off_start, total;
 };
-static SmoothPlan smooth_plan(int64_t tiles, int64_t P) {
+// (P_last: a second, smaller count the same storage must sort -- the last group of a per-pose cloud call)
+static SmoothPlan smooth_plan(int64_t tiles, int64_t P, int64_t P_last = 0) {
     SmoothPlan pl{};
     if (P <= 0) return pl;
     size_t o = 0;
@@ -820,6 +1088,7 @@ static SmoothPlan smooth_plan(int64_t tiles, int64_t P) {
     pl.off_idx_out = o;  o += align_up((size_t)P * 4);
     pl.off_temp = o;
     pl.temp_bytes = radix_pairs_temp_bytes(P);
+    if (P_last > 0 && radix_pairs_temp_bytes(P_last) > pl.temp_bytes) pl.temp_bytes = radix_pairs_temp_bytes(P_last);
     o += align_up(pl.temp_bytes);
     pl.off_start = o;    o += align_up((size_t)(tiles + 1) * 4);
     pl.total = o;
@@ -907,6 +1176,96 @@ int smooth_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, 
         hipLaunchKernelGGL((k_smooth_tile<T, NI, NO>), dim3((unsigned)sb.tiles), dim3(kSmBlock), 0, st, sb.gd, sb.tl,
                            P, b, out, points, rot, trans, ow, pw, (const uint32_t*)sb.start,
                            (const uint32_t*)sb.idx_out);
+        stage_mark(st);
+    }
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+// ---- per-pose clouds
+int64_t smooth_clouds_group(int n_out, const int64_t* grid, int64_t P, int64_t B, int max_group) {
+    const int64_t tiles = smooth_tile_count(n_out, grid, P);
+    if (tiles == 0) return 0;
+    const int64_t per_pose = P > tiles ? P : tiles;
+    int64_t bg = kSmoothCloudsGroupWork / per_pose;
+    if (bg > B) bg = B;
+    if (max_group > 0 && bg > max_group) bg = max_group;
+    return bg < 1 ? 1 : bg;
+}
+
+size_t smooth_clouds_tiled_workspace_bytes(int n_out, const int64_t* grid, int64_t P, int64_t B, int max_group) {
+    const int64_t bg = smooth_clouds_group(n_out, grid, P, B, max_group);
+    if (bg == 0) return (size_t)-1;
+    return smooth_plan(bg * smooth_tile_count(n_out, grid, P), bg * P, (B % bg) * P).total;
+}
+
+template <typename T, int NI, int NO>
+int smooth_clouds_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out,
+                             const T* points, const T* rot, const T* trans, const T* ow, const T* pw) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    dim3 g((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)(B < 65535 ? B : 65535));
+    hipLaunchKernelGGL((k_smooth_clouds_fwd_atomic<T, NI, NO>), g, dim3(kSmBlock), 0, st, gd, P, B, out, points, rot,
+                       trans, ow, pw);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+template <typename T, int NI, int NO>
+int smooth_clouds_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* g,
+                             const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts,
+                             T* d_rot, T* d_trans, T* d_ow, T* d_pw) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)(B < 65535 ? B : 65535));
+    hipLaunchKernelGGL((k_smooth_clouds_bwd<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, g, points, rot, trans,
+                       ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+// group after group of `bg` poses: keys -> sort -> start table -> tiles, four launches per GROUP; the workspace is
+// smooth_plan of (bg * tiles, bg * P), reused from group to group (the last group may hold fewer poses)
+template <typename T, int NI, int NO>
+int smooth_clouds_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int max_group,
+                            T* out, const T* points, const T* rot, const T* trans, const T* ow, const T* pw,
+                            void* ws_, size_t ws_bytes) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const int64_t bg = smooth_clouds_group(NO, grid, P, B, max_group);
+    if (bg == 0) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
+    const int64_t tiles = smooth_tile_count(NO, grid, P);
+    const SmoothPlan pl = smooth_plan(bg * tiles, bg * P, (B % bg) * P);
+    if (!ws_ || ws_bytes < pl.total)
+        return fail(DPR_ERR_WORKSPACE, "smooth clouds DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
+                    ws_ ? ws_bytes : (size_t)0);
+    char* ws = (char*)ws_;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    const SmoothTiles<NO> tl = smooth_tiles<NO>(grid);
+    uint32_t* keys_in = (uint32_t*)(ws + pl.off_keys_in);
+    uint32_t* keys_out = (uint32_t*)(ws + pl.off_keys_out);
+    uint32_t* idx_in = (uint32_t*)(ws + pl.off_idx_in);
+    uint32_t* idx_out = (uint32_t*)(ws + pl.off_idx_out);
+    uint32_t* start = (uint32_t*)(ws + pl.off_start);
+    const int64_t blocks_per_pose = (P + kSmBlock - 1) / kSmBlock;
+    const dim3 blk(kSmBlock);
+    for (int64_t b0 = 0; b0 < B; b0 += bg) {
+        const int64_t nb = B - b0 < bg ? B - b0 : bg;
+        const int64_t count = nb * P, entries = nb * tiles + 1;
+        const int bits = ord_key_bits((uint64_t)(nb * tiles));
+        const T* gpts = points + b0 * P * NI;
+        const T* gpw = pw ? pw + b0 * P : nullptr;
+        hipLaunchKernelGGL((k_smooth_clouds_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_pose)), blk, 0, st, gd,
+                           tl, (uint32_t)tiles, P, (uint32_t)blocks_per_pose, b0, gpts, rot, trans, keys_in, idx_in);
+        stage_mark(st);
+        DPR_HIP(radix_sort_pairs_u32(ws + pl.off_temp, pl.temp_bytes, keys_in, keys_out, idx_in, idx_out,
+                                     (size_t)count, 0u, (unsigned)bits, st));
+        stage_mark(st);
+        hipLaunchKernelGGL(k_smooth_ranges, dim3((unsigned)((entries + kSmBlock - 1) / kSmBlock)), blk, 0, st,
+                           (const uint32_t*)keys_out, (uint32_t)count, (uint64_t)entries, bits, start);
+        stage_mark(st);
+        hipLaunchKernelGGL((k_smooth_clouds_tile<T, NI, NO>), dim3((unsigned)(nb * tiles)), blk, 0, st, gd, tl,
+                           (uint32_t)tiles, (uint32_t)count, b0, out, gpts, rot, trans, ow, gpw,
+                           (const uint32_t*)start, (const uint32_t*)idx_out);
         stage_mark(st);
     }
     DPR_HIP(hipGetLastError());
@@ -1006,7 +1365,15 @@ int sample_smooth_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
                                              void*, size_t);                                                       \
     template int smooth_bwd_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, const T*,     \
                                               const T*, const T*, const T*, const T*, const T*, T*, T*, T*, T*,    \
-                                              T*, int, int64_t);
+                                              T*, int, int64_t);                                                   \
+    template int smooth_clouds_fwd_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, T*,    \
+                                                     const T*, const T*, const T*, const T*, const T*);            \
+    template int smooth_clouds_fwd_tiled<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, int,    \
+                                                    T*, const T*, const T*, const T*, const T*, const T*, void*,   \
+                                                    size_t);                                                       \
+    template int smooth_clouds_bwd_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t,        \
+                                                     const T*, const T*, const T*, const T*, const T*, const T*,   \
+                                                     T*, T*, T*, T*, T*);
 #define DPR_SMOOTH_INSTANTIATE_T(T) \
     DPR_SMOOTH_INSTANTIATE(T, 2, 2) DPR_SMOOTH_INSTANTIATE(T, 3, 3) DPR_SMOOTH_INSTANTIATE(T, 3, 2)
 DPR_SMOOTH_INSTANTIATE_T(float)

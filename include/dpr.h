@@ -266,6 +266,18 @@ extern "C" {
  *                        the background: rounding level, not
  *                        bit-reproducible
  *
+ *   smooth splat, per-pose clouds (dpr_raster_smooth_clouds_ex_* / dpr_raster_pullback_smooth_clouds_ex_*, see SMOOTH
+ *   SPLAT, PER-POSE CLOUDS below):
+ *   DPR_ALGO_ATOMIC      global float atomics in T, in arrival      one thread per (point, pose), one      wave -> block -> one float atomic per block:
+ *                        order: rounding level                       plain store per value, no slices, no   rounding level
+ *                                                                    accumulation: bit-reproducible
+ *   DPR_ALGO_TILED       as the smooth splat's tiled forward per
+ *   (forward only)       (pose, tile), whatever the pose groups:
+ *                        f64 LDS atomics in arrival order, rounded
+ *                        to T once per (tile, cell), <= 3^N such
+ *                        partials per cell as float atomics in T:
+ *                        rounding level, not bit-reproducible
+ *
  *   smooth splat, forward mode (dpr_raster_smooth_jvp_ex_*, see SMOOTH SPLAT, FORWARD MODE below), out_dot:
  *   DPR_ALGO_ATOMIC      global float atomics in T onto the background tangent, unordered: rounding level (lanes of
  *                        a wave with the same centre cell are first added in T in a fixed order, one atomic per group)
@@ -1033,6 +1045,90 @@ int dpr_raster_smooth_jvp_ex_f64(void *stream, int algo, unsigned flags, int n_i
                                  const double *translation_dot, const double *background_dot,
                                  const double *out_weight_dot, const double *point_weight_dot, void *workspace,
                                  size_t workspace_bytes);
+
+/* ---- SMOOTH SPLAT, PER-POSE CLOUDS: the quadratic B-spline splat with a different cloud for every pose -------------
+ * PER-POSE CLOUDS with the kernel of SMOOTH SPLAT.  For pose b, with its own cloud points[b]:
+ *     out[i.., b] = background[b] + out_weight[b] * sum_p point_weight[b, p] * Bspline_weight(i..; R_b points[b, p] + t_b)
+ * Plane b is dpr_raster_smooth_* of (grid, points[b], R_b, t_b, background[b], out_weight[b], point_weight[b]): the
+ * same centre cell j0, the same weights on 3^N cells, the same acceptance -1 <= coord_d < n_d + 1, cells outside the
+ * grid dropped one by one.  The pullback is its exact derivative and decomposes the same way: ds_dpoints[b] and
+ * ds_dpoint_weight[b] are the single-pose smooth gradients of pose b -- disjoint across poses, no sum over poses --
+ * and the four per-pose outputs the single-pose ones.  What a loop of B single-pose smooth calls computes, in one call.
+ * Layouts: those of PER-POSE CLOUDS (points, ds_dpoints n_in x P x B, cloud b at b * P * n_in; point_weight,
+ * ds_dpoint_weight P x B or NULL).  Clouds of different sizes: pad them to a common P with point_weight = 0; a
+ * zero-weight point deposits nothing and gets ds_dpoints = 0.  All six pullback outputs and `out` are overwritten.
+ * (n_in, n_out): (2,2), (3,3) and (3,2).  op: DPR_OP_RASTER or DPR_OP_PULLBACK.
+ * Flags: DPR_FLAG_NO_POINT_WEIGHT_GRAD keeps its meaning (ds_dpoint_weight may then be NULL); DPR_FLAG_COHERENT_POINTS
+ * is accepted and ignored; DPR_FLAG_MAX_POSE_GROUP(n) is HONOURED by the DPR_ALGO_TILED forward (below; pass the same
+ * flags to the workspace query); KEEP / REUSE are refused.
+ * Algorithms (DPR_ALGO_CHUNKED, DPR_ALGO_ORDERED: DPR_ERR_UNSUPPORTED_ALGO).
+ *   DPR_ALGO_ATOMIC  forward: one thread per (point, pose), a block inside one pose, 3^N global float atomics per
+ *                    accepted (point, pose).  Pullback: one thread per (point, pose); the 3^N gathers one 3^(N-1)
+ *                    plane at a time; ds_dpoints[b, p] and ds_dpoint_weight[b, p] one plain store each (no pose
+ *                    slices, no accumulation); per-pose sums wave -> block -> one float atomic per scalar per
+ *                    block; ds_dbackground one float atomic per block of cells.  Workspace 0.
+ *   DPR_ALGO_TILED   forward only (pullback: DPR_ERR_UNSUPPORTED_ALGO).  The poses are binned in GROUPS of bg: for a
+ *                    group, ONE key pass over its bg * P points (key = b_local * tiles + the tile of
+ *                    dpr_raster_smooth_ex_*(DPR_ALGO_TILED), all ones for a rejected point; value = the flat index
+ *                    b_local * P + p), ONE stable radix sort on the bits bg * tiles needs, ONE start table of
+ *                    bg * tiles + 1 entries and ONE launch of bg * tiles workgroups, each the tile workgroup of
+ *                    SMOOTH SPLAT for its (pose, tile): four launches per group instead of four per pose.
+ *                    GROUP SIZE: bg is the largest number of poses <= B with bg * max(P, tiles) <= 2^24, at least 1,
+ *                    and at most n under DPR_FLAG_MAX_POSE_GROUP(n), n in 1..16.  2^24 keeps every key below the
+ *                    all-ones key and every flat index below 2^32 - 1 whenever bg > 1, and bounds the workspace
+ *                    of a call at about 16 * 2^24 bytes of keys and indices plus the sort's storage (some 400 MB)
+ *                    whatever B; nothing measured asked for another value (profiles/smooth_clouds_probe.txt).
+ *                    With bg = 1 the LIMITS are those of SMOOTH SPLAT.  Workspace: that of
+ *                    dpr_raster_smooth_ex_*(DPR_ALGO_TILED) evaluated for bg * tiles tiles and bg * P points, reused
+ *                    from group to group; with a group of one exactly dpr_workspace_bytes_smooth_ex_*(DPR_OP_RASTER,
+ *                    DPR_ALGO_TILED, .., P, 1); 0 for P = 0.  The COST note of SMOOTH SPLAT applies per (pose, tile).
+ * AUTO (dpr_resolve_algo_smooth_clouds), from the shape alone, never from the points: the pullback DPR_ALGO_ATOMIC; the
+ * forward DPR_ALGO_TILED where the default group holds bg * P >= 100 000 points for a 3-D grid and >= 400 000 for a
+ * 2-D grid, a cloud holds at least 4 points per tile of the grid (P >= 4 * tiles) and the LIMITS hold;
+ * DPR_ALGO_ATOMIC otherwise.  The first is the rule of dpr_resolve_algo_smooth applied to the group, because the
+ * fixed cost is paid per group; this op's own times (profiles/smooth_clouds_probe.txt, fp32, uniform clouds) moved the
+ * 2-D constant from 500 000 (3e4 points x 16 poses -> 128^2 is 1.27x faster TILED) and added the second condition
+ * (1e4 x 16 -> 256^3, 0.6 points per tile, is 1.7x faster ATOMIC).  Between bg * P = 3.2e5 and 4.8e5 on 2-D grids and
+ * between 1.8 and 4.9 points per tile nothing was measured; no 2-D row has fewer than 100 points per tile.
+ * Summation order: the table in SUMMATION ORDER.
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): a pair outside the three
+ * DPR_ERR_UNSUPPORTED_DIMS (the grid is not looked at first); a bad op, negative P / B, a bad grid, a NULL required
+ * pointer, a misaligned data pointer, B * P * n_in beyond 2^60 DPR_ERR_INVALID_ARG; DPR_OP_RESIDUAL_PULLBACK, KEEP /
+ * REUSE, DPR_ALGO_CHUNKED / DPR_ALGO_ORDERED / an unknown algorithm, a DPR_ALGO_TILED pullback and a DPR_ALGO_TILED
+ * forward outside the LIMITS DPR_ERR_UNSUPPORTED_ALGO; a workspace smaller than
+ * dpr_workspace_bytes_smooth_clouds_ex_* or not 256-byte aligned DPR_ERR_WORKSPACE.
+ * dpr_workspace_bytes_smooth_clouds_ex_* returns (size_t)-1 for every refused combination;
+ * dpr_resolve_algo_smooth_clouds a negative status. */
+int dpr_resolve_algo_smooth_clouds(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_smooth_clouds_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_smooth_clouds_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                const int64_t *grid, int64_t P, int64_t B);
+int dpr_raster_smooth_clouds_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                    const int64_t *grid, int64_t P, int64_t B, float *out, const float *points,
+                                    const float *rotation, const float *translation, const float *background,
+                                    const float *out_weight, const float *point_weight, void *workspace,
+                                    size_t workspace_bytes);
+int dpr_raster_smooth_clouds_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                    const int64_t *grid, int64_t P, int64_t B, double *out, const double *points,
+                                    const double *rotation, const double *translation, const double *background,
+                                    const double *out_weight, const double *point_weight, void *workspace,
+                                    size_t workspace_bytes);
+int dpr_raster_pullback_smooth_clouds_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t *grid, int64_t P, int64_t B, const float *ds_dout,
+                                             const float *points, const float *rotation, const float *translation,
+                                             const float *out_weight, const float *point_weight, float *ds_dpoints,
+                                             float *ds_drotation, float *ds_dtranslation, float *ds_dbackground,
+                                             float *ds_dout_weight, float *ds_dpoint_weight, void *workspace,
+                                             size_t workspace_bytes);
+int dpr_raster_pullback_smooth_clouds_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t *grid, int64_t P, int64_t B, const double *ds_dout,
+                                             const double *points, const double *rotation,
+                                             const double *translation, const double *out_weight,
+                                             const double *point_weight, double *ds_dpoints, double *ds_drotation,
+                                             double *ds_dtranslation, double *ds_dbackground,
+                                             double *ds_dout_weight, double *ds_dpoint_weight, void *workspace,
+                                             size_t workspace_bytes);
 
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
