@@ -26,6 +26,9 @@ from .smooth_jvp import (raster_smooth_jvp, raster_smooth_jvp_, resolve_algo_smo
                          workspace_bytes_smooth_jvp)
 from .smooth_clouds import (raster_pullback_smooth_clouds_, raster_smooth_clouds, raster_smooth_clouds_,
                             raster_smooth_clouds_ad, resolve_algo_smooth_clouds, workspace_bytes_smooth_clouds)
+from .smooth_channels import (raster_pullback_smooth_channels_, raster_smooth_channels, raster_smooth_channels_,
+                              raster_smooth_channels_ad, resolve_algo_smooth_channels,
+                              workspace_bytes_smooth_channels)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -49,4 +52,6 @@ __all__ = [
     "raster_smooth_jvp", "raster_smooth_jvp_", "resolve_algo_smooth_jvp", "workspace_bytes_smooth_jvp",
     "raster_smooth_clouds", "raster_smooth_clouds_", "raster_pullback_smooth_clouds_", "raster_smooth_clouds_ad",
     "resolve_algo_smooth_clouds", "workspace_bytes_smooth_clouds",
+    "raster_smooth_channels", "raster_smooth_channels_", "raster_pullback_smooth_channels_",
+    "raster_smooth_channels_ad", "resolve_algo_smooth_channels", "workspace_bytes_smooth_channels",
 ]

@@ -75,6 +75,10 @@ EXPORTS = [
     "dpr_resolve_algo_smooth_clouds", "dpr_workspace_bytes_smooth_clouds_ex_f32",
     "dpr_workspace_bytes_smooth_clouds_ex_f64", "dpr_raster_smooth_clouds_ex_f32", "dpr_raster_smooth_clouds_ex_f64",
     "dpr_raster_pullback_smooth_clouds_ex_f32", "dpr_raster_pullback_smooth_clouds_ex_f64",
+    "dpr_resolve_algo_smooth_channels", "dpr_workspace_bytes_smooth_channels_ex_f32",
+    "dpr_workspace_bytes_smooth_channels_ex_f64", "dpr_raster_smooth_channels_ex_f32",
+    "dpr_raster_smooth_channels_ex_f64", "dpr_raster_pullback_smooth_channels_ex_f32",
+    "dpr_raster_pullback_smooth_channels_ex_f64",
 ]
 
 _lib = None
@@ -261,6 +265,19 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, f"dpr_raster_pullback_smooth_clouds_ex_{suf}")
         f.restype = i
         f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64] + [vp] * 12 + [vp, sz]
+    L.dpr_resolve_algo_smooth_channels.restype = i
+    L.dpr_resolve_algo_smooth_channels.argtypes = [i, i, i, vp, i64, i64, i64]
+    for suf in ("f32", "f64"):
+        f = getattr(L, f"dpr_workspace_bytes_smooth_channels_ex_{suf}")
+        f.restype = sz
+        f.argtypes = [i, i, ctypes.c_uint, i, i, vp, i64, i64, i64]
+        # the argument lists of dpr_raster_channels_ex_* / dpr_raster_pullback_channels_ex_*
+        f = getattr(L, f"dpr_raster_smooth_channels_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 7 + [vp, sz]
+        f = getattr(L, f"dpr_raster_pullback_smooth_channels_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 12 + [vp, sz]
     L.dpr_comm_unique_id.restype = i
     L.dpr_comm_unique_id.argtypes = [vp, sz]
     L.dpr_comm_init.restype = i

@@ -1,5 +1,5 @@
-// The smooth entry points of libdpr -- splat, sampling, forward mode and per-pose clouds: host checks, AUTO rules and
-// C ABI (core: dpr_api.hip; kernels and their launches: dpr_smooth.hip).
+// The smooth entry points of libdpr -- splat, sampling, forward mode, per-pose clouds and weight channels: host checks,
+// AUTO rules and C ABI (core: dpr_api.hip; kernels and their launches: dpr_smooth.hip, dpr_smooth_channels.hip).
 #include <hip/hip_runtime.h>
 
 #include "dpr_host.h"
@@ -515,6 +515,135 @@ static size_t workspace_smooth_clouds_impl(int op, int algo, unsigned flags, int
     return need;
 }
 
+// ---------------------------------------------------------------- smooth splat, C weights per point
+// dpr_raster_smooth_channels_ex_* / dpr_raster_pullback_smooth_channels_ex_* (include/dpr.h, "SMOOTH SPLAT,
+// MULTI-CHANNEL"; kernels: dpr_smooth_channels.hip).  fill_background / grid_sum serve the B * C planes as they are
+// (plane k = b * C + c pairs with background[k]).  DPR_ALGO_ATOMIC: forward and pullback; DPR_ALGO_TILED: forward, the
+// smooth forward's binning and workspace, once per pose for all C channels.
+// AUTO (dpr_resolve_algo_smooth_channels), from the shape and C alone (profiles/smooth_channels_probe.txt, fp32,
+// uniform clouds in random order, times in ms TILED / ATOMIC; tests/golden/smooth_channels_auto.json).  The pullback
+// is DPR_ALGO_ATOMIC.  The tiled path pays the key pass, the sort and the start table once per pose, whatever C; the
+// atomic one 3^N atomics per (point, channel).  So the rule is the smooth forward's with P * C in the place of P:
+//  - 3-D grids, P * C >= 1e5 (the forward's constant; no row of this op lies below 3e5): 1e5 x 16 poses -> 128^3,
+//    C = 3 1.75 / 5.05, C = 16 4.63 / 26.3; 1e6 -> 256^3, C = 4 0.663 / 4.03; 1e7 -> 256^3, C = 16 3.93 / 157.
+//  - 2-D grids, P * C >= 3e5: 1e5 x 16 poses -> 128^2, C = 3 1.48 / 1.90 (1.29x; the 4e5 of the JVP rule would have
+//    lost this row), C = 4 1.54 / 2.53, C = 16 1.63 / 9.32; 1e6 -> 512^2, C = 3 0.244 / 1.15.  With one weight that
+//    shape is ATOMIC's (0.68 against 1.38 ms, profiles/smooth_jvp_probe.txt): the constant lies between P * C = 1e5
+//    and 3e5, and 3e5 is the measured row.  Nothing was measured between.
+constexpr int64_t kSmoothChannelsTiledMinWork3D = 100000;
+constexpr int64_t kSmoothChannelsTiledMinWork2D = 300000;
+static int resolve_algo_smooth_channels(int algo, int op, int n_out, const int64_t* grid, int64_t P, int64_t C) {
+    if (algo != DPR_ALGO_AUTO) return algo;
+    if (op != DPR_OP_RASTER) return DPR_ALGO_ATOMIC;
+    const int64_t min_work = n_out == 3 ? kSmoothChannelsTiledMinWork3D : kSmoothChannelsTiledMinWork2D;
+    if (P * C >= min_work && smooth_tile_count(n_out, grid, P) != 0) return DPR_ALGO_TILED;
+    return DPR_ALGO_ATOMIC;
+}
+
+// the checks every entry point and query of the family shares, in the smooth entry points' order; *G and the
+// resolved *algo come back, *need: workspace
+static int check_smooth_channels(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                 int64_t P, int64_t B, int64_t C, int64_t* G, size_t* need) {
+    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
+    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
+    if (int rc = check_smooth(op, flags)) return rc;
+    if (C < 1 || C > kMaxChannels)
+        return fail(DPR_ERR_INVALID_ARG, "channels C = %lld out of range [1, %d]", (long long)C, kMaxChannels);
+    // 64-bit offsets: plane (c, b) starts at (b * C + c) * G, the weights of point p at p * C
+    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (B > 0 && *G * C > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "output too large");
+    *algo = resolve_algo_smooth_channels(*algo, op, n_out, grid, P, C);
+    *need = smooth_workspace_bytes(op, *algo, n_out, grid, P);
+    return *need == (size_t)-1 ? DPR_ERR_UNSUPPORTED_ALGO : DPR_OK;
+}
+
+template <typename T>
+static int raster_smooth_channels_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
+                                       const int64_t* grid, int64_t P, int64_t B, int64_t C, T* out, const T* points,
+                                       const T* rot, const T* trans, const T* bg, const T* ow, const T* pw, void* ws,
+                                       size_t ws_bytes) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_smooth_channels(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need)) return rc;
+    if (B == 0) return DPR_OK;
+    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
+    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (P > 0 && !pw) return fail(DPR_ERR_INVALID_ARG, "point_weight is NULL with P > 0 (the channel form needs it)");
+    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
+        return fail(DPR_ERR_WORKSPACE, "smooth splat with channels (algorithm %d) needs %zu workspace bytes, got %zu",
+                    algo, need, ws ? ws_bytes : (size_t)0);
+    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    fill_background(st, out, G, B * C, bg);
+    stage_mark(st);
+    const int c = (int)C;
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        const int rc = algo == DPR_ALGO_TILED
+                           ? smooth_channels_fwd_tiled<T, NI, NO>(st, grid, G, P, B, c, out, points, rot, trans, ow, pw,
+                                                                  ws, ws_bytes)
+                           : smooth_channels_fwd_atomic<T, NI, NO>(st, grid, G, P, B, c, out, points, rot, trans, ow,
+                                                                   pw);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+template <typename T>
+static int pullback_smooth_channels_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
+                                         const int64_t* grid, int64_t P, int64_t B, int64_t C, const T* g,
+                                         const T* points, const T* rot, const T* trans, const T* ow, const T* pw,
+                                         T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw, void* ws,
+                                         size_t ws_bytes) {
+    (void)ws_bytes;
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_smooth_channels(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need))
+        return rc;
+    if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
+    if (B == 0) return DPR_OK;  // (every output is empty)
+    if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
+    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+    if (!d_rot || !d_trans || !d_bg || !d_ow) return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
+    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
+        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (P > 0 && !pw) return fail(DPR_ERR_INVALID_ARG, "point_weight is NULL with P > 0 (the channel form needs it)");
+    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    const int64_t planes = B * C;
+    DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * n_out * n_in), st));
+    DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * n_out), st));
+    DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
+    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)planes, st));
+    // ds_dbackground[b, c] = sum of plane b * C + c
+    grid_sum(st, g, G, planes, d_bg, Residual<T>{nullptr, T(0), nullptr});
+    stage_mark(st);
+    if (P == 0) return DPR_OK;  // (the per-pose sums are 0, ds_dbackground is done)
+    int64_t slices = 1;
+    const int poses_per_slice = pose_slices(P, B, &slices);  // (the linear atomic pullback's: SUMMATION ORDER, note 1)
+    const int c = (int)C;
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        const int rc = smooth_channels_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
+            st, grid, G, P, B, c, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice,
+            slices);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+static size_t workspace_smooth_channels_impl(int op, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t* grid, int64_t P, int64_t B, int64_t C) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (check_smooth_channels(op, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need)) return (size_t)-1;
+    return need;
+}
+
 }  // namespace dpr
 
 extern "C" {
@@ -655,5 +784,43 @@ int dpr_resolve_algo_smooth_clouds(int op, int n_in, int n_out, const int64_t* g
 DPR_DEFINE_SMOOTH_CLOUDS(f32, float)
 DPR_DEFINE_SMOOTH_CLOUDS(f64, double)
 #undef DPR_DEFINE_SMOOTH_CLOUDS
+
+int dpr_resolve_algo_smooth_channels(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
+                                     int64_t C) {
+    int64_t G = 0;
+    size_t need = 0;
+    int algo = DPR_ALGO_AUTO;
+    if (int rc = dpr::check_smooth_channels(op, &algo, 0u, n_in, n_out, grid, P, B, C, &G, &need)) return rc;
+    return algo;
+}
+
+#define DPR_DEFINE_SMOOTH_CHANNELS(SUF, T)                                                                     \
+    size_t dpr_workspace_bytes_smooth_channels_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out, \
+                                                        const int64_t* grid, int64_t P, int64_t B, int64_t C) { \
+        return dpr::workspace_smooth_channels_impl(op, algo, flags, n_in, n_out, grid, P, B, C);               \
+    }                                                                                                          \
+    int dpr_raster_smooth_channels_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,       \
+                                            const int64_t* grid, int64_t P, int64_t B, int64_t C, T* out,      \
+                                            const T* points, const T* rotation, const T* translation,          \
+                                            const T* background, const T* out_weight, const T* point_weight,   \
+                                            void* workspace, size_t workspace_bytes) {                         \
+        return dpr::raster_smooth_channels_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, C, out,       \
+                                                   points, rotation, translation, background, out_weight,      \
+                                                   point_weight, workspace, workspace_bytes);                  \
+    }                                                                                                          \
+    int dpr_raster_pullback_smooth_channels_ex_##SUF(                                                          \
+        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, \
+        int64_t C, const T* ds_dout, const T* points, const T* rotation, const T* translation,                 \
+        const T* out_weight, const T* point_weight, T* ds_dpoints, T* ds_drotation, T* ds_dtranslation,        \
+        T* ds_dbackground, T* ds_dout_weight, T* ds_dpoint_weight, void* workspace, size_t workspace_bytes) {  \
+        return dpr::pullback_smooth_channels_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, C, ds_dout, \
+                                                     points, rotation, translation, out_weight, point_weight,  \
+                                                     ds_dpoints, ds_drotation, ds_dtranslation,                \
+                                                     ds_dbackground, ds_dout_weight, ds_dpoint_weight,         \
+                                                     workspace, workspace_bytes);                              \
+    }
+DPR_DEFINE_SMOOTH_CHANNELS(f32, float)
+DPR_DEFINE_SMOOTH_CHANNELS(f64, double)
+#undef DPR_DEFINE_SMOOTH_CHANNELS
 
 }  // extern "C"

@@ -68,6 +68,43 @@ int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
                       const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts, T* d_rot,
                       T* d_trans, T* d_ow, T* d_pw, int poses_per_slice, int64_t slices);
 
+// The binning of DPR_ALGO_TILED, for the launchers of dpr_smooth.hip and dpr_smooth_channels.hip (k_smooth_keys and
+// k_smooth_ranges are compiled in dpr_smooth.hip only).  smooth_binning: the tiles of a call and the pieces of its
+// workspace (DPR_ERR_UNSUPPORTED_ALGO / DPR_ERR_WORKSPACE where the call cannot run).  smooth_bin_pose: keys -> stable
+// sort -> start table of pose b, which depend on the primal only; afterwards sb.start[t] .. sb.start[t + 1] is the
+// run of tile t in sb.idx_out.
+template <int NO> struct SmoothBinning {
+    GridDesc<NO> gd;
+    SmoothTiles<NO> tl;
+    int64_t tiles;
+    int bits;  // of a key
+    char* temp;
+    size_t temp_bytes;
+    uint32_t *keys_in, *keys_out, *idx_in, *idx_out, *start;
+};
+template <int NO>
+int smooth_binning(const int64_t* grid, int64_t G, int64_t P, void* ws, size_t ws_bytes, SmoothBinning<NO>* sb);
+template <typename T, int NI, int NO>
+int smooth_bin_pose(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int64_t b, const T* points, const T* rot,
+                    const T* trans);
+
+// C weights per point (include/dpr.h, "SMOOTH SPLAT, MULTI-CHANNEL"; kernels: dpr_smooth_channels.hip): pw is
+// P x C with a point's weights contiguous, plane (c, b) of out / g at (b * C + c) * G.  The same contract with the
+// caller as above: `out` holds the B * C backgrounds already, the per-pose sums are zeroed and ds_dbackground is done
+// by the caller.  The tiled forward takes smooth_fwd_tiled's workspace and bins every pose once for all C channels.
+// The pullback is one launch for all C channels; d_pw is P x C (NULL: not wanted).
+template <typename T, int NI, int NO>
+int smooth_channels_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C, T* out,
+                               const T* points, const T* rot, const T* trans, const T* ow, const T* pw);
+template <typename T, int NI, int NO>
+int smooth_channels_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C, T* out,
+                              const T* points, const T* rot, const T* trans, const T* ow, const T* pw, void* ws,
+                              size_t ws_bytes);
+template <typename T, int NI, int NO>
+int smooth_channels_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C, const T* g,
+                               const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts,
+                               T* d_rot, T* d_trans, T* d_ow, T* d_pw, int poses_per_slice, int64_t slices);
+
 // Per-pose clouds (include/dpr.h, "SMOOTH SPLAT, PER-POSE CLOUDS"): cloud b at points + b * P * NI, its weights at
 // pw + b * P, and ds_dpoints / ds_dpoint_weight likewise.  The same contract with the caller as above.
 // The tiled forward bins a GROUP of poses with one key pass, one sort, one start table and one tile launch.

@@ -29,76 +29,9 @@
 #include "dpr_ordered.h"
 #include "dpr_ordered_index.h"
 #include "dpr_smooth.h"
+#include "dpr_smooth_device.h"
 
 namespace dpr {
-
-constexpr int kSmBlock = 256;
-
-template <typename T> __device__ __forceinline__ T floor_t(T x);
-template <> __device__ __forceinline__ float floor_t<float>(float x) { return floorf(x); }
-template <> __device__ __forceinline__ double floor_t<double>(double x) { return floor(x); }
-
-// Centre cell j0 (0-based, -1 .. n_d) and offset u from its centre.  false: the point is rejected for the pose
-// (some coord outside [-1, n_d + 1); the test runs in floating point before the conversion to int and rejects
-// NaN / Inf).  The projection has ref_and_deltas' operation order.
-template <typename T, int NI, int NO>
-__device__ __forceinline__ bool smooth_cell(const T (&p)[NI], const Pose<T, NI, NO>& ps, const GridDesc<NO>& gd,
-                                            int (&j0)[NO], T (&u)[NO]) {
-    bool ok = true;
-#pragma unroll
-    for (int d = 0; d < NO; ++d) {
-        T proj = ps.R[d] * p[0];
-#pragma unroll
-        for (int j = 1; j < NI; ++j) proj = proj + ps.R[d + j * NO] * p[j];
-        const T origin = T(-1) - ps.t[d];
-        const T scale = T(gd.n[d]) / T(2);
-        const T coord = (proj - origin) * scale;
-        ok = ok && (coord >= T(-1)) && (coord < T(gd.n[d] + 1));
-        const T f = floor_t<T>(coord);
-        j0[d] = ok ? (int)f : 0;
-        u[d] = coord - (f + T(0.5));
-    }
-    return ok;
-}
-
-// the three weights of an axis and their derivatives in coord
-template <typename T> __device__ __forceinline__ void spline_weights(T u, T (&w)[3]) {
-    const T a = T(0.5) - u, b = T(0.5) + u;
-    w[0] = a * a * T(0.5);
-    w[1] = T(0.75) - u * u;
-    w[2] = b * b * T(0.5);
-}
-template <typename T> __device__ __forceinline__ void spline_derivatives(T u, T (&dw)[3]) {
-    dw[0] = -(T(0.5) - u);
-    dw[1] = T(-2) * u;
-    dw[2] = T(0.5) + u;
-}
-
-// Per axis: the weights and, for the three cells j0 - 1 .. j0 + 1, whether the cell is in the grid and its
-// column-major offset term (0 for a dropped cell: the product would overflow an int next to 2^31 cells).
-template <typename T, int NO> struct SmoothAxes {
-    T w[NO][3];
-    int off[NO][3];
-    bool in[NO][3];
-};
-template <typename T, int NO>
-__device__ __forceinline__ SmoothAxes<T, NO> smooth_axes(const int (&j0)[NO], const T (&u)[NO],
-                                                         const GridDesc<NO>& gd) {
-    SmoothAxes<T, NO> ax;
-    int stride = 1;
-#pragma unroll
-    for (int d = 0; d < NO; ++d) {
-        spline_weights<T>(u[d], ax.w[d]);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int c = j0[d] + k - 1;
-            ax.in[d][k] = c >= 0 && c < gd.n[d];
-            ax.off[d][k] = ax.in[d][k] ? c * stride : 0;
-        }
-        stride *= gd.n[d];
-    }
-    return ax;
-}
 
 // ---------------------------------------------------------------- DPR_ALGO_ATOMIC forward
 template <typename T, int NI, int NO>
@@ -1113,20 +1046,11 @@ int smooth_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
     return DPR_OK;
 }
 
-// What the two tiled launchers share: the tiles and workspace pieces of a call (smooth_binning), and the binning of
-// one pose (smooth_bin_pose): keys -> sort -> ranges, which depend on the primal only.
-template <int NO> struct SmoothBinning {
-    GridDesc<NO> gd;
-    SmoothTiles<NO> tl;
-    int64_t tiles;
-    int bits;  // of a key
-    char* temp;
-    size_t temp_bytes;
-    uint32_t *keys_in, *keys_out, *idx_in, *idx_out, *start;
-};
+// What the tiled launchers share (declared in dpr_smooth.h): the tiles and workspace pieces of a call
+// (smooth_binning), and the binning of one pose (smooth_bin_pose): keys -> sort -> ranges, which depend on the
+// primal only.
 template <int NO>
-static int smooth_binning(const int64_t* grid, int64_t G, int64_t P, void* ws_, size_t ws_bytes,
-                          SmoothBinning<NO>* sb) {
+int smooth_binning(const int64_t* grid, int64_t G, int64_t P, void* ws_, size_t ws_bytes, SmoothBinning<NO>* sb) {
     const int64_t tiles = smooth_tile_count(NO, grid, P);
     if (tiles == 0) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
     const SmoothPlan pl = smooth_plan(tiles, P);
@@ -1148,8 +1072,8 @@ static int smooth_binning(const int64_t* grid, int64_t G, int64_t P, void* ws_, 
     return DPR_OK;
 }
 template <typename T, int NI, int NO>
-static int smooth_bin_pose(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int64_t b, const T* points,
-                           const T* rot, const T* trans) {
+int smooth_bin_pose(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int64_t b, const T* points,
+                    const T* rot, const T* trans) {
     const dim3 blk(kSmBlock);
     const dim3 pgrid((unsigned)((P + kSmBlock - 1) / kSmBlock));
     const dim3 rgrid((unsigned)((sb.tiles + 1 + kSmBlock - 1) / kSmBlock));
@@ -1348,7 +1272,12 @@ int sample_smooth_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
     return DPR_OK;
 }
 
+template int smooth_binning<2>(const int64_t*, int64_t, int64_t, void*, size_t, SmoothBinning<2>*);
+template int smooth_binning<3>(const int64_t*, int64_t, int64_t, void*, size_t, SmoothBinning<3>*);
+
 #define DPR_SMOOTH_INSTANTIATE(T, NI, NO)                                                                           \
+    template int smooth_bin_pose<T, NI, NO>(hipStream_t, const SmoothBinning<NO>&, int64_t, int64_t, const T*,      \
+                                            const T*, const T*);                                                   \
     template int sample_smooth_fwd<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, T*, const T*, \
                                               const T*, const T*, const T*, int, int64_t);                         \
     template int sample_smooth_bwd<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, const T*,     \

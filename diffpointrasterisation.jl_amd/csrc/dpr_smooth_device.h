@@ -1,0 +1,79 @@
+// Device helpers of the smooth splat (include/dpr.h, "SMOOTH SPLAT") that the kernels of dpr_smooth.hip and
+// dpr_smooth_channels.hip share: the cell of a point, the B-spline weights of an axis and their derivatives, and
+// the per-axis offsets of the 3^N cells.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "dpr_smooth.h"
+
+namespace dpr {
+
+constexpr int kSmBlock = 256;
+
+template <typename T> __device__ __forceinline__ T floor_t(T x);
+template <> __device__ __forceinline__ float floor_t<float>(float x) { return floorf(x); }
+template <> __device__ __forceinline__ double floor_t<double>(double x) { return floor(x); }
+
+// Centre cell j0 (0-based, -1 .. n_d) and offset u from its centre.  false: the point is rejected for the pose
+// (some coord outside [-1, n_d + 1); the test runs in floating point before the conversion to int and rejects
+// NaN / Inf).  The projection has ref_and_deltas' operation order.
+template <typename T, int NI, int NO>
+__device__ __forceinline__ bool smooth_cell(const T (&p)[NI], const Pose<T, NI, NO>& ps, const GridDesc<NO>& gd,
+                                            int (&j0)[NO], T (&u)[NO]) {
+    bool ok = true;
+#pragma unroll
+    for (int d = 0; d < NO; ++d) {
+        T proj = ps.R[d] * p[0];
+#pragma unroll
+        for (int j = 1; j < NI; ++j) proj = proj + ps.R[d + j * NO] * p[j];
+        const T origin = T(-1) - ps.t[d];
+        const T scale = T(gd.n[d]) / T(2);
+        const T coord = (proj - origin) * scale;
+        ok = ok && (coord >= T(-1)) && (coord < T(gd.n[d] + 1));
+        const T f = floor_t<T>(coord);
+        j0[d] = ok ? (int)f : 0;
+        u[d] = coord - (f + T(0.5));
+    }
+    return ok;
+}
+
+// the three weights of an axis and their derivatives in coord
+template <typename T> __device__ __forceinline__ void spline_weights(T u, T (&w)[3]) {
+    const T a = T(0.5) - u, b = T(0.5) + u;
+    w[0] = a * a * T(0.5);
+    w[1] = T(0.75) - u * u;
+    w[2] = b * b * T(0.5);
+}
+template <typename T> __device__ __forceinline__ void spline_derivatives(T u, T (&dw)[3]) {
+    dw[0] = -(T(0.5) - u);
+    dw[1] = T(-2) * u;
+    dw[2] = T(0.5) + u;
+}
+
+// Per axis: the weights and, for the three cells j0 - 1 .. j0 + 1, whether the cell is in the grid and its
+// column-major offset term (0 for a dropped cell: the product would overflow an int next to 2^31 cells).
+template <typename T, int NO> struct SmoothAxes {
+    T w[NO][3];
+    int off[NO][3];
+    bool in[NO][3];
+};
+template <typename T, int NO>
+__device__ __forceinline__ SmoothAxes<T, NO> smooth_axes(const int (&j0)[NO], const T (&u)[NO],
+                                                         const GridDesc<NO>& gd) {
+    SmoothAxes<T, NO> ax;
+    int stride = 1;
+#pragma unroll
+    for (int d = 0; d < NO; ++d) {
+        spline_weights<T>(u[d], ax.w[d]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int c = j0[d] + k - 1;
+            ax.in[d][k] = c >= 0 && c < gd.n[d];
+            ax.off[d][k] = ax.in[d][k] ? c * stride : 0;
+        }
+        stride *= gd.n[d];
+    }
+    return ax;
+}
+
+}  // namespace dpr

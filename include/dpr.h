@@ -278,6 +278,20 @@ extern "C" {
  *                        partials per cell as float atomics in T:
  *                        rounding level, not bit-reproducible
  *
+ *   smooth splat, C weights per point (dpr_raster_smooth_channels_ex_* / dpr_raster_pullback_smooth_channels_ex_*, see
+ *   SMOOTH SPLAT, MULTI-CHANNEL below), per channel / plane:
+ *   DPR_ALGO_ATOMIC      as the smooth splat's, into plane (c, b):   as the smooth splat's, pose slices      as the smooth splat's; a thread adds its
+ *                        rounding level                              alike (note 1).  One slice: one thread  C channels in index order before the wave
+ *                                                                    adds all poses and, for ds_dpoints,     sum: rounding level
+ *                                                                    all channels in index order, one plain
+ *                                                                    store per value: bit-reproducible
+ *   DPR_ALGO_TILED       as the smooth splat's tiled forward per
+ *   (forward only)       (tile, channel): f64 LDS atomics in arrival
+ *                        order, rounded to T once per (tile, cell,
+ *                        channel), <= 3^N such partials per cell as
+ *                        float atomics in T: rounding level, not
+ *                        bit-reproducible
+ *
  *   smooth splat, forward mode (dpr_raster_smooth_jvp_ex_*, see SMOOTH SPLAT, FORWARD MODE below), out_dot:
  *   DPR_ALGO_ATOMIC      global float atomics in T onto the background tangent, unordered: rounding level (lanes of
  *                        a wave with the same centre cell are first added in T in a fixed order, one atomic per group)
@@ -1129,6 +1143,86 @@ int dpr_raster_pullback_smooth_clouds_ex_f64(void *stream, int algo, unsigned fl
                                              double *ds_dtranslation, double *ds_dbackground,
                                              double *ds_dout_weight, double *ds_dpoint_weight, void *workspace,
                                              size_t workspace_bytes);
+
+/* ---- SMOOTH SPLAT, MULTI-CHANNEL: the quadratic B-spline splat with C weights per point ---------------------------
+ * MULTI-CHANNEL with the kernel of SMOOTH SPLAT.  For channel c and pose b:
+ *     out[i.., c, b] = background[b, c] + out_weight[b] * sum_p point_weight[p, c] * Bspline_weight(i..; R_b p + t_b)
+ * Plane (c, b) is dpr_raster_smooth_* of (grid, points, R_b, t_b, background[b, c], out_weight[b], point_weight[:, c]):
+ * the same centre cell j0, the same weights on 3^N cells, the same acceptance -1 <= coord_d < n_d + 1, cells outside
+ * the grid dropped one by one.  The cell, the weights and the offsets of a (point, pose) are computed once and serve
+ * the C channels.  The pullback is the exact derivative (no cell is held fixed): ds_dpoints, ds_drotation,
+ * ds_dtranslation and ds_dout_weight are the sums over c of the single-channel smooth gradients, ds_dpoint_weight[p, c]
+ * and ds_dbackground[b, c] those of channel c.
+ * Layouts: those of MULTI-CHANNEL.  point_weight, ds_dpoint_weight C x P (a point's C weights contiguous; point_weight
+ * is REQUIRED: NULL with P > 0 is DPR_ERR_INVALID_ARG); background, ds_dbackground C x B (background may be NULL: 0);
+ * out, ds_dout (n_1, .., n_N, C, B) column-major, plane (c, b) at (b * C + c) * G; out_weight one value per pose.
+ * All six pullback outputs and `out` are overwritten.  C = 1..16; (n_in, n_out): (2,2), (3,3) and (3,2).
+ * op: DPR_OP_RASTER or DPR_OP_PULLBACK.  P = 0: `out` is the backgrounds, the per-pose gradients are 0, ds_dbackground
+ * the plane sums.  B = 0: DPR_OK after the checks, nothing is written.
+ * Flags: DPR_FLAG_NO_POINT_WEIGHT_GRAD keeps its meaning (ds_dpoint_weight may then be NULL); DPR_FLAG_COHERENT_POINTS
+ * and DPR_FLAG_MAX_POSE_GROUP are accepted and ignored; KEEP / REUSE are refused.
+ * Algorithms (DPR_ALGO_CHUNKED, DPR_ALGO_ORDERED: DPR_ERR_UNSUPPORTED_ALGO).
+ *   DPR_ALGO_ATOMIC  forward: one thread per point, the pose loop inside; per accepted cell C global float atomics,
+ *                    one into each plane.  Pullback: one thread per point, the poses sliced as SMOOTH SPLAT slices
+ *                    them (SUMMATION ORDER note 1); per channel the 3^N gathers one 3^(N-1) plane at a time, all C
+ *                    channels in one launch; per-pose sums wave -> block -> one float atomic per scalar per block;
+ *                    ds_dbackground one float atomic per block of cells.  Workspace 0.
+ *   DPR_ALGO_TILED   forward only (pullback: DPR_ERR_UNSUPPORTED_ALGO).  Per pose the key pass, the stable radix sort
+ *                    and the start table of dpr_raster_smooth_ex_*(DPR_ALGO_TILED), ONCE for all C channels, then one
+ *                    launch of tiles x ceil(C / 2) workgroups: a workgroup keeps the tile + halo of up to 2 channels
+ *                    as f64 cells in LDS (3-D 28 800 bytes, 2-D 19 008), walks its run of the sorted points once and
+ *                    adds every non-zero cell inside the grid onto its plane with one float atomic per (tile, cell,
+ *                    channel).  LIMITS, COST and workspace: those of SMOOTH SPLAT --
+ *                    dpr_workspace_bytes_smooth_ex_*(DPR_OP_RASTER, DPR_ALGO_TILED, .., P, 1) whatever B and C; 0 for
+ *                    P = 0.
+ * AUTO (dpr_resolve_algo_smooth_channels), from the shape and C alone, never from the points: the pullback
+ * DPR_ALGO_ATOMIC; the forward DPR_ALGO_TILED where P * C >= 100 000 for a 3-D grid and >= 300 000 for a 2-D grid and
+ * the LIMITS hold; DPR_ALGO_ATOMIC otherwise.  It is the rule of dpr_resolve_algo_smooth with P * C in the place of P:
+ * the binning is paid once per pose, the atomics once per (point, channel).  This op's own times
+ * (profiles/smooth_channels_probe.txt, fp32, uniform clouds, 18 rows) have DPR_ALGO_TILED ahead on every row, from
+ * 1.29x (1e5 points x 16 poses -> 128^2, C = 3, P * C = 3e5: 1.48 against 1.90 ms) to 40x (1e7 -> 256^3, C = 16).
+ * The 2-D constant lies between the smooth forward's row of that shape (P = 1e5, one weight: 0.68 ms ATOMIC against
+ * 1.38 TILED, profiles/smooth_jvp_probe.txt) and this op's row at P * C = 3e5; the jvp rule's 4e5 would have lost
+ * that row.  No row of this op lies below P * C = 3e5: the 3-D constant is the smooth forward's, not re-measured.
+ * Summation order: the table in SUMMATION ORDER.
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): a pair outside the three
+ * DPR_ERR_UNSUPPORTED_DIMS (the grid is not looked at first); a bad op, negative P / B, a bad grid, C outside 1..16, a
+ * NULL required pointer, a misaligned data pointer, an image beyond 2^62 cells DPR_ERR_INVALID_ARG;
+ * DPR_OP_RESIDUAL_PULLBACK, KEEP / REUSE, DPR_ALGO_CHUNKED / DPR_ALGO_ORDERED / an unknown algorithm, a DPR_ALGO_TILED
+ * pullback and a DPR_ALGO_TILED forward outside the LIMITS DPR_ERR_UNSUPPORTED_ALGO; a workspace smaller than
+ * dpr_workspace_bytes_smooth_channels_ex_* or not 256-byte aligned DPR_ERR_WORKSPACE.
+ * dpr_workspace_bytes_smooth_channels_ex_* returns (size_t)-1 for every refused combination;
+ * dpr_resolve_algo_smooth_channels a negative status. */
+int dpr_resolve_algo_smooth_channels(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B,
+                                     int64_t C);
+size_t dpr_workspace_bytes_smooth_channels_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                  const int64_t *grid, int64_t P, int64_t B, int64_t C);
+size_t dpr_workspace_bytes_smooth_channels_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                  const int64_t *grid, int64_t P, int64_t B, int64_t C);
+int dpr_raster_smooth_channels_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, int64_t C, float *out,
+                                      const float *points, const float *rotation, const float *translation,
+                                      const float *background, const float *out_weight, const float *point_weight,
+                                      void *workspace, size_t workspace_bytes);
+int dpr_raster_smooth_channels_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, int64_t C, double *out,
+                                      const double *points, const double *rotation, const double *translation,
+                                      const double *background, const double *out_weight, const double *point_weight,
+                                      void *workspace, size_t workspace_bytes);
+int dpr_raster_pullback_smooth_channels_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                               const int64_t *grid, int64_t P, int64_t B, int64_t C,
+                                               const float *ds_dout, const float *points, const float *rotation,
+                                               const float *translation, const float *out_weight,
+                                               const float *point_weight, float *ds_dpoints, float *ds_drotation,
+                                               float *ds_dtranslation, float *ds_dbackground, float *ds_dout_weight,
+                                               float *ds_dpoint_weight, void *workspace, size_t workspace_bytes);
+int dpr_raster_pullback_smooth_channels_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                               const int64_t *grid, int64_t P, int64_t B, int64_t C,
+                                               const double *ds_dout, const double *points, const double *rotation,
+                                               const double *translation, const double *out_weight,
+                                               const double *point_weight, double *ds_dpoints, double *ds_drotation,
+                                               double *ds_dtranslation, double *ds_dbackground, double *ds_dout_weight,
+                                               double *ds_dpoint_weight, void *workspace, size_t workspace_bytes);
 
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
