@@ -136,6 +136,7 @@ static int pullback_smooth_impl(void* stream, int algo, unsigned flags, int n_in
     DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
     grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
     stage_mark(st);
+    if (P == 0) return DPR_OK;  // (the per-pose sums are 0, ds_dbackground is done; pose_slices divides by the blocks)
     int64_t slices = 1;
     const int poses_per_slice = pose_slices(P, B, &slices);  // (the linear atomic pullback's: SUMMATION ORDER, note 1)
     return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {

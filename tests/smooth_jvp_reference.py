@@ -15,7 +15,9 @@ from tests.smooth_reference import _defaults, _terms
 
 def raster_smooth_jvp(grid, points, rotation, translation, out_weight=None, point_weight=None, *, K,
                       points_dot=None, rotation_dot=None, translation_dot=None, background_dot=None,
-                      out_weight_dot=None, point_weight_dot=None, dtype=np.float64):
+                      out_weight_dot=None, point_weight_dot=None, dtype=np.float64, magnitudes=False):
+    """out_dot.  With `magnitudes` the same deposit loop on |v|: (A, n) with A of shape grid + (K, B), the sum of the
+    absolute values of the deposits on a cell plus |background_dot|, and n of shape grid + (B,), their number."""
     dtype = np.dtype(dtype).type
     grid = tuple(int(g) for g in grid)
     N, B, P = len(grid), rotation.shape[0], points.shape[0]
@@ -31,6 +33,7 @@ def raster_smooth_jvp(grid, points, rotation, translation, out_weight=None, poin
     td, bgd = tan(translation_dot, (K, B, N)), tan(background_dot, (K, B))
     owd, pwd = tan(out_weight_dot, (K, B)), tan(point_weight_dot, (K, P))
     out = np.empty(grid + (K, B), dtype=dtype)
+    count = np.zeros(grid + (B,), np.int64)
     for b, idx, j0, w, dw in _terms(grid, points, rotation, translation, dtype):
         R = np.asarray(rotation[b], dtype=dtype)
         # (K, A, ..): a rejected point's tangents are never read (idx holds the accepted points only)
@@ -39,6 +42,9 @@ def raster_smooth_jvp(grid, points, rotation, translation, out_weight=None, poin
         c = ow[b] * pw[idx]
         planes = np.empty((K,) + grid, dtype=dtype)
         planes[...] = bgd[:, b].reshape((K,) + (1,) * N)
+        if magnitudes:
+            planes = np.abs(planes)
+        hits = np.zeros(grid, np.int64)
         for s in itertools.product(range(3), repeat=N):
             cell = j0 + (np.asarray(s) - 1)
             inside = np.all((cell >= 0) & (cell < np.asarray(grid)), axis=1)
@@ -51,6 +57,10 @@ def raster_smooth_jvp(grid, points, rotation, translation, out_weight=None, poin
                     if d != m:
                         term = term * w[:, d, s[d]]
                 v = v + term
+            if magnitudes:
+                v = np.abs(v)
             np.add.at(planes, (slice(None),) + tuple(cell[inside].T), v[:, inside])
+            np.add.at(hits, tuple(cell[inside].T), 1)
         out[..., b] = np.moveaxis(planes, 0, -1)
-    return out
+        count[..., b] = hits
+    return (out, count) if magnitudes else out

@@ -240,6 +240,43 @@ def test_pullback_output_buffers_and_point_weight_grad(dev, npdt, tdt):
     assert_close(d_pts, c["pb"][0].astype(npdt), tol(npdt, "points"), "flagged C call, ds_dpoints")
 
 
+@pytest.mark.parametrize("npdt,tdt", DTYPES)
+@pytest.mark.parametrize("n_in,n_out", PAIRS)
+def test_pullback_of_an_empty_cloud_with_several_poses(dev, npdt, tdt, n_in, n_out):
+    """P = 0, B = 3: the point gradients are empty, the per-pose sums exactly 0, ds_dbackground the plane sums; and
+    the backward of raster_smooth_ad on an empty cloud with two poses.  (The pose slicing of the launch divides by
+    the number of point blocks: before the pullback returned ahead of it, this call ended the process.)"""
+    c = _case(n_in, n_out)
+    B = 3
+    g = c["g"].astype(npdt)
+    rot, trans, bg, ow = (T(c[k][:B].astype(npdt), dev) for k in ("rot", "trans", "bg", "ow"))
+    none = torch.zeros((0, n_in), dtype=tdt, device=dev)
+    pb = dpr_amd.raster_pullback_smooth_(grid_to_dev(g, dev), none, rot, trans, bg, ow,
+                                         torch.zeros(0, dtype=tdt, device=dev))
+    assert tuple(pb.points.shape) == (0, n_in) and tuple(pb.point_weight.shape) == (0,)
+    assert pb.points.dtype == tdt and pb.point_weight.dtype == tdt
+    assert tuple(pb.rotation.shape) == (B, n_out, n_in) and tuple(pb.translation.shape) == (B, n_out)
+    for f in ("rotation", "translation", "out_weight"):
+        assert not bool((getattr(pb, f) != 0).any()), f"ds_d{f} of an empty cloud is not 0"
+    assert tuple(pb.background.shape) == (B,)
+    assert_close(pb.background, g.astype(np.float64).reshape(-1, B).sum(axis=0).astype(npdt), tol(npdt, "pose"),
+                 "ds_dbackground")
+    # autograd: two poses, no point
+    xs = [none.clone().requires_grad_(True)] + [x[:2].clone().requires_grad_(True) for x in (rot, trans, bg, ow)]
+    for algo in ("atomic", "tiled"):
+        for x in xs:
+            x.grad = None
+        out = dpr_amd.raster_smooth_ad(c["grid"], *xs, algo=algo)
+        assert tuple(out.shape) == c["grid"] + (2,)
+        w = grid_to_dev(g[..., :2], dev)
+        (out * w).sum().backward()
+        assert tuple(xs[0].grad.shape) == (0, n_in)
+        assert not bool((xs[1].grad != 0).any()) and not bool((xs[2].grad != 0).any())
+        assert not bool((xs[4].grad != 0).any())
+        assert_close(xs[3].grad, g[..., :2].astype(np.float64).reshape(-1, 2).sum(axis=0).astype(npdt),
+                     tol(npdt, "pose"), f"{algo}: background.grad")
+
+
 # ------------------------------------------------------------------ derivative tests on the device
 @pytest.mark.parametrize("n_in,n_out", PAIRS)
 def test_autograd_agrees_with_central_differences(dev, n_in, n_out):

@@ -191,21 +191,20 @@ def coords(grid, points, R, t):
         return ((points @ R.T + t) + 1.0) * (n / 2.0)
 
 
-@functools.lru_cache(maxsize=None)
-def budget(name):
-    """E[c, b] of the module docstring, grid + (B,), fp64."""
-    h, s = smooth_input(name), smooth_data(name)
-    N = h.n_out
-    E = np.empty(h.grid + (h.B,))
+def budget_of(grid, points, rot, trans, bg, ow, pw):
+    """E[c, b] of the module docstring for any cloud, grid + (B,), fp64 (the core of `budget`; the hard tests of the
+    other smooth families form it with a channel's or a cloud's own weights)."""
+    N, B = len(grid), len(rot)
+    E = np.empty(tuple(grid) + (B,))
     with np.errstate(invalid="ignore"):
-        terms = list(SR._terms(h.grid, h.points, h.rot, h.trans, np.float64))
+        terms = list(SR._terms(grid, points, rot, trans, np.float64))
     for b, idx, j0, w, dw in terms:
-        c = np.abs(coords(h.grid, h.points, h.rot[b], h.trans[b])[idx])
-        plane = np.full(h.grid, abs(s.bg[b]))
-        scale = np.abs(s.ow[b] * s.pw[idx])
+        c = np.abs(coords(grid, points, rot[b], trans[b])[idx])
+        plane = np.full(grid, abs(bg[b]))
+        scale = np.abs(ow[b] * pw[idx])
         for st in itertools.product(range(3), repeat=N):
             cell = j0 + (np.asarray(st) - 1)
-            inside = np.all((cell >= 0) & (cell < np.asarray(h.grid)), axis=1)
+            inside = np.all((cell >= 0) & (cell < np.asarray(grid)), axis=1)
             v = np.ones(len(idx))
             for d in range(N):
                 v = v * w[:, d, st[d]]
@@ -217,6 +216,14 @@ def budget(name):
                 v = v + sens
             np.add.at(plane, tuple(cell[inside].T), (scale * v)[inside])
         E[..., b] = plane
+    return E
+
+
+@functools.lru_cache(maxsize=None)
+def budget(name):
+    """E[c, b] of the module docstring, grid + (B,), fp64."""
+    h, s = smooth_input(name), smooth_data(name)
+    E = budget_of(h.grid, h.points, h.rot, h.trans, s.bg, s.ow, s.pw)
     assert np.all(E > 0)
     return frozen(E)
 
@@ -232,26 +239,30 @@ def measured_rho(name):
     return r
 
 
-@functools.lru_cache(maxsize=None)
-def far_cells(name):
+def far_cells_of(grid, points, rot, trans):
     """grid + (B,) bool: no point of the pose has |coord_d - (c_d + 1/2)| < 2 on every axis (the true reach is 1.5
-    cells; the extra half cell is far above any coordinate rounding)."""
-    h = smooth_input(name)
-    n = np.asarray(h.grid)
-    far = np.ones(h.grid + (h.B,), bool)
-    for b in range(h.B):
-        c = coords(h.grid, h.points, h.rot[b], h.trans[b])
+    cells; the extra half cell is far above any coordinate rounding).  The core of `far_cells`, for any cloud."""
+    n = np.asarray(grid)
+    far = np.ones(tuple(grid) + (len(rot),), bool)
+    for b in range(len(rot)):
+        c = coords(grid, points, rot[b], trans[b])
         c = c[np.all(np.isfinite(c) & (np.abs(c) < 1e6), axis=1)]
         lo = np.floor(c - 2.5).astype(np.int64) + 1  # the cells with c_d + 1/2 in (coord_d - 2, coord_d + 2)
         hi = np.ceil(c + 1.5).astype(np.int64) - 1
         assert (hi - lo).max() <= 4
-        near = np.zeros(h.grid, bool)
-        for k in itertools.product(range(5), repeat=h.n_out):
+        near = np.zeros(grid, bool)
+        for k in itertools.product(range(5), repeat=len(grid)):
             cell = lo + np.asarray(k)
             okay = np.all((cell <= hi) & (cell >= 0) & (cell < n), axis=1)
             near[tuple(cell[okay].T)] = True
         far[..., b] = ~near
-    return frozen(far)
+    return far
+
+
+@functools.lru_cache(maxsize=None)
+def far_cells(name):
+    h = smooth_input(name)
+    return frozen(far_cells_of(h.grid, h.points, h.rot, h.trans))
 
 
 def dev_args(h, s, tdt, dev, B, keep=slice(None)):

@@ -104,3 +104,32 @@ def test_an_omitted_tangent_is_a_zero_tangent(n_in, n_out):
     # ... and J is linear in the tangents: the six parts add up to the joint derivative
     assert np.linalg.norm(total - jv) <= 1e-13 * np.linalg.norm(jv)
     assert not np.any(reference(c, 2, 3, {}))
+
+
+def test_magnitudes_are_the_same_loop_on_absolute_values():
+    """`magnitudes=True` (the budget of tests/test_smooth_jvp_hard_gpu.py): for a single accepted point the sum of
+    |deposit| plus |background_dot| is |out_dot - background_dot| + |background_dot| cell by cell and every cell of
+    its 3^N stencil inside the grid counts once; for a cloud it bounds |out_dot| and counts every (point, cell)."""
+    rng = np.random.default_rng(12)
+    grid, K, B = (6, 5, 7), 2, 2
+    rot, trans = np.stack([np.eye(3)] * B), np.zeros((B, 3))
+    kw = dict(K=K, rotation_dot=rng.normal(size=(K, B, 3, 3)), translation_dot=rng.normal(size=(K, B, 3)),
+              background_dot=rng.normal(size=(K, B)), out_weight_dot=rng.normal(size=(K, B)))
+    one = np.array([[0.1, -0.95, 0.3]])  # (centre cell 0 on axis 1: a third of the stencil is dropped)
+    tan = dict(points_dot=rng.normal(size=(K, 1, 3)), point_weight_dot=rng.normal(size=(K, 1)), **kw)
+    out = JR.raster_smooth_jvp(grid, one, rot, trans, **tan)
+    A, n = JR.raster_smooth_jvp(grid, one, rot, trans, magnitudes=True, **tan)
+    bgd = kw["background_dot"]
+    assert A.shape == out.shape and n.shape == grid + (B,) and n.dtype == np.int64
+    np.testing.assert_allclose(A, np.abs(out - bgd) + np.abs(bgd), rtol=1e-14, atol=0)
+    assert np.all(n.sum(axis=(0, 1, 2)) == 18) and n.max() == 1
+    pts = rng.uniform(-1.2, 1.2, size=(200, 3))
+    tan = dict(points_dot=rng.normal(size=(K, 200, 3)), point_weight_dot=rng.normal(size=(K, 200)), **kw)
+    out = JR.raster_smooth_jvp(grid, pts, rot, trans, **tan)
+    A, n = JR.raster_smooth_jvp(grid, pts, rot, trans, magnitudes=True, **tan)
+    empty = np.broadcast_to((n == 0)[..., None, :], A.shape)
+    assert np.all(A >= np.abs(out) * (1 - 1e-12)) and np.all(A[empty] == np.abs(np.broadcast_to(bgd, A.shape))[empty])
+    _b, _idx, j0, _w, _dw = next(iter(SR._terms(grid, pts, rot[:1], trans[:1], np.float64)))
+    per_axis = [((j0[:, d, None] + np.arange(-1, 2) >= 0) & (j0[:, d, None] + np.arange(-1, 2) < grid[d])).sum(axis=1)
+                for d in range(3)]
+    assert n[..., 0].sum() == int((per_axis[0] * per_axis[1] * per_axis[2]).sum()) > 0
