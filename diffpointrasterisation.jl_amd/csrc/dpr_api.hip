@@ -305,6 +305,37 @@ void stage_mark(hipStream_t st) {
         (void)hipEventRecord(g_stage_events[g_stage_n++], st);
 }
 
+// zero_async (dpr_tiled.h): the words up to the first 16-byte boundary and behind the last one as dwords, the
+// middle as 16-byte stores, a grid-stride loop of at most 8192 blocks (a 120 MB gradient buffer: four rounds);
+// a buffer that is not made of aligned dwords (none of the library's is) byte by byte.
+__global__ __launch_bounds__(256) void k_zero_words(uint32_t* __restrict__ p, size_t words) {
+    size_t lead = ((16 - ((uintptr_t)p & 15)) & 15) / 4;
+    lead = lead < words ? lead : words;
+    uint4* __restrict__ q = (uint4*)(p + lead);
+    const size_t n4 = (words - lead) / 4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (size_t k = i; k < n4; k += stride) q[k] = make_uint4(0u, 0u, 0u, 0u);
+    for (size_t k = i; k < lead; k += stride) p[k] = 0u;
+    for (size_t k = lead + n4 * 4 + i; k < words; k += stride) p[k] = 0u;
+}
+__global__ __launch_bounds__(256) void k_zero_bytes(unsigned char* __restrict__ p, size_t bytes) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < bytes; k += stride) p[k] = 0;
+}
+hipError_t zero_async(hipStream_t st, void* p, size_t bytes) {
+    if (bytes == 0) return hipSuccess;
+    const bool words = (((uintptr_t)p | bytes) & 3) == 0;
+    const size_t items = words ? bytes / 16 + 1 : bytes;
+    size_t blocks = (items + 255) / 256;
+    blocks = blocks > 8192 ? 8192 : blocks;
+    if (words)
+        hipLaunchKernelGGL(k_zero_words, dim3((unsigned)blocks), dim3(256), 0, st, (uint32_t*)p, bytes / 4);
+    else
+        hipLaunchKernelGGL(k_zero_bytes, dim3((unsigned)blocks), dim3(256), 0, st, (unsigned char*)p, bytes);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- launch helpers
 // Pose slices (grid.y) of the per-point kernels: enough blocks to fill 256 CUs x 8 when P is small.
 // Returns the poses per slice; *slices_out: the slices that cover the B poses.
@@ -428,11 +459,11 @@ static int pullback_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64
                            const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow,
                            T* d_pw, Residual<T> rs) {
     const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    if (rs.target && rs.loss) DPR_HIP(hipMemsetAsync(rs.loss, 0, sizeof(T) * (size_t)B, st));
-    DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * NO * NI), st));
-    DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * NO), st));
-    DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
-    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
+    if (rs.target && rs.loss) DPR_HIP(zero_async(st, rs.loss, sizeof(T) * (size_t)B));
+    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * NO * NI)));
+    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * NO)));
+    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
+    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)B));
     grid_sum(st, g, G, B, d_bg, rs);
     stage_mark(st);
     if (P > 0) {
@@ -441,8 +472,8 @@ static int pullback_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64
         const int poses_per_slice = pose_slices(P, B, &slices);
         const int accumulate = slices > 1;
         if (accumulate) {
-            DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
-            if (d_pw) DPR_HIP(hipMemsetAsync(d_pw, 0, sizeof(T) * (size_t)P, st));
+            DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * NI)));
+            if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)P));
         }
         dim3 gg((unsigned)pblocks, (unsigned)slices);
         hipLaunchKernelGGL((k_bwd_gather<T, NI, NO>), gg, dim3(kBlock), 0, st, gd, P, B, g, points,
@@ -592,8 +623,8 @@ static int pullback_impl(void* stream, int algo, unsigned flags, int n_in, int n
     if (B == 0) {
         // no poses: point gradients are empty sums
         if (P > 0) {
-            DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * n_in), st));
-            if (d_pw) DPR_HIP(hipMemsetAsync(d_pw, 0, sizeof(T) * (size_t)P, st));
+            DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
+            if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)P));
         }
         return DPR_OK;
     }

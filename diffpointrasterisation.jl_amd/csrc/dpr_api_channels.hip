@@ -123,8 +123,8 @@ static int pullback_channels_impl(void* stream, int algo, unsigned flags, int n_
                     algo);
     if (B == 0) {
         if (P > 0) {
-            DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * n_in), st));
-            if (d_pw) DPR_HIP(hipMemsetAsync(d_pw, 0, sizeof(T) * (size_t)(P * C), st));
+            DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
+            if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)(P * C)));
         }
         return DPR_OK;
     }

@@ -14,10 +14,10 @@ int pullback_atomic_channels(hipStream_t st, const int64_t* grid, int64_t G, int
                              const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw) {
     const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     const int64_t planes = B * C;
-    DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * NO * NI), st));
-    DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * NO), st));
-    DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
-    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)planes, st));
+    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * NO * NI)));
+    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * NO)));
+    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
+    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)planes));
     // ds_dbackground[c, b] = sum of plane b * C + c: the single-channel grid sum over B * C planes
     grid_sum(st, g, G, planes, d_bg, Residual<T>{nullptr, T(0), nullptr});
     stage_mark(st);
@@ -27,8 +27,8 @@ int pullback_atomic_channels(hipStream_t st, const int64_t* grid, int64_t G, int
         const int poses_per_slice = pose_slices(P, B, &slices);
         const int accumulate = slices > 1;
         if (accumulate) {
-            DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
-            if (d_pw) DPR_HIP(hipMemsetAsync(d_pw, 0, sizeof(T) * (size_t)(P * C), st));
+            DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * NI)));
+            if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)(P * C)));
         }
         dim3 gg((unsigned)pblocks, (unsigned)slices);
         if (C <= 4)

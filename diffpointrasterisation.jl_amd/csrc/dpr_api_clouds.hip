@@ -214,13 +214,13 @@ static int pullback_clouds_run(hipStream_t st, int algo, unsigned flags, const i
             return DPR_OK;
         }
     }
-    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
+    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)B));
     grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
     stage_mark(st);
     if (algo == DPR_ALGO_ATOMIC || P == 0) {
-        DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * NO * NI), st));
-        DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * NO), st));
-        DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
+        DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * NO * NI)));
+        DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * NO)));
+        DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
         if (P > 0) {
             dim3 gg((unsigned)((P + kBlock - 1) / kBlock), (unsigned)(B < 65535 ? B : 65535));
             hipLaunchKernelGGL((k_clouds_bwd_atomic<T, NI, NO>), gg, dim3(kBlock), 0, st, gd, P, B, g, points, rot,

@@ -94,17 +94,17 @@ static int sample_pullback_run(hipStream_t st, int algo, unsigned flags, const i
                                size_t ws_bytes) {
     const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     const bool tiled = algo == DPR_ALGO_TILED;
-    if (d_rot) DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * NO * NI), st));
-    if (d_trans) DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * NO), st));
-    if (d_img && (!tiled || P == 0)) DPR_HIP(hipMemsetAsync(d_img, 0, sizeof(T) * (size_t)(B * G), st));
-    if (d_pts && B == 0) DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
+    if (d_rot) DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * NO * NI)));
+    if (d_trans) DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * NO)));
+    if (d_img && (!tiled || P == 0)) DPR_HIP(zero_async(st, d_img, sizeof(T) * (size_t)(B * G)));
+    if (d_pts && B == 0) DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * NI)));
     if (P == 0 || B == 0) return DPR_OK;
     T* const kernel_img = tiled ? nullptr : d_img;
     if (kernel_img || d_pts || d_rot || d_trans) {
         int64_t slices = 1;
         const int pps = pose_slices(P, B, &slices);
         const int accumulate = slices > 1;
-        if (accumulate && d_pts) DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
+        if (accumulate && d_pts) DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * NI)));
         dim3 gg((unsigned)((P + kBlock - 1) / kBlock), (unsigned)slices);
         hipLaunchKernelGGL((k_sample_bwd<T, NI, NO>), gg, dim3(kBlock), 0, st, gd, P, B, dv, image, points, rot,
                            trans, kernel_img, d_pts, d_rot, d_trans, pps, accumulate);

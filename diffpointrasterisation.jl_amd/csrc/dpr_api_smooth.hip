@@ -130,10 +130,10 @@ static int pullback_smooth_impl(void* stream, int algo, unsigned flags, int n_in
         return rc;
     hipStream_t st = (hipStream_t)stream;
     stage_mark(st);
-    DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * n_out * n_in), st));
-    DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * n_out), st));
-    DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
-    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
+    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * n_out * n_in)));
+    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * n_out)));
+    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
+    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)B));
     grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
     stage_mark(st);
     if (P == 0) return DPR_OK;  // (the per-pose sums are 0, ds_dbackground is done; pose_slices divides by the blocks)
@@ -260,10 +260,10 @@ static int sample_smooth_pullback_impl(void* stream, int algo, unsigned flags, i
     if (int rc = check_alignment<T>(ws, {dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans})) return rc;
     hipStream_t st = (hipStream_t)stream;
     stage_mark(st);
-    if (d_rot) DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * n_out * n_in), st));
-    if (d_trans) DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * n_out), st));
-    if (d_img) DPR_HIP(hipMemsetAsync(d_img, 0, sizeof(T) * (size_t)(B * G), st));
-    if (d_pts && B == 0) DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * n_in), st));
+    if (d_rot) DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * n_out * n_in)));
+    if (d_trans) DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * n_out)));
+    if (d_img) DPR_HIP(zero_async(st, d_img, sizeof(T) * (size_t)(B * G)));
+    if (d_pts && B == 0) DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
     if (P == 0 || B == 0) return DPR_OK;
     int64_t slices = 1;
     const int pps = pose_slices(P, B, &slices);
@@ -494,10 +494,10 @@ static int pullback_smooth_clouds_impl(void* stream, int algo, unsigned flags, i
         return rc;
     hipStream_t st = (hipStream_t)stream;
     stage_mark(st);
-    DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * n_out * n_in), st));
-    DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * n_out), st));
-    DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
-    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
+    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * n_out * n_in)));
+    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * n_out)));
+    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
+    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)B));
     grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
     stage_mark(st);
     return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
@@ -617,10 +617,10 @@ static int pullback_smooth_channels_impl(void* stream, int algo, unsigned flags,
     hipStream_t st = (hipStream_t)stream;
     stage_mark(st);
     const int64_t planes = B * C;
-    DPR_HIP(hipMemsetAsync(d_rot, 0, sizeof(T) * (size_t)(B * n_out * n_in), st));
-    DPR_HIP(hipMemsetAsync(d_trans, 0, sizeof(T) * (size_t)(B * n_out), st));
-    DPR_HIP(hipMemsetAsync(d_ow, 0, sizeof(T) * (size_t)B, st));
-    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)planes, st));
+    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * n_out * n_in)));
+    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * n_out)));
+    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
+    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)planes));
     // ds_dbackground[b, c] = sum of plane b * C + c
     grid_sum(st, g, G, planes, d_bg, Residual<T>{nullptr, T(0), nullptr});
     stage_mark(st);

@@ -422,7 +422,7 @@ static int build_lists(hipStream_t st, const GridDesc<NO>& gd, const CGeom<NO>& 
     uint32_t* start = (uint32_t*)(ws + pl.off_start);
     uint32_t* order = (uint32_t*)(ws + pl.off_order);
     uint32_t* list = (uint32_t*)(ws + pl.off_list);
-    DPR_HIP(hipMemsetAsync(count, 0, (size_t)nb * tg.NT * 4, st));
+    DPR_HIP(zero_async(st, count, (size_t)nb * tg.NT * 4));
     const unsigned cblocks = (unsigned)((pl.n_chunks + 3) / 4);
     hipLaunchKernelGGL((k_chunk_sets<T, NI, NO>), dim3(cblocks, (unsigned)nb), dim3(256), 0, st, gd,
                        tg, P, pl.n_chunks, points, rot, trans, b0, sets, nset, count);

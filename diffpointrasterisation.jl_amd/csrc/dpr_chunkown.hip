@@ -1100,8 +1100,8 @@ int pullback_chunkown(hipStream_t st, unsigned flags, const int64_t* grid, int64
     }
     stage_mark(st);
     // ds_dbackground[b] = sum(ds_dout[.., b]) (and the loss of the residual form)
-    if (rs.target && rs.loss) DPR_HIP(hipMemsetAsync(rs.loss, 0, sizeof(T) * (size_t)B, st));
-    DPR_HIP(hipMemsetAsync(d_bg, 0, sizeof(T) * (size_t)B, st));
+    if (rs.target && rs.loss) DPR_HIP(zero_async(st, rs.loss, sizeof(T) * (size_t)B));
+    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)B));
     for (int64_t b0 = 0; b0 < B; b0 += 65535) {
         const int64_t nb = (B - b0 < 65535) ? B - b0 : 65535;
         const int64_t want = grid_sum_blocks(G, nb);
@@ -1116,8 +1116,8 @@ int pullback_chunkown(hipStream_t st, unsigned flags, const int64_t* grid, int64
     const int accumulate = pl.slices > 1;
     if (P > 0) {
         if (accumulate) {
-            DPR_HIP(hipMemsetAsync(gp, 0, sizeof(T) * (size_t)(P * NI), st));
-            if (gw) DPR_HIP(hipMemsetAsync(gw, 0, sizeof(T) * (size_t)P, st));
+            DPR_HIP(zero_async(st, gp, sizeof(T) * (size_t)(P * NI)));
+            if (gw) DPR_HIP(zero_async(st, gw, sizeof(T) * (size_t)P));
         }
         dim3 gg((unsigned)pl.nblk, (unsigned)pl.slices);
         if (pws)
@@ -1129,7 +1129,7 @@ int pullback_chunkown(hipStream_t st, unsigned flags, const int64_t* grid, int64
                                pl.poses_per_slice, g, pts, pws, rot, trans, ow, gp, gw, partials,
                                accumulate, rs, want, hdr, perm);
     } else {
-        DPR_HIP(hipMemsetAsync(partials, 0, (size_t)(2 * NI + 3) * (size_t)B * pl.nblk * 8, st));
+        DPR_HIP(zero_async(st, partials, (size_t)(2 * NI + 3) * (size_t)B * pl.nblk * 8));
     }
     stage_mark(st);
     for (int64_t b0 = 0; b0 < B; b0 += 65535) {

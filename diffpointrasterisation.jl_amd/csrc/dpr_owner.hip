@@ -1517,7 +1517,7 @@ static int own_prepare(hipStream_t st, const OGeom& tg, const GridDesc<3>& gd, c
                            pl.nL1, pl.nL2, (const IBox*)(ws + pl.off_b1), (const float*)mw1,
                            (IBox*)(ws + pl.off_b2), (float*)(ws + pl.off_mw2));
     } else {
-        DPR_HIP(hipMemsetAsync(ctl, 0, (size_t)ctl_words * 4, st));
+        DPR_HIP(zero_async(st, ctl, (size_t)ctl_words * 4));
     }
     stage_mark(st);
     OwnPlanArgs pa = plan_args(pl, ws);

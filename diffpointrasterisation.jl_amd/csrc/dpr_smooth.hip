@@ -1235,8 +1235,8 @@ int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
     const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     const int accumulate = slices > 1;
     if (accumulate) {
-        DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
-        if (d_pw) DPR_HIP(hipMemsetAsync(d_pw, 0, sizeof(T) * (size_t)P, st));
+        DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * NI)));
+        if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)P));
     }
     dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)slices);
     hipLaunchKernelGGL((k_smooth_bwd<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, g, points, rot, trans, ow, pw,
@@ -1264,7 +1264,7 @@ int sample_smooth_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
     if (P <= 0 || B <= 0 || !(d_img || d_pts || d_rot || d_trans)) return DPR_OK;
     const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     const int accumulate = slices > 1;
-    if (accumulate && d_pts) DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
+    if (accumulate && d_pts) DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * NI)));
     dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)slices);
     hipLaunchKernelGGL((k_sample_smooth_bwd<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, dv, image, points, rot,
                        trans, d_img, d_pts, d_rot, d_trans, poses_per_slice, accumulate);

@@ -419,8 +419,8 @@ int smooth_channels_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, i
     const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     const int accumulate = slices > 1;
     if (accumulate) {
-        DPR_HIP(hipMemsetAsync(d_pts, 0, sizeof(T) * (size_t)(P * NI), st));
-        if (d_pw) DPR_HIP(hipMemsetAsync(d_pw, 0, sizeof(T) * (size_t)(P * C), st));
+        DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * NI)));
+        if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)(P * C)));
     }
     dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)slices);
     if (C <= 4)

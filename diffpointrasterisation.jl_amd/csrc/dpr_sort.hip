@@ -104,12 +104,29 @@ static size_t radix_temp_bytes(int64_t P) {
     return temp;
 }
 
+// rocPRIM sorts up to radix_sort_config<>::merge_sort_limit keys (2^20) with kernels only: one block, or block sorts
+// and merges.  Above that it takes its onesweep path, which clears its digit histogram and look-back states with
+// hipMemsetAsync on the caller's stream (rocprim/device/device_radix_sort.hpp, radix_sort_onesweep_global_offsets
+// and radix_sort_onesweep_iteration).  A captured hipMemsetAsync is not replayed reliably (zero_async, dpr_tiled.h),
+// and a histogram that is not cleared makes the scatter offsets of the sort wild addresses: so a sort of more than
+// 2^20 keys on a stream that is being captured is REFUSED (hipErrorStreamCaptureUnsupported; the entry point
+// returns DPR_ERR_HIP), whatever was enqueued before it in the call.  Outside a capture nothing changes.
+constexpr size_t kRadixKernelOnlyKeys = rocprim::radix_sort_config<>::merge_sort_limit;
+static hipError_t refuse_onesweep_under_capture(size_t n, hipStream_t st) {
+    if (n <= kRadixKernelOnlyKeys) return hipSuccess;
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(st, &status);
+    if (e != hipSuccess) return e;
+    return status == hipStreamCaptureStatusNone ? hipSuccess : hipErrorStreamCaptureUnsupported;
+}
+
 // the same instantiation for the other callers of the library (dpr_ordered.hip): bytes of temporary storage, and the
 // stable sort of (key, value) pairs on key bits [begin_bit, end_bit)
 size_t radix_pairs_temp_bytes(int64_t P) { return radix_temp_bytes(P < 1 ? 1 : P); }
 hipError_t radix_sort_pairs_u32(void* temp, size_t temp_bytes, uint32_t* keys_in, uint32_t* keys_out,
                                 uint32_t* vals_in, uint32_t* vals_out, size_t n, unsigned begin_bit,
                                 unsigned end_bit, hipStream_t st) {
+    if (const hipError_t e = refuse_onesweep_under_capture(n, st)) return e;
     return rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit,
                                      st);
 }
@@ -162,8 +179,10 @@ int sort_points_impl(void* stream, int n_in, int64_t P, const T* points, T* poin
     // -- and 15 key bits are two radix passes instead of three.
     constexpr int kCoarseBits = 5;
     const unsigned begin_bit = (!fine && n_in == 3) ? (unsigned)(3 * (8 - kCoarseBits)) : 0u;
-    hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, idx_in, perm,
-                                             (size_t)P, begin_bit, (fine && n_in == 3) ? 30 : 24, st);
+    hipError_t e = refuse_onesweep_under_capture((size_t)P, st);
+    if (e == hipSuccess)
+        e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, idx_in, perm, (size_t)P, begin_bit,
+                                      (fine && n_in == 3) ? 30 : 24, st);
     if (e != hipSuccess)
         return fail(DPR_ERR_HIP, "rocprim::radix_sort_pairs failed: %s", hipGetErrorString(e));
     const dim3 ggrid((unsigned)((P + 256 * kGatherPer - 1) / (256 * kGatherPer)));

@@ -33,6 +33,18 @@ template <int NO> GridDesc<NO> make_grid_desc(const int64_t* grid, int64_t G) {
 // records hipEvent k (if stage timing is armed, see dpr_stage_timing_begin) on `st`
 void stage_mark(hipStream_t st);
 
+// `bytes` bytes at `p` become zero, by a kernel on `st` (dpr_api.hip; nothing is launched for 0 bytes).  Returns
+// hipGetLastError() after the launch: a sticky error of an earlier launch of the same driver surfaces here, at the next
+// zeroing, and not only at the driver's final check.
+// Every driver zeroes through this and none through hipMemsetAsync: the memset node that a captured hipMemsetAsync
+// becomes is not replayed reliably (tools/graph_memset_probe.py, profiles/graph_memset_probe.txt: six memsets of
+// 12 .. 36 012 bytes in one graph are right on the first replay and hold 0x50 / 0xfe bytes and pointer-like words from
+// the second on; the channel pullback's six already on the first).  What is left of hipMemsetAsync in the library:
+//  * rocPRIM's onesweep radix sort (more than 2^20 keys) clears its histogram with it: dpr_sort.hip refuses such a
+//    sort on a stream that is being captured;
+//  * dpr_comm.hip's 0xff fill of a failed rank's gradients, in front of a collective that no graph holds.
+hipError_t zero_async(hipStream_t st, void* p, size_t bytes);
+
 bool tiled_supported(int n_out, const int64_t* grid);
 bool tiled_preferred(int op, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t G);
 size_t tiled_workspace_bytes(size_t elem, int op, unsigned flags, int n_in, int n_out,

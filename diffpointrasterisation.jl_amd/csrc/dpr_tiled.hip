@@ -3274,10 +3274,8 @@ static int bin_points_local(hipStream_t st, const GridDesc<NO>& gd, const TileGe
                             bool keep_valid, const T* hdr_points, const T* hdr_pw) {
     // ndesc[NT] | npts[NT] | - | max|pw| bits, and behind them the placement's cursors
     const size_t ltot_bytes = (pl.off_dcursor - pl.off_ltot) + (size_t)tg.NT * 4;
-    if (nb > 1)
-        DPR_HIP(hipMemset2DAsync(ws + pl.off_ltot, pl.pose_stride, 0, ltot_bytes, (size_t)nb, st));
-    else
-        DPR_HIP(hipMemsetAsync(ws + pl.off_ltot, 0, ltot_bytes, st));
+    for (int j = 0; j < nb; ++j)  // (nb <= 16 pose copies, pose_stride bytes apart)
+        DPR_HIP(zero_async(st, ws + (size_t)j * pl.pose_stride + pl.off_ltot, ltot_bytes));
     stage_mark(st);
     const uint32_t spare = (uint32_t)(pl.nsub * pl.sub);
     const size_t lds = (size_t)tg.NT * 4;
@@ -3710,7 +3708,7 @@ int raster_tiled_channels(hipStream_t st, const int64_t* grid, int64_t G, int64_
     for (int64_t b = 0; b < B; ++b) {
         if (int rc = pb.bin(st, P, points, rot, trans, pw, b)) return rc;
         if (pw) {
-            DPR_HIP(hipMemsetAsync(keys, 0, (size_t)C * 2 * 4, st));
+            DPR_HIP(zero_async(st, keys, (size_t)C * 2 * 4));
             hipLaunchKernelGGL(k_channel_weights<T>, dim3(pb.pass_blocks), dim3(256), 0, st, P, C, pw, pb.rec(),
                                pb.n_rec(), w_sorted, P + 1, keys);
         }
@@ -3800,7 +3798,7 @@ int raster_tiled_jvp(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, 
             JvpTangents<T> tk = tan;
             tk.points = tan.points ? tan.points + (int64_t)k * P * NI : nullptr;
             tk.pw = tan.pw ? tan.pw + (int64_t)k * P : nullptr;
-            DPR_HIP(hipMemsetAsync(keys, 0, 2 * 4, st));
+            DPR_HIP(zero_async(st, keys, 2 * 4));
             hipLaunchKernelGGL((k_jvp_coeffs<T, NI, NO>), dim3(pb.pass_blocks), dim3(256), 0, st, pb.gd, P, pb.rec(),
                                pb.n_rec(), rot_b, trans_b, ow_b, pw, tk, tan.rot ? tan.rot + kb * (NO * NI) : nullptr,
                                tan.trans ? tan.trans + kb * NO : nullptr, tan.ow ? tan.ow + kb : nullptr, coef, keys);

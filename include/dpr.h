@@ -33,7 +33,27 @@
  * All data pointers are DEVICE pointers owned by the caller (including the
  * workspace).  Calls only enqueue work on `stream` (a hipStream_t; NULL = the
  * default stream); they never synchronise the device and keep no device memory
- * or global state between calls.  Supported (n_in, n_out): 1 <= n_in, n_out <= 4 in any
+ * or global state between calls.
+ * THE STREAM CONTRACT.  Every entry point of every family only enqueues on `stream`, and can be
+ * captured into a HIP graph: no synchronising call, no allocation, no launch or memset on another
+ * stream, and what a captured call leaves in the graph is kernel nodes only (the library zeroes with
+ * a kernel: the memset node of a captured hipMemsetAsync is not replayed reliably).
+ * ONE EXCEPTION, refused and never silent: the paths that radix-sort -- DPR_ALGO_ORDERED's forward
+ * (P keys per pose), the smooth families on DPR_ALGO_TILED (P keys per pose; per-pose clouds: P times
+ * the poses of a group), dpr_sort_points_* and the Hilbert sort inside 3-D DPR_ALGO_CHUNKED batches
+ * and 2-D ones of more than 96 poses (P keys) -- use rocPRIM, whose sort of more than 2^20 keys
+ * clears its histograms with hipMemsetAsync.  On a stream that is being captured such a call
+ * returns DPR_ERR_HIP ("operation not permitted when stream is capturing"; kernels of the call in
+ * front of the sort may already be nodes of the capture, which the caller discards).  Up to 2^20
+ * keys these paths capture like the others, and outside a capture they run at any size.
+ * Host threads may call concurrently, each on its own stream, outputs and workspace.
+ * THE WORKSPACE CONTRACT (dpr_workspace_bytes_* below).  The initial contents of the workspace do
+ * not matter: every piece of a layout is written by the call before the call reads it.  The
+ * library writes only inside [workspace, workspace + workspace_bytes); with a workspace_bytes
+ * equal to the query it uses no more.  What a call leaves in the workspace is unspecified, except
+ * what a DPR_FLAG_KEEP_BINNING forward leaves for its DPR_FLAG_REUSE_BINNING pullback.
+ * tests/test_workspace_contract_gpu.py and tests/test_families_streams_gpu.py hold every family to both.
+ * Supported (n_in, n_out): 1 <= n_in, n_out <= 4 in any
  * combination -- the reference is generic in both (src/raster.jl:5-13).
  * (2,2), (3,3), (3,2) -- the shapes the reference tests (src/raster.jl:112,
  * test/data.jl:13-19) -- have every algorithm; all other pairs (incl. n_out > n_in and 4-D) run on
@@ -450,7 +470,12 @@ int dpr_stage_timing_end(void);
  * are); every non-NULL data pointer must be aligned to its element type
  * (DPR_ERR_INVALID_ARG otherwise, before any launch).  DPR_ALGO_TILED with a shape it would
  * refuse (a tile layer of more than 16384 tiles, P >= 2^32, KEEP / REUSE flags on a grid of more
- * than 32768 tiles) returns (size_t)-1 here too. */
+ * than 32768 tiles) returns (size_t)-1 here too.
+ * Contents and bounds (every dpr_workspace_bytes*_ex_* query of this header alike): the initial contents
+ * of the workspace do not matter -- a long-lived buffer that other calls have written to serves as it is,
+ * no clearing between calls; the library writes only inside [workspace, workspace + workspace_bytes), and
+ * with a workspace_bytes equal to the query it uses no more; what a call leaves in the workspace is
+ * unspecified, except what a KEEP forward leaves for its REUSE pullback. */
 size_t dpr_workspace_bytes_f32(int op, int algo, int n_in, int n_out, const int64_t *grid,
                                int64_t P, int64_t B);
 size_t dpr_workspace_bytes_f64(int op, int algo, int n_in, int n_out, const int64_t *grid,

@@ -122,7 +122,7 @@ def test_resolve_algo_clouds_matches_the_recorded_table():
 def test_cloud_entry_points_refuse_bad_arguments_before_any_launch():
     """Dummy device pointers that are never dereferenced: every call below fails in the host checks."""
     L = dpr_amd.lib()
-    a, gp = _g((16, 16, 16))
+    a, gp = _g((16, 16, 16, 16))  # (four sizes: the (4, 4) pair below reads grid[3]; n_out = 3 reads the first three)
     d = ctypes.c_void_p(256)
     for suf in ("f32", "f64"):
         fwd = getattr(L, f"dpr_raster_clouds_ex_{suf}")
