@@ -29,6 +29,7 @@ from .smooth_clouds import (raster_pullback_smooth_clouds_, raster_smooth_clouds
 from .smooth_channels import (raster_pullback_smooth_channels_, raster_smooth_channels, raster_smooth_channels_,
                               raster_smooth_channels_ad, resolve_algo_smooth_channels,
                               workspace_bytes_smooth_channels)
+from .bodies import (raster_bodies, raster_bodies_, raster_bodies_ad, raster_pullback_bodies_, resolve_algo_bodies)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -54,4 +55,5 @@ __all__ = [
     "resolve_algo_smooth_clouds", "workspace_bytes_smooth_clouds",
     "raster_smooth_channels", "raster_smooth_channels_", "raster_pullback_smooth_channels_",
     "raster_smooth_channels_ad", "resolve_algo_smooth_channels", "workspace_bytes_smooth_channels",
+    "raster_bodies", "raster_bodies_", "raster_pullback_bodies_", "raster_bodies_ad", "resolve_algo_bodies",
 ]

@@ -1249,6 +1249,77 @@ int dpr_raster_pullback_smooth_channels_ex_f64(void *stream, int algo, unsigned 
                                                double *ds_dtranslation, double *ds_dbackground, double *ds_dout_weight,
                                                double *ds_dpoint_weight, void *workspace, size_t workspace_bytes);
 
+/* ---- RIGID BODIES: one cloud of K rigid bodies, a pose per (image, body) -------------------------------------------
+ * Point p belongs to body[p] in [0, K) and is seen in image b through the pose of its body in that image:
+ *     out[i.., b] = background[b]
+ *                 + out_weight[b] * sum_p point_weight[p] * voxel_weight(i..; R[b, body[p]] points[p] + t[b, body[p]])
+ * Cell choice, weights, drop rules and the fp operation order per (point, pose) are those of dpr_raster_*.  With
+ * background 0, plane b is the sum over k of dpr_raster_* of the points with body[p] == k under pose (b, k), and
+ * every gradient is the matching piece of dpr_raster_pullback_* of that subset: ds_dpoints[p] and
+ * ds_dpoint_weight[p] sum over the images, ds_drotation[b, k] and ds_dtranslation[b, k] over the points of body k,
+ * ds_dbackground[b] and ds_dout_weight[b] over all points.  The reference cell is held fixed, as everywhere.
+ * Not in the reference.  It stands between dpr_raster_* (K = 1) and PER-POSE CLOUDS (every point free), which
+ * would need the B warped copies of the cloud in memory.
+ * Layouts (column-major like the rest of this header):
+ *   points, point_weight, ds_dpoints, ds_dpoint_weight    as for dpr_raster_ex_* (one cloud, P points)
+ *   body                        P values of int32_t (declared const void *; 4-byte aligned), read-only, no gradient
+ *   rotation, ds_drotation      n_out x n_in x K x B: pose (b, k) at index b * K + k, each column-major
+ *                               (a contiguous (B, K, n_in, n_out) tensor)
+ *   translation, ds_dtranslation   n_out x K x B: pose (b, k) at (b * K + k) * n_out
+ *   background, out_weight, ds_dbackground, ds_dout_weight    B values; out, ds_dout: grid x B
+ * Dropped points.  A point whose body index lies outside [0, K) -- negative values included -- deposits nothing
+ * and gets ds_dpoints = ds_dpoint_weight = 0, like a point outside the grid; the index is checked on the device,
+ * lane by lane, before it addresses anything.  A body no accepted point belongs to gets gradients that are exactly
+ * 0.  `out` and all six pullback outputs are overwritten.  P = 0 and B = 0 are valid: out = background, the
+ * gradients are 0 (ds_dpoints and ds_dpoint_weight too when B = 0), ds_dbackground the grid sum.
+ * (n_in, n_out): (2,2), (3,3), (3,2).  K >= 1 and B * K <= 2^31 - 1.
+ * Algorithm: DPR_ALGO_ATOMIC (and AUTO, which resolves to it), workspace 0 -- dpr_workspace_bytes_bodies_ex_*
+ * returns 0 for every accepted call and exists so that a later binned path changes no prototype.  Forward: one
+ * thread per point, global float atomics, the images over grid.y.  Pullback: one thread per point with the image
+ * loop inside; ds_dpoints / ds_dpoint_weight are plain stores when one launch covers all images and float atomics
+ * onto zeroed buffers when the images are cut into slices (few points, many images), as in dpr_raster_pullback_*.
+ * A wave whose points share one body -- SORT THE CLOUD BY BODY -- reads its pose with scalar loads and reduces its
+ * pose sums wave -> block -> one float atomic per value; a wave with several bodies gathers its poses per lane and
+ * reduces per body (masked wave sums over the lanes of each body in turn, one atomic per value and body).  Every
+ * order is that of float atomics: results vary at rounding level from run to run.
+ * Flags: DPR_FLAG_NO_POINT_WEIGHT_GRAD keeps its meaning (ds_dpoint_weight may then be NULL);
+ * DPR_FLAG_COHERENT_POINTS is accepted and ignored.
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): a pair outside the three
+ * DPR_ERR_UNSUPPORTED_DIMS; a bad op, negative P / B, a bad grid, K < 1, B * K beyond 2^31 - 1, a NULL out, points,
+ * body, rotation or translation while P * B > 0 (a NULL out or pullback output while B > 0), a misaligned data pointer
+ * DPR_ERR_INVALID_ARG; any algorithm but AUTO / DPR_ALGO_ATOMIC, KEEP / REUSE, DPR_FLAG_MAX_POSE_GROUP and
+ * DPR_OP_RESIDUAL_PULLBACK DPR_ERR_UNSUPPORTED_ALGO.  dpr_workspace_bytes_bodies_ex_* returns (size_t)-1 for every
+ * refused combination; dpr_resolve_algo_bodies a negative status, DPR_ALGO_ATOMIC otherwise. */
+int dpr_resolve_algo_bodies(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B, int64_t K);
+size_t dpr_workspace_bytes_bodies_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                         const int64_t *grid, int64_t P, int64_t B, int64_t K);
+size_t dpr_workspace_bytes_bodies_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                         const int64_t *grid, int64_t P, int64_t B, int64_t K);
+int dpr_raster_bodies_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                             int64_t P, int64_t B, int64_t K, float *out, const float *points, const void *body,
+                             const float *rotation, const float *translation, const float *background,
+                             const float *out_weight, const float *point_weight, void *workspace,
+                             size_t workspace_bytes);
+int dpr_raster_bodies_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                             int64_t P, int64_t B, int64_t K, double *out, const double *points, const void *body,
+                             const double *rotation, const double *translation, const double *background,
+                             const double *out_weight, const double *point_weight, void *workspace,
+                             size_t workspace_bytes);
+int dpr_raster_pullback_bodies_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, int64_t K, const float *ds_dout,
+                                      const float *points, const void *body, const float *rotation,
+                                      const float *translation, const float *out_weight, const float *point_weight,
+                                      float *ds_dpoints, float *ds_drotation, float *ds_dtranslation,
+                                      float *ds_dbackground, float *ds_dout_weight, float *ds_dpoint_weight,
+                                      void *workspace, size_t workspace_bytes);
+int dpr_raster_pullback_bodies_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, int64_t K, const double *ds_dout,
+                                      const double *points, const void *body, const double *rotation,
+                                      const double *translation, const double *out_weight,
+                                      const double *point_weight, double *ds_dpoints, double *ds_drotation,
+                                      double *ds_dtranslation, double *ds_dbackground, double *ds_dout_weight,
+                                      double *ds_dpoint_weight, void *workspace, size_t workspace_bytes);
+
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
  * not in the reference; every algorithm here is faster on coherent input and the sort only depends
