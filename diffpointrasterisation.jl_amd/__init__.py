@@ -30,6 +30,8 @@ from .smooth_channels import (raster_pullback_smooth_channels_, raster_smooth_ch
                               raster_smooth_channels_ad, resolve_algo_smooth_channels,
                               workspace_bytes_smooth_channels)
 from .bodies import (raster_bodies, raster_bodies_, raster_bodies_ad, raster_pullback_bodies_, resolve_algo_bodies)
+from .smooth_bodies import (raster_pullback_smooth_bodies_, raster_smooth_bodies, raster_smooth_bodies_,
+                            raster_smooth_bodies_ad, resolve_algo_smooth_bodies)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -56,4 +58,6 @@ __all__ = [
     "raster_smooth_channels", "raster_smooth_channels_", "raster_pullback_smooth_channels_",
     "raster_smooth_channels_ad", "resolve_algo_smooth_channels", "workspace_bytes_smooth_channels",
     "raster_bodies", "raster_bodies_", "raster_pullback_bodies_", "raster_bodies_ad", "resolve_algo_bodies",
+    "raster_smooth_bodies", "raster_smooth_bodies_", "raster_pullback_smooth_bodies_", "raster_smooth_bodies_ad",
+    "resolve_algo_smooth_bodies",
 ]

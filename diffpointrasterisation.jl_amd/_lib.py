@@ -82,6 +82,9 @@ EXPORTS = [
     "dpr_resolve_algo_bodies", "dpr_workspace_bytes_bodies_ex_f32", "dpr_workspace_bytes_bodies_ex_f64",
     "dpr_raster_bodies_ex_f32", "dpr_raster_bodies_ex_f64",
     "dpr_raster_pullback_bodies_ex_f32", "dpr_raster_pullback_bodies_ex_f64",
+    "dpr_resolve_algo_smooth_bodies", "dpr_workspace_bytes_smooth_bodies_ex_f32",
+    "dpr_workspace_bytes_smooth_bodies_ex_f64", "dpr_raster_smooth_bodies_ex_f32", "dpr_raster_smooth_bodies_ex_f64",
+    "dpr_raster_pullback_smooth_bodies_ex_f32", "dpr_raster_pullback_smooth_bodies_ex_f64",
 ]
 
 _lib = None
@@ -293,6 +296,19 @@ def lib() -> ctypes.CDLL:
         f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 8 + [vp, sz]
         # ..., K, ds_dout, points, body, rot, trans, ow, pw, 6 outputs, ws, ws_bytes
         f = getattr(L, f"dpr_raster_pullback_bodies_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 13 + [vp, sz]
+    L.dpr_resolve_algo_smooth_bodies.restype = i
+    L.dpr_resolve_algo_smooth_bodies.argtypes = [i, i, i, vp, i64, i64, i64]
+    for suf in ("f32", "f64"):
+        f = getattr(L, f"dpr_workspace_bytes_smooth_bodies_ex_{suf}")
+        f.restype = sz
+        f.argtypes = [i, i, ctypes.c_uint, i, i, vp, i64, i64, i64]
+        # the argument lists of dpr_raster_bodies_ex_* / dpr_raster_pullback_bodies_ex_*
+        f = getattr(L, f"dpr_raster_smooth_bodies_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 8 + [vp, sz]
+        f = getattr(L, f"dpr_raster_pullback_smooth_bodies_ex_{suf}")
         f.restype = i
         f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 13 + [vp, sz]
     L.dpr_comm_unique_id.restype = i

@@ -88,6 +88,16 @@ template <typename T, int NI, int NO>
 int smooth_bin_pose(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int64_t b, const T* points, const T* rot,
                     const T* trans);
 
+// The workspace of one binning of `P` sorted entries over `tiles` keys (offsets of its pieces, `total` bytes; all 0
+// for P <= 0), and the start table over sorted keys (k_smooth_ranges, compiled in dpr_smooth.hip only): start[k] =
+// first position with key >= k for k = 0 .. entries - 1.  For the grouped launchers of dpr_smooth.hip and
+// dpr_smooth_bodies.hip.
+struct SmoothPlan {
+    size_t off_keys_in, off_keys_out, off_idx_in, off_idx_out, off_temp, temp_bytes, off_start, total;
+};
+SmoothPlan smooth_plan(int64_t tiles, int64_t P, int64_t P_last = 0);
+int smooth_ranges(hipStream_t st, const uint32_t* keys, uint32_t count, uint64_t entries, int bits, uint32_t* start);
+
 // C weights per point (include/dpr.h, "SMOOTH SPLAT, MULTI-CHANNEL"; kernels: dpr_smooth_channels.hip): pw is
 // P x C with a point's weights contiguous, plane (c, b) of out / g at (b * C + c) * G.  The same contract with the
 // caller as above: `out` holds the B * C backgrounds already, the per-pose sums are zeroed and ds_dbackground is done

@@ -72,58 +72,7 @@ __global__ __launch_bounds__(kSmBlock) void k_smooth_fwd_atomic(GridDesc<NO> gd,
 }
 
 // ---------------------------------------------------------------- DPR_ALGO_ATOMIC pullback
-// The sums of one (point, pose) without out_weight * point_weight:
-//   W = sum_s g[j0 + s] prod_d w_d(s_d),   dcoord[k] = sum_s g[j0 + s] w'_k(s_k) prod_{d != k} w_d(s_d).
-// The nine gathers of a plane (axes 0 and 1) are requested before the first is used; a dropped cell fetches cell 0
-// of the pose and is replaced by 0 (a select, not a multiplication).  3-D: plane after plane, so that nine values
-// are live at a time, not 27.
-template <typename T, int NO, typename Fetch>
-__device__ __forceinline__ void smooth_point_backward(const int (&j0)[NO], const T (&u)[NO], const GridDesc<NO>& gd,
-                                                      Fetch fetch, T (&dcoord)[NO], T& W) {
-    const SmoothAxes<T, NO> ax = smooth_axes<T, NO>(j0, u, gd);
-    T dw[NO][3];
-#pragma unroll
-    for (int d = 0; d < NO; ++d) spline_derivatives<T>(u[d], dw[d]);
-    auto plane = [&](int base, bool vb, T& S, T& S0, T& S1) {
-        T gq[3][3];
-#pragma unroll
-        for (int k1 = 0; k1 < 3; ++k1)
-#pragma unroll
-            for (int k0 = 0; k0 < 3; ++k0) {
-                const bool v = vb && ax.in[1][k1] && ax.in[0][k0];
-                const T x = fetch(v ? base + ax.off[1][k1] + ax.off[0][k0] : 0);
-                gq[k1][k0] = v ? x : T(0);
-            }
-        S = T(0);
-        S0 = T(0);
-        S1 = T(0);
-#pragma unroll
-        for (int k1 = 0; k1 < 3; ++k1) {
-            const T a = (gq[k1][0] * ax.w[0][0] + gq[k1][1] * ax.w[0][1]) + gq[k1][2] * ax.w[0][2];
-            const T da = (gq[k1][0] * dw[0][0] + gq[k1][1] * dw[0][1]) + gq[k1][2] * dw[0][2];
-            S += a * ax.w[1][k1];
-            S0 += da * ax.w[1][k1];
-            S1 += a * dw[1][k1];
-        }
-    };
-    if constexpr (NO == 2) {
-        plane(0, true, W, dcoord[0], dcoord[1]);
-    } else {
-        W = T(0);
-#pragma unroll
-        for (int d = 0; d < NO; ++d) dcoord[d] = T(0);
-#pragma unroll
-        for (int k2 = 0; k2 < 3; ++k2) {
-            T S, S0, S1;
-            plane(ax.off[2][k2], ax.in[2][k2], S, S0, S1);
-            W += S * ax.w[2][k2];
-            dcoord[0] += S0 * ax.w[2][k2];
-            dcoord[1] += S1 * ax.w[2][k2];
-            dcoord[2] += S * dw[2][k2];
-        }
-    }
-}
-
+// (the point term, smooth_point_backward: dpr_smooth_device.h)
 // Pre-zeroed: ds_drotation, ds_dtranslation, ds_dout_weight; with accumulate_points also ds_dpoints and
 // ds_dpoint_weight (the poses are cut into slices on grid.y, every slice adds its share with atomics).
 template <typename T, int NI, int NO>
@@ -1007,11 +956,9 @@ int64_t smooth_tile_count(int n_out, const int64_t* grid, int64_t P) {
     return tiles < (int64_t)0x7fffffffLL ? tiles : 0;  // (also the largest launch: one workgroup per tile)
 }
 
-struct SmoothPlan {
-    size_t off_keys_in, off_keys_out, off_idx_in, off_idx_out, off_temp, temp_bytes, off_start, total;
-};
-// (P_last: a second, smaller count the same storage must sort -- the last group of a per-pose cloud call)
-static SmoothPlan smooth_plan(int64_t tiles, int64_t P, int64_t P_last = 0) {
+// (declared in dpr_smooth.h; P_last: a second, smaller count the same storage must sort -- the last group of a
+// grouped call)
+SmoothPlan smooth_plan(int64_t tiles, int64_t P, int64_t P_last) {
     SmoothPlan pl{};
     if (P <= 0) return pl;
     size_t o = 0;
@@ -1086,6 +1033,13 @@ int smooth_bin_pose(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int6
     hipLaunchKernelGGL(k_smooth_ranges, rgrid, blk, 0, st, (const uint32_t*)sb.keys_out, (uint32_t)P,
                        (uint64_t)(sb.tiles + 1), sb.bits, sb.start);
     stage_mark(st);
+    return DPR_OK;
+}
+
+int smooth_ranges(hipStream_t st, const uint32_t* keys, uint32_t count, uint64_t entries, int bits, uint32_t* start) {
+    hipLaunchKernelGGL(k_smooth_ranges, dim3((unsigned)((entries + kSmBlock - 1) / kSmBlock)), dim3(kSmBlock), 0, st,
+                       keys, count, entries, bits, start);
+    DPR_HIP(hipGetLastError());
     return DPR_OK;
 }
 

@@ -1,0 +1,617 @@
+// The smooth splat of rigid bodies (include/dpr.h, "SMOOTH SPLAT, RIGID BODIES"): RIGID BODIES with the quadratic
+// B-spline weights of SMOOTH SPLAT.  Point p belongs to body[p] in [0, K) and is seen in image b through pose
+// b * K + body[p]; kernels, launches, host checks, the AUTO rule and the C ABI of the family.
+//
+//   DPR_ALGO_ATOMIC forward   k_smooth_bodies_fwd_atomic: k_smooth_fwd_atomic with the pose of wave_bodies /
+//                             load_body_pose (dpr_kernels_bodies.h): scalar loads where a wave's accepted lanes share
+//                             a body, a per-lane gather otherwise
+//   DPR_ALGO_ATOMIC pullback  k_smooth_bodies_bwd: k_bodies_bwd's per-(image, body) reduction around the point term of
+//                             k_smooth_bwd (smooth_point_backward, the same operation order)
+//   DPR_ALGO_TILED forward    the images binned in GROUPS as smooth_clouds_fwd_tiled bins poses: k_smooth_bodies_keys
+//                             (key = b_local * tiles + tile, value = b_local * P + p) -> one stable radix sort ->
+//                             k_smooth_ranges -> k_smooth_bodies_tile, one workgroup per (image, tile), which takes
+//                             p = q - b_local * P, checks body[p] and gathers its pose per lane
+// These are copies of the smooth and the rigid-body kernels, not shared bodies: those kernels keep their registers.
+// A body index outside [0, K) is checked per lane before it addresses a pose, in every kernel.
+#include <hip/hip_runtime.h>
+
+#include "dpr_host.h"
+#include "dpr_kernels_bodies.h"
+#include "dpr_ordered.h"
+#include "dpr_ordered_index.h"
+#include "dpr_smooth.h"
+#include "dpr_smooth_device.h"
+
+namespace dpr {
+
+static_assert(kSmBlock == kBlock, "pose_slices and the P bound of the host checks count blocks of kBlock points");
+
+// ---------------------------------------------------------------- DPR_ALGO_ATOMIC forward
+// One thread per point, the images striding over blockIdx.y.  `out` holds the background.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_bodies_fwd_atomic(
+    GridDesc<NO> gd, int64_t P, int64_t B, int K, T* __restrict__ out, const T* __restrict__ points,
+    const int32_t* __restrict__ body, const T* __restrict__ rot, const T* __restrict__ trans,
+    const T* __restrict__ ow, const T* __restrict__ pw) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    const WaveBodies wb = wave_bodies(body, p, P, K);
+    if (wb.distinct == 0) return;  // (the whole wave: no lane has a point to deposit)
+    T pt[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) pt[j] = T(0);
+    if (wb.ok) load_point<T, NI>(points, p, pt);
+    const T pwi = (wb.ok && pw) ? pw[p] : T(1);
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+        const Pose<T, NI, NO> ps = load_body_pose<T, NI, NO>(rot, trans, ow, b, K, wb);
+        int j0[NO];
+        T u[NO];
+        if (!(wb.ok && smooth_cell<T, NI, NO>(pt, ps, gd, j0, u))) continue;
+        const T w = ps.ow * pwi;  // as k_smooth_fwd_atomic
+        const SmoothAxes<T, NO> ax = smooth_axes<T, NO>(j0, u, gd);
+        T* o = out + b * gd.G;
+#pragma unroll
+        for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+            const bool in2 = NO == 3 ? ax.in[NO - 1][k2] : true;
+            const int off2 = NO == 3 ? ax.off[NO - 1][k2] : 0;
+            const T w2 = NO == 3 ? ax.w[NO - 1][k2] * w : w;
+#pragma unroll
+            for (int k1 = 0; k1 < 3; ++k1) {
+                const T w12 = ax.w[1][k1] * w2;
+#pragma unroll
+                for (int k0 = 0; k0 < 3; ++k0)
+                    if (in2 && ax.in[1][k1] && ax.in[0][k0])
+                        atomic_add<T>(o + (off2 + ax.off[1][k1] + ax.off[0][k0]), ax.w[0][k0] * w12);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- DPR_ALGO_ATOMIC pullback
+// Over the image range [b_lo, b_hi) of blockIdx.y.  Pre-zeroed: ds_drotation, ds_dtranslation (B * K poses),
+// ds_dout_weight.  ds_dpoints / ds_dpoint_weight: plain stores when `accumulate_points` is 0 (one launch covers all
+// images), atomics onto pre-zeroed buffers otherwise.  The per-(image, body) sums are k_bodies_bwd's: a block whose
+// accepted lanes share one body goes wave -> block -> one atomic per value, otherwise every wave walks its bodies.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_bodies_bwd(
+    GridDesc<NO> gd, int64_t P, int64_t B, int K, const T* __restrict__ g, const T* __restrict__ points,
+    const int32_t* __restrict__ body, const T* __restrict__ rot, const T* __restrict__ trans,
+    const T* __restrict__ ow, const T* __restrict__ pw, T* __restrict__ ds_dpoints, T* __restrict__ ds_drotation,
+    T* __restrict__ ds_dtranslation, T* __restrict__ ds_dout_weight, T* __restrict__ ds_dpoint_weight,
+    int poses_per_slice, int accumulate_points) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    constexpr int NR = NO * NI + NO;  // dR | dt: per (image, body)
+    constexpr int NV = NR + 1;        // | d out_weight: per image
+    constexpr int NW = kSmBlock / kWave;
+    __shared__ T red[NW][NV];
+    __shared__ int wave_body[NW];
+
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    const bool live = p < P;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const WaveBodies wb = wave_bodies(body, p, P, K);
+    // the block's body: -1 no accepted lane in the block, -2 more than one body, else the body all of them share
+    if (lane == 0) wave_body[wave] = wb.distinct == 0 ? -1 : (wb.distinct == 1 ? wb.first : -2);
+    __syncthreads();
+    int block_body = -1;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const int v = wave_body[i];
+        if (v == -1) continue;
+        block_body = (block_body == -1 || block_body == v) ? v : -2;
+    }
+    block_body = __builtin_amdgcn_readfirstlane(block_body);
+
+    T pt[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) pt[j] = T(0);
+    if (wb.ok) load_point<T, NI>(points, p, pt);
+    const T pwi = (wb.ok && pw) ? pw[p] : T(1);
+    T acc_pt[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) acc_pt[j] = T(0);
+    T acc_pw = T(0);
+
+    const int64_t b_lo = (int64_t)blockIdx.y * poses_per_slice;
+    const int64_t b_hi = (b_lo + poses_per_slice < B) ? b_lo + poses_per_slice : B;
+    for (int64_t b = b_lo; b < b_hi; ++b) {
+        const Pose<T, NI, NO> ps = load_body_pose<T, NI, NO>(rot, trans, ow, b, K, wb);
+        T vals[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) vals[i] = T(0);
+        int j0[NO];
+        T u[NO];
+        if (wb.ok && smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) {
+            const T* gb = g + b * gd.G;
+            T dcoord[NO], W;
+            smooth_point_backward<T, NO>(j0, u, gd, [&](int off) { return gb[off]; }, dcoord, W);
+            const T opw = ps.ow * pwi;  // from here to acc_pw: k_smooth_bwd's operation order
+            T scaled[NO];
+#pragma unroll
+            for (int n = 0; n < NO; ++n) scaled[n] = (dcoord[n] * opw) * (T(gd.n[n]) / T(2));
+#pragma unroll
+            for (int n = 0; n < NO; ++n) {
+#pragma unroll
+                for (int j = 0; j < NI; ++j) vals[n + j * NO] = scaled[n] * pt[j];
+                vals[NO * NI + n] = scaled[n];
+            }
+            vals[NR] = W * pwi;
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {  // rotation' * scaled
+                T v = ps.R[0 + j * NO] * scaled[0];
+#pragma unroll
+                for (int n = 1; n < NO; ++n) v = v + ps.R[n + j * NO] * scaled[n];
+                acc_pt[j] += v;
+            }
+            acc_pw += W * ps.ow;
+        }
+        // value i of pose q = b * K + body: ds_drotation[q][i], then ds_dtranslation[q][i - NO * NI]
+        auto add_to_pose = [&](int64_t q, int i, T s) {
+            if (i < NO * NI)
+                atomic_add<T>(ds_drotation + q * (NO * NI) + i, s);
+            else
+                atomic_add<T>(ds_dtranslation + q * NO + (i - NO * NI), s);
+        };
+        if (block_body != -2) {
+            // one body in the block: wave -> block -> one atomic per value, d out_weight with them
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const T s = wave_sum<T>(vals[i]);
+                if (lane == 0) red[wave][i] = s;
+            }
+        } else {
+            const T sw = wave_sum<T>(vals[NR]);
+            if (lane == 0) red[wave][NR] = sw;
+            // walk the wave's bodies: lane i ends up with the sum of value i over the lanes of the body
+            uint64_t rest = __builtin_amdgcn_ballot_w64(wb.ok);
+            while (rest) {
+                const int kc = lane_value(wb.k, __ffsll((unsigned long long)rest) - 1);
+                const bool mine = wb.ok && wb.k == kc;
+                T s_lane = T(0);
+#pragma unroll
+                for (int i = 0; i < NR; ++i) {
+                    const T s = wave_sum<T>(mine ? vals[i] : T(0));
+                    if (lane == i) s_lane = s;
+                }
+                if (lane < NR && s_lane != T(0)) add_to_pose(b * K + kc, lane, s_lane);
+                rest &= ~__builtin_amdgcn_ballot_w64(mine);
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < NV && (threadIdx.x == NR || block_body >= 0)) {
+            T s = red[0][threadIdx.x];
+#pragma unroll
+            for (int i = 1; i < NW; ++i) s += red[i][threadIdx.x];
+            if (s != T(0)) {
+                if (threadIdx.x == NR)
+                    atomic_add<T>(ds_dout_weight + b, s);
+                else
+                    add_to_pose(b * K + block_body, threadIdx.x, s);
+            }
+        }
+        __syncthreads();
+    }
+    if (live) {
+        if (accumulate_points) {
+#pragma unroll
+            for (int j = 0; j < NI; ++j) atomic_add<T>(ds_dpoints + p * NI + j, acc_pt[j]);
+            if (ds_dpoint_weight) atomic_add<T>(ds_dpoint_weight + p, acc_pw);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NI; ++j) ds_dpoints[p * NI + j] = acc_pt[j];
+            if (ds_dpoint_weight) ds_dpoint_weight[p] = acc_pw;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- DPR_ALGO_TILED forward
+// The binning of a GROUP of nb images b0 .. b0 + nb - 1 at once (k_smooth_clouds_keys' shape): block blockIdx.x covers
+// points (blockIdx.x % blocks_per_image) * 256 .. of image blockIdx.x / blocks_per_image.  key = b_local * tiles +
+// (tile of the clamped centre cell under pose (b0 + b_local) * K + body[p]); all ones for a rejected point and for a
+// body outside [0, K); value = the flat index b_local * P + p.  Every entry of keys / idx [0, nb * P) is written.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_bodies_keys(
+    GridDesc<NO> gd, SmoothTiles<NO> tl, uint32_t tiles, int64_t P, uint32_t blocks_per_image, int64_t b0, int K,
+    const T* __restrict__ points, const int32_t* __restrict__ body, const T* __restrict__ rot,
+    const T* __restrict__ trans, uint32_t* __restrict__ keys, uint32_t* __restrict__ idx) {
+    const uint32_t bl = blockIdx.x / blocks_per_image;
+    const int64_t p = (int64_t)(blockIdx.x % blocks_per_image) * kSmBlock + threadIdx.x;
+    const WaveBodies wb = wave_bodies(body, p, P, K);  // (all 64 lanes; before the return of the lanes past P)
+    if (p >= P) return;
+    uint32_t key = kSmoothNoKey;
+    if (wb.ok) {
+        T pt[NI];
+        load_point<T, NI>(points, p, pt);
+        const Pose<T, NI, NO> ps = load_body_pose<T, NI, NO>(rot, trans, nullptr, b0 + bl, K, wb);
+        int j0[NO];
+        T u[NO];
+        if (smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) {
+            uint32_t stride = 1;
+            key = bl * tiles;
+#pragma unroll
+            for (int d = 0; d < NO; ++d) {
+                const int c = j0[d] < 0 ? 0 : (j0[d] >= gd.n[d] ? gd.n[d] - 1 : j0[d]);
+                key += (uint32_t)(c / SmoothTileShape<NO>::e[d]) * stride;
+                stride *= (uint32_t)tl.nt[d];
+            }
+        }
+    }
+    const int64_t q = (int64_t)bl * P + p;
+    keys[q] = key;
+    idx[q] = (uint32_t)q;
+}
+
+// Workgroup blockIdx.x = b_local * tiles + tile: k_smooth_tile's body for the (image, tile)'s run of the group's sorted
+// flat indices (`count` of them: nb * P), flushed onto plane b0 + b_local.  idx comes from a workspace whose contents
+// the kernel does not trust: the run is clamped to [0, count) (ord_cell_range), the point index to [0, P) and the
+// body to [0, K) before either addresses anything.  The pose is gathered per lane; out_weight is per image.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_bodies_tile(
+    GridDesc<NO> gd, SmoothTiles<NO> tl, uint32_t tiles, uint32_t count, int64_t P, int64_t b0, int K,
+    T* __restrict__ out, const T* __restrict__ points, const int32_t* __restrict__ body, const T* __restrict__ rot,
+    const T* __restrict__ trans, const T* __restrict__ ow, const T* __restrict__ pw,
+    const uint32_t* __restrict__ start, const uint32_t* __restrict__ idx) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    constexpr int NC = smooth_lds_cells<NO>();
+    __shared__ double cells[NC];
+    uint32_t begin, end;
+    ord_cell_range(start, blockIdx.x, count, begin, end);
+    if (begin >= end) return;  // (uniform: an empty (image, tile) adds nothing)
+    const int64_t bl = (int64_t)(blockIdx.x / tiles);
+    const int64_t b = b0 + bl;
+    int org[NO];  // first cell of the tile
+    {
+        uint32_t t = blockIdx.x % tiles;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            org[d] = (int)(t % (uint32_t)tl.nt[d]) * SmoothTileShape<NO>::e[d];
+            t /= (uint32_t)tl.nt[d];
+        }
+    }
+    for (int i = threadIdx.x; i < NC; i += kSmBlock) cells[i] = 0.0;
+    __syncthreads();
+
+    const T owb = ow ? ow[b] : T(1);
+    for (uint32_t i = begin + threadIdx.x; i < end; i += kSmBlock) {
+        const int64_t p = (int64_t)idx[i] - bl * P;
+        if (p < 0 || p >= P) continue;  // (never for an index k_smooth_bodies_keys wrote into this run)
+        const int kb = body[p];
+        if ((unsigned)kb >= (unsigned)K) continue;  // (its key was all ones: never in a run of the sorted keys)
+        T pt[NI];
+        load_point<T, NI>(points, p, pt);
+        const Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, nullptr, b * K + kb);
+        int j0[NO];
+        T u[NO];
+        if (!smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) continue;
+        const T w = owb * (pw ? pw[p] : T(1));
+        // LDS cell l = (cell - org) + 1 per axis; only cells of the grid that lie on the tile + halo are added
+        T wt[NO][3];
+        int loff[NO][3];
+        bool in[NO][3];
+        int lstride = 1;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            spline_weights<T>(u[d], wt[d]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int c = j0[d] + k - 1, l = c - org[d] + 1;
+                in[d][k] = c >= 0 && c < gd.n[d] && l >= 0 && l < SmoothTileShape<NO>::e[d] + 2;
+                loff[d][k] = in[d][k] ? l * lstride : 0;
+            }
+            lstride *= SmoothTileShape<NO>::e[d] + 2;
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+            const bool in2 = NO == 3 ? in[NO - 1][k2] : true;
+            const int off2 = NO == 3 ? loff[NO - 1][k2] : 0;
+            const T w2 = NO == 3 ? wt[NO - 1][k2] * w : w;
+#pragma unroll
+            for (int k1 = 0; k1 < 3; ++k1) {
+                const T w12 = wt[1][k1] * w2;
+#pragma unroll
+                for (int k0 = 0; k0 < 3; ++k0)
+                    if (in2 && in[1][k1] && in[0][k0])
+                        atomicAdd(&cells[off2 + loff[1][k1] + loff[0][k0]], (double)(wt[0][k0] * w12));
+            }
+        }
+    }
+    __syncthreads();
+
+    // flush: consecutive threads walk axis 0 of the tile + halo, so a wave's atomics cover rows of the plane
+    T* o = out + b * gd.G;
+    for (int i = threadIdx.x; i < NC; i += kSmBlock) {
+        const double v = cells[i];
+        int rest = i, off = 0, stride = 1;
+        bool in_grid = true;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            const int ext = SmoothTileShape<NO>::e[d] + 2;
+            const int c = org[d] + (rest % ext) - 1;
+            rest /= ext;
+            in_grid = in_grid && c >= 0 && c < gd.n[d];
+            off += in_grid ? c * stride : 0;
+            stride *= gd.n[d];
+        }
+        if (in_grid && v != 0.0) atomic_add<T>(o + off, (T)v);
+    }
+}
+
+// ---------------------------------------------------------------- launches
+template <typename T, int NI, int NO>
+static int smooth_bodies_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out,
+                                    const T* points, const int32_t* body, const T* rot, const T* trans, const T* ow,
+                                    const T* pw) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)(B < 65535 ? B : 65535));
+    hipLaunchKernelGGL((k_smooth_bodies_fwd_atomic<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, K, out, points,
+                       body, rot, trans, ow, pw);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+// group after group of `bg` images: keys -> sort -> start table -> tiles, four launches per GROUP; the workspace is
+// smooth_plan of (bg * tiles, bg * P), reused from group to group (the last group may hold fewer images): the layout,
+// the group rule and the byte count of smooth_clouds_fwd_tiled
+template <typename T, int NI, int NO>
+static int smooth_bodies_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K,
+                                   int max_group, T* out, const T* points, const int32_t* body, const T* rot,
+                                   const T* trans, const T* ow, const T* pw, void* ws_, size_t ws_bytes) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const int64_t bg = smooth_clouds_group(NO, grid, P, B, max_group);
+    if (bg == 0) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
+    const int64_t tiles = smooth_tile_count(NO, grid, P);
+    const SmoothPlan pl = smooth_plan(bg * tiles, bg * P, (B % bg) * P);
+    if (!ws_ || ws_bytes < pl.total)
+        return fail(DPR_ERR_WORKSPACE, "smooth bodies DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
+                    ws_ ? ws_bytes : (size_t)0);
+    char* ws = (char*)ws_;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    const SmoothTiles<NO> tl = smooth_tiles<NO>(grid);
+    uint32_t* keys_in = (uint32_t*)(ws + pl.off_keys_in);
+    uint32_t* keys_out = (uint32_t*)(ws + pl.off_keys_out);
+    uint32_t* idx_in = (uint32_t*)(ws + pl.off_idx_in);
+    uint32_t* idx_out = (uint32_t*)(ws + pl.off_idx_out);
+    uint32_t* start = (uint32_t*)(ws + pl.off_start);
+    const int64_t blocks_per_image = (P + kSmBlock - 1) / kSmBlock;
+    const dim3 blk(kSmBlock);
+    for (int64_t b0 = 0; b0 < B; b0 += bg) {
+        const int64_t nb = B - b0 < bg ? B - b0 : bg;
+        const int64_t count = nb * P, entries = nb * tiles + 1;
+        const int bits = ord_key_bits((uint64_t)(nb * tiles));
+        hipLaunchKernelGGL((k_smooth_bodies_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_image)), blk, 0, st, gd,
+                           tl, (uint32_t)tiles, P, (uint32_t)blocks_per_image, b0, K, points, body, rot, trans,
+                           keys_in, idx_in);
+        stage_mark(st);
+        DPR_HIP(radix_sort_pairs_u32(ws + pl.off_temp, pl.temp_bytes, keys_in, keys_out, idx_in, idx_out,
+                                     (size_t)count, 0u, (unsigned)bits, st));
+        stage_mark(st);
+        if (int rc = smooth_ranges(st, keys_out, (uint32_t)count, (uint64_t)entries, bits, start)) return rc;
+        stage_mark(st);
+        hipLaunchKernelGGL((k_smooth_bodies_tile<T, NI, NO>), dim3((unsigned)(nb * tiles)), blk, 0, st, gd, tl,
+                           (uint32_t)tiles, (uint32_t)count, P, b0, K, out, points, body, rot, trans, ow, pw,
+                           (const uint32_t*)start, (const uint32_t*)idx_out);
+        stage_mark(st);
+    }
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+// ---------------------------------------------------------------- host checks
+static int smooth_bodies_max_group(unsigned flags) { return (int)((flags >> 8) & 0xffu); }
+
+// AUTO (dpr_resolve_algo_smooth_bodies), from the shape alone.  The pullback is DPR_ALGO_ATOMIC.  The forward is
+// DPR_ALGO_TILED where the default GROUP of images holds bg * P >= the constant below and the cloud holds at least
+// kSmoothBodiesTiledMinPointsPerTile points per tile of the grid, DPR_ALGO_ATOMIC otherwise: the shape of
+// dpr_resolve_algo_smooth_clouds' rule, because the tiled path pays its four launches per group here too.  K does not
+// enter: TILED / ATOMIC move by less than 10 % from K = 1 to 64 and between a sorted and a shuffled cloud.  From this
+// op's own rows (profiles/smooth_bodies_probe.txt, tests/golden/smooth_bodies_auto.json; fp32, ms TILED / ATOMIC):
+//  - 3-D, 1e5 (the smooth clouds' constant, confirmed): 128^3, 1e4 x 4 images (bg * P = 4e4) 0.130 / 0.130 and
+//    0.128 / 0.114, 3e4 x 4 (1.2e5) 0.155 / 0.214, 1e4 x 16 0.235 / 0.271, 1e6 x 4 0.35 / 4.4.
+//  - 2-D, 1.6e5 (the smooth clouds' 4e5 lost this op's two lowest rows): 128^2, 1e4 x 16 (1.6e5) 0.121 / 0.144 --
+//    1.19x, beyond the 1.15 margin -- 1e4 x 32 0.176 / 0.200, 3e4 x 16 0.192 / 0.266; 512^2, 3e4 x 16 0.203 / 0.269,
+//    1e6 x 16 0.91 / 6.2.  TILED is ahead on every 2-D row measured; nothing was measured below 1.6e5.
+//  - 4 points per tile (confirmed): 256^3 (16 384 tiles), 1e4 x 16 (0.6 per tile) 0.685 / 0.426, 3e4 x 4 (1.8)
+//    0.309 / 0.244, 1e5 x 4 (6.1) 0.424 / 0.534; 128^3, 1e4 x 16 (4.9) 0.235 / 0.271.
+constexpr int64_t kSmoothBodiesTiledMinWork3D = 100000;
+constexpr int64_t kSmoothBodiesTiledMinWork2D = 160000;
+constexpr int64_t kSmoothBodiesTiledMinPointsPerTile = 4;
+static int resolve_algo_smooth_bodies(int algo, int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
+    if (algo != DPR_ALGO_AUTO) return algo;
+    if (op != DPR_OP_RASTER) return DPR_ALGO_ATOMIC;
+    const int64_t bg = smooth_clouds_group(n_out, grid, P, B, 0);
+    if (bg == 0) return DPR_ALGO_ATOMIC;
+    const int64_t min_work = n_out == 3 ? kSmoothBodiesTiledMinWork3D : kSmoothBodiesTiledMinWork2D;
+    const int64_t tiles = smooth_tile_count(n_out, grid, P);
+    return bg * P >= min_work && P / kSmoothBodiesTiledMinPointsPerTile >= tiles ? DPR_ALGO_TILED : DPR_ALGO_ATOMIC;
+}
+
+// Every refusal of the family, shared by the entry points, the workspace query and dpr_resolve_algo_smooth_bodies;
+// *G, the resolved *algo and the workspace bytes *need come back.
+static int check_smooth_bodies(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
+                               int64_t B, int64_t K, int64_t* G, size_t* need) {
+    // (a pair outside the three is refused before the grid is looked at)
+    if (!smooth_dims_supported(n_in, n_out))
+        return fail(DPR_ERR_UNSUPPORTED_DIMS,
+                    "smooth rigid bodies: (n_in, n_out) = (%d, %d); supports (2,2), (3,3), (3,2)", n_in, n_out);
+    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
+    if (op == DPR_OP_RESIDUAL_PULLBACK)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth rigid bodies have no residual pullback");
+    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
+        return fail(DPR_ERR_INVALID_ARG, "smooth bodies: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
+    if (K < 1) return fail(DPR_ERR_INVALID_ARG, "K = %lld: a call needs at least one body", (long long)K);
+    // the kernels compare a body index with K as 32-bit values and count poses b * K + k in 64 bits; the zeroing of
+    // the B * K pose gradients and their offsets stay far inside both with this bound
+    if (K > 0x7fffffffLL || (B > 0 && K > 0x7fffffffLL / B))
+        return fail(DPR_ERR_INVALID_ARG, "B * K = %lld * %lld poses exceed 2^31 - 1", (long long)B, (long long)K);
+    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (flags & 3u)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "smooth rigid bodies keep / reuse no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
+    if (op == DPR_OP_PULLBACK && (flags & 0xff00u))
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "the smooth rigid-body pullback forms no groups of images (DPR_FLAG_MAX_POSE_GROUP)");
+    if (*algo != DPR_ALGO_AUTO && *algo != DPR_ALGO_ATOMIC && *algo != DPR_ALGO_TILED)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "smooth rigid bodies run on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d", *algo);
+    if (*algo == DPR_ALGO_TILED && op != DPR_OP_RASTER)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth rigid-body pullback runs on DPR_ALGO_ATOMIC only");
+    *algo = resolve_algo_smooth_bodies(*algo, op, n_out, grid, P, B);
+    *need = 0;
+    if (*algo == DPR_ALGO_TILED) {
+        *need = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, smooth_bodies_max_group(flags));
+        if (*need == (size_t)-1) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
+    }
+    return DPR_OK;
+}
+
+template <class F> static int with_smooth_dims(int n_in, int n_out, F&& f) {
+    if (n_in == 2 && n_out == 2) return f(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
+    if (n_in == 3 && n_out == 3) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
+    if (n_in == 3 && n_out == 2) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{});
+    return fail(DPR_ERR_UNSUPPORTED_DIMS, "smooth bodies: unsupported (n_in, n_out) = (%d, %d)", n_in, n_out);
+}
+
+template <typename T>
+static int raster_smooth_bodies_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                     int64_t P, int64_t B, int64_t K, T* out, const T* points, const int32_t* body,
+                                     const T* rot, const T* trans, const T* bg, const T* ow, const T* pw, void* ws,
+                                     size_t ws_bytes) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_smooth_bodies(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
+    if (B == 0) return DPR_OK;
+    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
+    if (P > 0 && (!rot || !trans)) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL with P > 0");
+    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
+        return fail(DPR_ERR_WORKSPACE, "smooth rigid bodies (algorithm %d) need %zu workspace bytes, got %zu", algo,
+                    need, ws ? ws_bytes : (size_t)0);
+    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
+    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    fill_background(st, out, G, B, bg);
+    stage_mark(st);
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        const int rc = algo == DPR_ALGO_TILED
+                           ? smooth_bodies_fwd_tiled<T, NI, NO>(st, grid, G, P, B, (int)K,
+                                                                smooth_bodies_max_group(flags), out, points, body, rot,
+                                                                trans, ow, pw, ws, ws_bytes)
+                           : smooth_bodies_fwd_atomic<T, NI, NO>(st, grid, G, P, B, (int)K, out, points, body, rot,
+                                                                 trans, ow, pw);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+template <typename T>
+static int pullback_smooth_bodies_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
+                                       const int64_t* grid, int64_t P, int64_t B, int64_t K, const T* g,
+                                       const T* points, const int32_t* body, const T* rot, const T* trans,
+                                       const T* ow, const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow,
+                                       T* d_pw, void* ws) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_smooth_bodies(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
+    if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
+    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
+        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
+    if (B > 0) {
+        if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
+        if (!d_rot || !d_trans || !d_bg || !d_ow)
+            return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
+        if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+        if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
+        if (P > 0 && (!rot || !trans)) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL with P > 0");
+    }
+    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
+        return rc;
+    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    if (B == 0) {  // no image: the sums over the images are empty
+        if (P > 0) {
+            DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
+            if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)P));
+        }
+        return DPR_OK;
+    }
+    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * K * n_out * n_in)));
+    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * K * n_out)));
+    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
+    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)B));
+    grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
+    stage_mark(st);
+    if (P == 0) return DPR_OK;  // (the pose sums are 0, ds_dbackground is done)
+    int64_t slices = 1;
+    const int poses_per_slice = pose_slices(P, B, &slices);  // (the smooth pullback's: SUMMATION ORDER, note 1)
+    const int accumulate = slices > 1;
+    if (accumulate) {
+        DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
+        if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)P));
+    }
+    const int rc = with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+        dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)slices);
+        hipLaunchKernelGGL((k_smooth_bodies_bwd<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, (int)K, g, points,
+                           body, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice, accumulate);
+        return DPR_OK;
+    });
+    if (rc) return rc;
+    stage_mark(st);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+}  // namespace dpr
+
+extern "C" {
+
+int dpr_resolve_algo_smooth_bodies(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
+                                   int64_t K) {
+    int64_t G = 0;
+    size_t need = 0;
+    int algo = DPR_ALGO_AUTO;
+    if (int rc = dpr::check_smooth_bodies(op, &algo, 0u, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
+    return algo;
+}
+
+#define DPR_DEFINE_SMOOTH_BODIES(SUF, T)                                                                          \
+    size_t dpr_workspace_bytes_smooth_bodies_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,      \
+                                                      const int64_t* grid, int64_t P, int64_t B, int64_t K) {     \
+        int64_t G = 0;                                                                                            \
+        size_t need = 0;                                                                                          \
+        return dpr::check_smooth_bodies(op, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need) ? (size_t)-1     \
+                                                                                                  : need;         \
+    }                                                                                                             \
+    int dpr_raster_smooth_bodies_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,            \
+                                          const int64_t* grid, int64_t P, int64_t B, int64_t K, T* out,           \
+                                          const T* points, const void* body, const T* rotation,                   \
+                                          const T* translation, const T* background, const T* out_weight,         \
+                                          const T* point_weight, void* workspace, size_t workspace_bytes) {       \
+        return dpr::raster_smooth_bodies_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, K, out, points,    \
+                                                 (const int32_t*)body, rotation, translation, background,         \
+                                                 out_weight, point_weight, workspace, workspace_bytes);           \
+    }                                                                                                             \
+    int dpr_raster_pullback_smooth_bodies_ex_##SUF(                                                               \
+        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,   \
+        int64_t K, const T* ds_dout, const T* points, const void* body, const T* rotation, const T* translation,  \
+        const T* out_weight, const T* point_weight, T* ds_dpoints, T* ds_drotation, T* ds_dtranslation,           \
+        T* ds_dbackground, T* ds_dout_weight, T* ds_dpoint_weight, void* workspace, size_t workspace_bytes) {     \
+        (void)workspace_bytes;                                                                                    \
+        return dpr::pullback_smooth_bodies_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, K, ds_dout,      \
+                                                   points, (const int32_t*)body, rotation, translation,           \
+                                                   out_weight, point_weight, ds_dpoints, ds_drotation,            \
+                                                   ds_dtranslation, ds_dbackground, ds_dout_weight,               \
+                                                   ds_dpoint_weight, workspace);                                  \
+    }
+DPR_DEFINE_SMOOTH_BODIES(f32, float)
+DPR_DEFINE_SMOOTH_BODIES(f64, double)
+#undef DPR_DEFINE_SMOOTH_BODIES
+
+}  // extern "C"

@@ -39,8 +39,8 @@
  * stream, and what a captured call leaves in the graph is kernel nodes only (the library zeroes with
  * a kernel: the memset node of a captured hipMemsetAsync is not replayed reliably).
  * ONE EXCEPTION, refused and never silent: the paths that radix-sort -- DPR_ALGO_ORDERED's forward
- * (P keys per pose), the smooth families on DPR_ALGO_TILED (P keys per pose; per-pose clouds: P times
- * the poses of a group), dpr_sort_points_* and the Hilbert sort inside 3-D DPR_ALGO_CHUNKED batches
+ * (P keys per pose), the smooth families on DPR_ALGO_TILED (P keys per pose; per-pose clouds and rigid
+ * bodies: P times the poses / images of a group), dpr_sort_points_* and the Hilbert sort inside 3-D DPR_ALGO_CHUNKED batches
  * and 2-D ones of more than 96 poses (P keys) -- use rocPRIM, whose sort of more than 2^20 keys
  * clears its histograms with hipMemsetAsync.  On a stream that is being captured such a call
  * returns DPR_ERR_HIP ("operation not permitted when stream is capturing"; kernels of the call in
@@ -52,7 +52,9 @@
  * library writes only inside [workspace, workspace + workspace_bytes); with a workspace_bytes
  * equal to the query it uses no more.  What a call leaves in the workspace is unspecified, except
  * what a DPR_FLAG_KEEP_BINNING forward leaves for its DPR_FLAG_REUSE_BINNING pullback.
- * tests/test_workspace_contract_gpu.py and tests/test_families_streams_gpu.py hold every family to both.
+ * tests/test_workspace_contract_gpu.py and tests/test_families_streams_gpu.py hold every family to both
+ * (SMOOTH SPLAT, RIGID BODIES, whose grouped layout is named piece by piece in its section:
+ * tests/test_smooth_bodies_contract_gpu.py).
  * Supported (n_in, n_out): 1 <= n_in, n_out <= 4 in any
  * combination -- the reference is generic in both (src/raster.jl:5-13).
  * (2,2), (3,3), (3,2) -- the shapes the reference tests (src/raster.jl:112,
@@ -311,6 +313,23 @@ extern "C" {
  *                        channel), <= 3^N such partials per cell as
  *                        float atomics in T: rounding level, not
  *                        bit-reproducible
+ *
+ *   smooth splat, rigid bodies (dpr_raster_smooth_bodies_ex_* / dpr_raster_pullback_smooth_bodies_ex_*, see SMOOTH SPLAT,
+ *   RIGID BODIES below):
+ *   DPR_ALGO_ATOMIC      global float atomics in T, in arrival      as the smooth splat's, image slices     ds_drotation / ds_dtranslation per (image, body):
+ *                        order: rounding level                       alike (note 1).  One slice (B == 1, or  a block of one body wave -> block -> one float
+ *                                                                    P >= 524 033): one thread adds all      atomic per value; otherwise a masked wave sum
+ *                                                                    images in index order, one plain        per body of the wave, one float atomic per value
+ *                                                                    store: bit-reproducible; K = 1, B = 1:  and body.  ds_dout_weight wave -> block -> one
+ *                                                                    the bits of the smooth splat's ATOMIC   float atomic per block; ds_dbackground as
+ *                                                                    pullback                                everywhere: rounding level
+ *   DPR_ALGO_TILED       as the smooth splat's tiled forward per
+ *   (forward only)       (image, tile), whatever the groups and
+ *                        the order of the bodies: f64 LDS atomics
+ *                        in arrival order, rounded to T once per
+ *                        (tile, cell), <= 3^N such partials per
+ *                        cell as float atomics in T: rounding
+ *                        level, not bit-reproducible
  *
  *   smooth splat, forward mode (dpr_raster_smooth_jvp_ex_*, see SMOOTH SPLAT, FORWARD MODE below), out_dot:
  *   DPR_ALGO_ATOMIC      global float atomics in T onto the background tangent, unordered: rounding level (lanes of
@@ -1319,6 +1338,110 @@ int dpr_raster_pullback_bodies_ex_f64(void *stream, int algo, unsigned flags, in
                                       const double *point_weight, double *ds_dpoints, double *ds_drotation,
                                       double *ds_dtranslation, double *ds_dbackground, double *ds_dout_weight,
                                       double *ds_dpoint_weight, void *workspace, size_t workspace_bytes);
+
+/* ---- SMOOTH SPLAT, RIGID BODIES: the quadratic B-spline splat of K rigid bodies, a pose per (image, body) ---------
+ * RIGID BODIES with the kernel of SMOOTH SPLAT.  Point p belongs to body[p] in [0, K) and is seen in image b through
+ * the pose of its body in that image:
+ *     out[i.., b] = background[b]
+ *                 + out_weight[b] * sum_p point_weight[p] * Bspline_weight(i..; R[b, body[p]] points[p] + t[b, body[p]])
+ * Centre cell j0, the weights on 3^N cells, the acceptance -1 <= coord_d < n_d + 1, the cells outside the grid dropped
+ * one by one and the fp operation order per (point, pose) are those of dpr_raster_smooth_*.  With background 0, plane
+ * b is the sum over k of dpr_raster_smooth_* of the points with body[p] == k under pose (b, k), and every gradient is
+ * the matching piece of dpr_raster_pullback_smooth_* of that subset: ds_dpoints[p] and ds_dpoint_weight[p] sum over the
+ * images, ds_drotation[b, k] and ds_dtranslation[b, k] over the points of body k, ds_dbackground[b] and
+ * ds_dout_weight[b] over all points.  The pullback is the exact derivative (the operator is C1, no cell is held fixed).
+ * Not in the reference.  What a loop of K dpr_raster_smooth_* calls on subsets computes, or SMOOTH SPLAT, PER-POSE CLOUDS
+ * on the B warped copies of the cloud, in one call and with the pose gradients.
+ * Layouts: those of RIGID BODIES (body: P values of int32_t, declared const void *, 4-byte aligned; rotation,
+ * ds_drotation n_out x n_in x K x B with pose (b, k) at index b * K + k; translation, ds_dtranslation n_out x K x B).
+ * Dropped points.  A point whose body index lies outside [0, K) -- negative values included -- deposits nothing and
+ * gets ds_dpoints = ds_dpoint_weight = 0; every kernel checks the index per lane before it addresses a pose.  A body no
+ * accepted point belongs to gets gradients that are exactly 0.  `out` and all six pullback outputs are overwritten.
+ * P = 0 and B = 0 are valid: out = background, the gradients are 0 (ds_dpoints and ds_dpoint_weight too when B = 0),
+ * ds_dbackground the grid sum.  (n_in, n_out): (2,2), (3,3), (3,2).  K >= 1 and B * K <= 2^31 - 1.
+ * op: DPR_OP_RASTER or DPR_OP_PULLBACK.
+ * Flags: DPR_FLAG_NO_POINT_WEIGHT_GRAD keeps its meaning (ds_dpoint_weight may then be NULL); DPR_FLAG_COHERENT_POINTS
+ * is accepted and ignored; DPR_FLAG_MAX_POSE_GROUP(n) is HONOURED by the DPR_ALGO_TILED forward (pass the same flags to
+ * the workspace query), accepted and ignored by the DPR_ALGO_ATOMIC forward and REFUSED by the pullback, which forms no
+ * groups; KEEP / REUSE are refused.
+ * Algorithms (DPR_ALGO_CHUNKED, DPR_ALGO_ORDERED: DPR_ERR_UNSUPPORTED_ALGO).
+ *   DPR_ALGO_ATOMIC  forward: one thread per point, the images over grid.y, 3^N global float atomics per accepted
+ *                    (point, image).  Pullback: one thread per point with the image loop inside, the images sliced as
+ *                    SMOOTH SPLAT slices its poses (SUMMATION ORDER note 1); the 3^N gathers one 3^(N-1) plane at a
+ *                    time.  A wave whose points share one body -- SORT THE CLOUD BY BODY -- reads its pose with scalar
+ *                    loads and reduces its pose sums wave -> block -> one float atomic per value; a wave with several
+ *                    bodies gathers its poses per lane and reduces per body (masked wave sums over the lanes of each
+ *                    body in turn, one atomic per value and body).  With K = 1 and one image ds_dpoints and
+ *                    ds_dpoint_weight are the bits of dpr_raster_pullback_smooth_ex_*(DPR_ALGO_ATOMIC).  Workspace 0.
+ *   DPR_ALGO_TILED   forward only (pullback: DPR_ERR_UNSUPPORTED_ALGO).  The IMAGES are binned in groups of bg as
+ *                    SMOOTH SPLAT, PER-POSE CLOUDS bins its poses: for a group, ONE key pass over its bg * P (point,
+ *                    image) pairs (key = b_local * tiles + the tile of dpr_raster_smooth_ex_*(DPR_ALGO_TILED) under pose
+ *                    (b, body[p]), all ones for a rejected point and for a body outside [0, K); value = the flat index
+ *                    b_local * P + p), ONE stable radix sort, ONE start table of bg * tiles + 1 entries and ONE launch
+ *                    of bg * tiles workgroups.  A workgroup walks the run of its (image, tile), takes p = value -
+ *                    b_local * P, checks p and body[p] against their ranges (it does not trust the workspace),
+ *                    gathers the pose of body[p] per lane, accumulates into the f64 LDS tile + halo of SMOOTH SPLAT and
+ *                    adds every non-zero cell inside the grid with one float atomic per (tile, cell).  In a cloud
+ *                    sorted by body a tile's run is contiguous per body (the sort is stable) and neighbouring lanes
+ *                    gather the same pose.  GROUP SIZE, LIMITS and workspace: those of SMOOTH SPLAT, PER-POSE CLOUDS
+ *                    for (P, B) -- bg the largest number of images <= B with bg * max(P, tiles) <= 2^24, at least 1,
+ *                    at most n under DPR_FLAG_MAX_POSE_GROUP(n); the layout of dpr_raster_smooth_ex_*(DPR_ALGO_TILED)
+ *                    for bg * tiles tiles and bg * P points, reused from group to group, whatever K; 0 for P = 0.
+ *                    Every piece of the layout is written before it is read: keys and values by the key pass (all
+ *                    bg * P entries), their sorted copies and the sort's storage by the sort, the start table by its
+ *                    kernel.
+ * AUTO (dpr_resolve_algo_smooth_bodies), from the shape alone, never from the points or `body`: the pullback
+ * DPR_ALGO_ATOMIC; the forward DPR_ALGO_TILED where the default group holds bg * P >= 100 000 (point, image) pairs for a
+ * 3-D grid and >= 160 000 for a 2-D grid, the cloud holds at least 4 points per tile of the grid (P >= 4 * tiles) and
+ * the LIMITS hold; DPR_ALGO_ATOMIC otherwise.  K does not enter (the two forwards move by less than 10 % from K = 1 to
+ * 64).  It is the rule of dpr_resolve_algo_smooth_clouds with this op's own times behind the constants
+ * (profiles/smooth_bodies_probe.txt, tests/golden/smooth_bodies_auto.json; fp32, uniform clouds, 46 rows): they confirm
+ * 100 000 (128^3: 1e4 points x 4 images a tie, 3e4 x 4 1.4x faster TILED) and the 4 points per tile (256^3: 1.8 per tile
+ * 1.27x faster ATOMIC, 6.1 per tile 1.26x faster TILED) and move the 2-D constant from 400 000: DPR_ALGO_TILED is ahead
+ * on every 2-D row measured, by 1.19x at the lowest (1e4 x 16 -> 128^2, bg * P = 160 000).  Below 160 000 on 2-D grids
+ * and between 1.8 and 4.9 points per tile nothing was measured.  AUTO is within 1.15x of the faster forward on every row.
+ * Summation order: the table in SUMMATION ORDER.
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): a pair outside the three
+ * DPR_ERR_UNSUPPORTED_DIMS (the grid is not looked at first); a bad op, negative P / B, a bad grid, K < 1, B * K beyond
+ * 2^31 - 1, a NULL out, points, body, rotation or translation while P * B > 0 (a NULL out or pullback output while
+ * B > 0), a misaligned data pointer DPR_ERR_INVALID_ARG; DPR_OP_RESIDUAL_PULLBACK, KEEP / REUSE,
+ * DPR_FLAG_MAX_POSE_GROUP on the pullback, DPR_ALGO_CHUNKED / DPR_ALGO_ORDERED / an unknown algorithm, a DPR_ALGO_TILED
+ * pullback and a DPR_ALGO_TILED forward outside the LIMITS DPR_ERR_UNSUPPORTED_ALGO; a workspace smaller than
+ * dpr_workspace_bytes_smooth_bodies_ex_* or not 256-byte aligned DPR_ERR_WORKSPACE.  Every refusal comes from one
+ * check that the entry points, the query and the resolver share: dpr_workspace_bytes_smooth_bodies_ex_* returns
+ * (size_t)-1 for every refused combination, dpr_resolve_algo_smooth_bodies a negative status. */
+int dpr_resolve_algo_smooth_bodies(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B,
+                                   int64_t K);
+size_t dpr_workspace_bytes_smooth_bodies_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                const int64_t *grid, int64_t P, int64_t B, int64_t K);
+size_t dpr_workspace_bytes_smooth_bodies_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                const int64_t *grid, int64_t P, int64_t B, int64_t K);
+int dpr_raster_smooth_bodies_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                    const int64_t *grid, int64_t P, int64_t B, int64_t K, float *out,
+                                    const float *points, const void *body, const float *rotation,
+                                    const float *translation, const float *background, const float *out_weight,
+                                    const float *point_weight, void *workspace, size_t workspace_bytes);
+int dpr_raster_smooth_bodies_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                    const int64_t *grid, int64_t P, int64_t B, int64_t K, double *out,
+                                    const double *points, const void *body, const double *rotation,
+                                    const double *translation, const double *background, const double *out_weight,
+                                    const double *point_weight, void *workspace, size_t workspace_bytes);
+int dpr_raster_pullback_smooth_bodies_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t *grid, int64_t P, int64_t B, int64_t K,
+                                             const float *ds_dout, const float *points, const void *body,
+                                             const float *rotation, const float *translation,
+                                             const float *out_weight, const float *point_weight, float *ds_dpoints,
+                                             float *ds_drotation, float *ds_dtranslation, float *ds_dbackground,
+                                             float *ds_dout_weight, float *ds_dpoint_weight, void *workspace,
+                                             size_t workspace_bytes);
+int dpr_raster_pullback_smooth_bodies_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t *grid, int64_t P, int64_t B, int64_t K,
+                                             const double *ds_dout, const double *points, const void *body,
+                                             const double *rotation, const double *translation,
+                                             const double *out_weight, const double *point_weight,
+                                             double *ds_dpoints, double *ds_drotation, double *ds_dtranslation,
+                                             double *ds_dbackground, double *ds_dout_weight,
+                                             double *ds_dpoint_weight, void *workspace, size_t workspace_bytes);
 
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
