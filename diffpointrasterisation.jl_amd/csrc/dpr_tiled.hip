@@ -20,7 +20,8 @@
 //                           assembled from their slabs
 //   pullback k_tile_gather  ds_dout tile (+halo) staged in LDS, per-point gathers from LDS, the
 //                           gradient overwrites the record in place; per-item partial sums
-//            k_unpermute    gradient records back to the original point order
+//            k_unpermute    gradient records back to the original point order (k_unpermute_runs: one
+//                           pose behind k_scatter_wc_runs, whole record runs through the sorted map)
 //            k_pose_reduce  per-item partials (f64) -> ds_drotation, ds_dtranslation, ...
 //
 // Why f64 accumulators for fp32 data: on gfx950 ds_add_f32 retires ~1 lane per 3 cycles
@@ -727,15 +728,20 @@ __global__ __launch_bounds__(kBinThreads) void k_scatter(
 // one 64-lane store instruction then covers a few contiguous runs instead of 64 unrelated
 // 16-byte pieces (measured: 10 M scattered 16-byte stores cost ~75 us more than coalesced
 // ones, profiles/r01_experiments.md).
-//   LDS: cursor[NT * nb] (dynamic) | lhist[NT] (dynamic) | recs[S] | dest[S]
-template <typename T, int NI, int NO, bool HAS_PW, int S, bool GROUP, bool W3>
-__global__ __launch_bounds__(kWcThreads) void k_scatter_wc(
-    GridDesc<NO> gd, TileGeom<NO> tg, int64_t P, int64_t chunk, const T* __restrict__ points,
+//   LDS: cursor[NT * nb] (dynamic) | lhist[NT] (dynamic) | recs[S] | dest[S] | lpos[S] (RUNS)
+// RUNS (single pose, 4-word records; Plan::run_map): the map for the pullback's un-permute is written in
+// SORTED order -- per sub-chunk, slot_of[base + i] = dest[i] and run_lp[base + i] = the index inside the
+// sub-chunk of the point at sorted position i, kRunEnd in slot_of from position n_valid on -- so that
+// k_unpermute_runs reads the gradient records run by run, as this kernel wrote the point records.
+// (The body of the two kernels that follow it: k_scatter_wc, and k_scatter_wc_runs for RUNS.)
+template <typename T, int NI, int NO, bool HAS_PW, int S, bool GROUP, bool W3, bool RUNS>
+__device__ __forceinline__ void scatter_wc_body(
+    const GridDesc<NO>& gd, const TileGeom<NO>& tg, int64_t P, int64_t chunk, const T* __restrict__ points,
     const T* __restrict__ pw, const T* __restrict__ rot, const T* __restrict__ trans, int64_t b0,
     int nb, const uint32_t* __restrict__ prefix, const uint32_t* __restrict__ tile_start,
-    RecT<T, W3>* __restrict__ rec, uint32_t* __restrict__ slot_of, T* __restrict__ ds_dpoints,
-    T* __restrict__ ds_dpw, int zero_dropped, uint32_t* __restrict__ maxpw, int fused_scan,
-    TileScanArgs ts) {
+    RecT<T, W3>* __restrict__ rec, uint32_t* __restrict__ slot_of, uint16_t* __restrict__ run_lp,
+    T* __restrict__ ds_dpoints, T* __restrict__ ds_dpw, int zero_dropped, uint32_t* __restrict__ maxpw,
+    int fused_scan, const TileScanArgs& ts) {
     // fused_scan: the tile scan (tile offsets for later kernels, work list, binning header) runs
     // as ONE EXTRA workgroup of this launch instead of a launch of its own between the column scan
     // and the scatter -- nothing in the scatter depends on its results: every scatter workgroup
@@ -749,6 +755,7 @@ __global__ __launch_bounds__(kWcThreads) void k_scatter_wc(
         return;
     }
     static_assert(!(W3 && HAS_PW), "compact records carry no point weight");
+    static_assert(!RUNS || (!GROUP && !W3 && S <= 65536), "the sorted map: one pose, 4-word records, uint16 owners");
     constexpr int PPT = S / kWcThreads;  // points per thread per sub-chunk
     uint32_t wkey = 0;  // max / min |point_weight| of the binned points (wrange_*: k_tile_splat's fixed point)
     // Pose group (nb > 1): the S points of a sub-chunk stay in registers while the poses of the
@@ -762,6 +769,7 @@ __global__ __launch_bounds__(kWcThreads) void k_scatter_wc(
     uint32_t* lhist = dyn + NTe;   // [NT]
     __shared__ RecT<T, W3> recs[S];
     __shared__ uint32_t dest[S];
+    __shared__ uint16_t lpos[RUNS ? S : 1];  // owner (index inside the sub-chunk) of every sorted position
     // the scan's per-wave sums live in dest[]: they are dead before phase c writes it (two barriers
     // in between), and dest[] is dead after the write-out of the previous round (barrier)
     uint32_t* const wsum = dest;
@@ -911,9 +919,10 @@ __global__ __launch_bounds__(kWcThreads) void k_scatter_wc(
                     if constexpr (!W3) r.v[3] = HAS_PW ? w[k] : idx_to_slot((uint32_t)base + lp, T(0));
                     recs[sidx] = r;
                     dest[sidx] = d;
-                    if (slot_b) __builtin_nontemporal_store(d, &slot_b[lp]);
+                    if constexpr (RUNS) lpos[sidx] = (uint16_t)lp;
+                    else if (slot_b) __builtin_nontemporal_store(d, &slot_b[lp]);
                 } else if (lp < nloc) {
-                    if (slot_b) __builtin_nontemporal_store(Pe, &slot_b[lp]);  // spare slot
+                    if (!RUNS && slot_b) __builtin_nontemporal_store(Pe, &slot_b[lp]);  // spare slot
                     if (zero_dropped) {
                         T* const dp_b = ds_dpoints + base * NI;
 #pragma unroll
@@ -924,7 +933,21 @@ __global__ __launch_bounds__(kWcThreads) void k_scatter_wc(
             }
             lds_barrier();
             // d. write-out in LDS (= tile) order; e. advance cursors, clear the histogram
-            for (uint32_t i = threadIdx.x; i < n_valid; i += kWcThreads) rec[dest[i]] = recs[i];
+            if constexpr (RUNS) {
+                // ... and the sorted map of the sub-chunk, both halves coalesced
+                uint16_t* const lp_b = run_lp + base;
+                for (uint32_t i = threadIdx.x; i < nloc; i += kWcThreads) {
+                    const bool owned = i < n_valid;
+                    const uint32_t d = dest[i];
+                    if (owned) {
+                        rec[d] = recs[i];
+                        __builtin_nontemporal_store(lpos[i], &lp_b[i]);
+                    }
+                    __builtin_nontemporal_store(owned ? d : kRunEnd, &slot_b[i]);
+                }
+            } else {
+                for (uint32_t i = threadIdx.x; i < n_valid; i += kWcThreads) rec[dest[i]] = recs[i];
+            }
             // advance the cursors by the owned bins' counts (kept in registers since the scan)
             // and clear the histogram; the next round's atomics start after the barrier
 #pragma unroll
@@ -939,6 +962,30 @@ __global__ __launch_bounds__(kWcThreads) void k_scatter_wc(
         }
     }
     if (HAS_PW) publish_max_abs(maxpw, wkey);
+}
+template <typename T, int NI, int NO, bool HAS_PW, int S, bool GROUP, bool W3>
+__global__ __launch_bounds__(kWcThreads) void k_scatter_wc(
+    GridDesc<NO> gd, TileGeom<NO> tg, int64_t P, int64_t chunk, const T* __restrict__ points,
+    const T* __restrict__ pw, const T* __restrict__ rot, const T* __restrict__ trans, int64_t b0,
+    int nb, const uint32_t* __restrict__ prefix, const uint32_t* __restrict__ tile_start,
+    RecT<T, W3>* __restrict__ rec, uint32_t* __restrict__ slot_of, T* __restrict__ ds_dpoints,
+    T* __restrict__ ds_dpw, int zero_dropped, uint32_t* __restrict__ maxpw, int fused_scan,
+    TileScanArgs ts) {
+    scatter_wc_body<T, NI, NO, HAS_PW, S, GROUP, W3, false>(gd, tg, P, chunk, points, pw, rot, trans, b0, nb, prefix,
+                                                            tile_start, rec, slot_of, nullptr, ds_dpoints, ds_dpw,
+                                                            zero_dropped, maxpw, fused_scan, ts);
+}
+// single pose, 4-word records, the map in sorted order: run_slot (the slot_of region) | run_lp (the indices region)
+template <typename T, int NI, int NO, bool HAS_PW, int S>
+__global__ __launch_bounds__(kWcThreads) void k_scatter_wc_runs(
+    GridDesc<NO> gd, TileGeom<NO> tg, int64_t P, int64_t chunk, const T* __restrict__ points,
+    const T* __restrict__ pw, const T* __restrict__ rot, const T* __restrict__ trans, int64_t b0,
+    const uint32_t* __restrict__ prefix, const uint32_t* __restrict__ tile_start, Rec4<T>* __restrict__ rec,
+    uint32_t* __restrict__ run_slot, uint16_t* __restrict__ run_lp, uint32_t* __restrict__ maxpw, int fused_scan,
+    TileScanArgs ts) {
+    scatter_wc_body<T, NI, NO, HAS_PW, S, false, false, true>(gd, tg, P, chunk, points, pw, rot, trans, b0, 1, prefix,
+                                                              tile_start, rec, run_slot, run_lp, nullptr, nullptr, 0,
+                                                              maxpw, fused_scan, ts);
 }
 
 // ------------------------------------------------------------------ local binning: K1
@@ -2999,6 +3046,93 @@ __global__ __launch_bounds__(1024) void k_unpermute(int64_t P, int nb,
     }
 }
 
+// ------------------------------------------------------------------ pullback un-permute, run order
+// The single-pose un-permute over the SORTED map k_scatter_wc_runs left (Plan::run_map): a block per
+// scatter sub-chunk of S points, lane i takes sorted position i -- its slot, the gradient record there,
+// and the index inside the sub-chunk of the point that owns it.  Neighbouring lanes sit in the same
+// record run and share its cache lines (a thread per ORIGINAL point asks for a line of its own: ~16
+// distinct lines per 16 lanes against ~8 in run order at C3).  The records are put in original order in
+// an LDS stage (zero-filled first: a rejected point owns no position and leaves with an empty gradient,
+// which is what the spare slot holds for k_unpermute), then ds_dpoints / ds_dpoint_weight of the
+// sub-chunk leave as dense stores.  Same values, same additions as k_unpermute: a pure permutation.
+//   LDS: stage[S] records = 64 KB (two workgroups per CU)
+template <typename T, int NI, bool FIRST_POSE>
+__global__ __launch_bounds__(1024, 8) void k_unpermute_runs(int64_t P, const Rec4<T>* __restrict__ grad,
+                                                            const uint32_t* __restrict__ run_slot,
+                                                            const uint16_t* __restrict__ run_lp,
+                                                            T* __restrict__ ds_dpoints, T* __restrict__ ds_dpw,
+                                                            const BinHeader* __restrict__ hdr,
+                                                            int reduce_blocks, PoseReduceArgs<T> pr) {
+    constexpr int S = sizeof(T) == 4 ? kWcPpt * kWcThreads : kWcPpt * kWcThreads / 2;  // the scatter's sub-chunk
+    constexpr int PPT = S / 1024;
+    __shared__ Rec4<T> stage[S];
+    // the first `reduce_blocks` blocks are the per-pose reduction
+    if ((int)blockIdx.x < reduce_blocks) {
+        pose_reduce_body<T>((int)blockIdx.x, 0u, false, pr);
+        return;
+    }
+    const unsigned ublock = blockIdx.x - (unsigned)reduce_blocks;
+    const unsigned ublocks = gridDim.x - (unsigned)reduce_blocks;
+    if (hdr && hdr->verdict != 1u) {
+        // REUSE_BINNING without a matching KEEP_BINNING forward: no gradient was computed
+        const T nan = T(__builtin_nanf(""));
+        const int64_t b0 = (int64_t)ublock * S + threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {
+            const int64_t p = b0 + k * 1024;
+            if (p >= P) continue;
+#pragma unroll
+            for (int j = 0; j < NI; ++j) ds_dpoints[p * NI + j] = nan;
+            if (ds_dpw) ds_dpw[p] = nan;
+        }
+        return;
+    }
+    const int64_t base = (int64_t)xcd_slice(ublock, ublocks) * S;
+    const uint32_t nloc = (uint32_t)((P - base < S) ? P - base : S);  // points of this sub-chunk (>= 1)
+    uint32_t slot[PPT], lp[PPT];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const uint32_t i = threadIdx.x + (uint32_t)k * 1024;
+        const uint32_t ic = i < nloc ? i : nloc - 1;
+        slot[k] = __builtin_nontemporal_load(&run_slot[base + ic]);
+        lp[k] = __builtin_nontemporal_load(&run_lp[base + ic]);
+        if (i >= nloc) slot[k] = kRunEnd;
+    }
+    Rec4<T> zero;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) zero.v[c] = T(0);
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) stage[threadIdx.x + k * 1024] = zero;
+    // (a slot is a record of this pose: below P; kRunEnd and anything a foreign map holds is no record)
+    Rec4<T> g[PPT];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        g[k] = zero;
+        if (slot[k] < (uint64_t)P) g[k] = grad[slot[k]];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < PPT; ++k)
+        if (slot[k] < (uint64_t)P) stage[lp[k] & (uint32_t)(S - 1)] = g[k];
+    __syncthreads();
+    // original order: point base + q is stage[q]; component j of it is word 4 q + j of the stage
+    const T* const words = &stage[0].v[0];
+    T* const dp = ds_dpoints + base * NI;
+    for (uint32_t e = threadIdx.x; e < nloc * NI; e += 1024) {
+        const T v = words[(e / NI) * 4 + e % NI];
+        if (FIRST_POSE) __builtin_nontemporal_store(v, &dp[e]);
+        else dp[e] += v;
+    }
+    if (ds_dpw) {
+        T* const dw = ds_dpw + base;
+        for (uint32_t q = threadIdx.x; q < nloc; q += 1024) {
+            const T v = stage[q].v[3];
+            if (FIRST_POSE) __builtin_nontemporal_store(v, &dw[q]);
+            else dw[q] += v;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ pullback K5
 // (pose groups and batches un-permuted in one pass: the reduction as a launch of its own)
 template <typename T>
@@ -3169,6 +3303,11 @@ static int launch_scatter(hipStream_t st, const GridDesc<NO>& gd, const TileGeom
             }
         }
         if (nb > 1) DPR_LAUNCH_WC(true, false);
+        else if (WANT_IDX && pl.run_map)  // the map of the pullback's un-permute in sorted order
+            hipLaunchKernelGGL((k_scatter_wc_runs<T, NI, NO, HAS_PW, S>), dim3(pl.nblk + (fused ? 1 : 0)),
+                               dim3(kWcThreads), lds2, st, gd, tg, P, pl.chunk, points, pw, rot, trans, b, w.counts(),
+                               w.tile_start(), w.rec<Rec4<T>>(), w.slot(), (uint16_t*)w.idx(), w.weight_keys(),
+                               fused ? 1 : 0, ts);
         else DPR_LAUNCH_WC(false, false);
 #undef DPR_LAUNCH_WC
         return DPR_OK;
@@ -3509,7 +3648,8 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
         if (reuse || (pl.local && !walk.opens_local_batch(b))) {
             // REUSE: the binning of the preceding raster call (same points / pose / grid) is in the
             // workspace (points without an in-range voxel are in no tile: the un-permute reads
-            // zeros from the spare slot for them).  A later pose of a local batch: binned with the
+            // zeros from the spare slot for them, or, in run order, finds no sorted position of
+            // theirs).  A later pose of a local batch: binned with the
             // first.  The three binning stages are marked, empty.
             stage_mark(st);
             stage_mark(st);
@@ -3555,6 +3695,14 @@ int pullback_tiled(hipStream_t st, unsigned flags, const int64_t* grid, int64_t 
             } else if (nb > 1) {
                 if (first_acc) DPR_LAUNCH_UNPERM(true, 1, 0);
                 else DPR_LAUNCH_UNPERM(false, 1, 0);
+            } else if (pl.run_map) {
+                // one pose, the map in sorted order (written by k_scatter_wc_runs, in this call or by the
+                // KEEP forward): a block per scatter sub-chunk; the per-pose reduction rides along
+                auto unpermute_runs = first_acc ? k_unpermute_runs<T, NI, true> : k_unpermute_runs<T, NI, false>;
+                hipLaunchKernelGGL(unpermute_runs, dim3((unsigned)((P + pl.sub - 1) / pl.sub) + n_reduce), dim3(1024),
+                                   0, st, P, w.rec<const Rec4<T>>(), (const uint32_t*)w.slot(),
+                                   (const uint16_t*)w.idx(), d_pts, d_pw, (const BinHeader*)hdr, (int)n_reduce, pr);
+                reduced = true;
             } else {
                 // one pose: the per-pose reduction rides in the same launch
                 if (first_acc) DPR_LAUNCH_UNPERM(true, kUpb, n_reduce);

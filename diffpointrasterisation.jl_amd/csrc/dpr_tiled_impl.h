@@ -132,6 +132,18 @@ constexpr int kMaxRunsGather = 64;   // ... and in k_tile_gather (their tables l
 // Workspace layout (identical for raster and pullback so that a pullback can reuse the
 // binning a raster call left behind, DPR_FLAG_KEEP_BINNING / DPR_FLAG_REUSE_BINNING):
 //   counts table | totals | tile_start | work items, n_items, tile_parts, tile_slab | records | indices | slot_of | aux (halo / partials)
+// What a pullback's un-permute finds in `indices` and `slot_of` (the sizes of the two regions never change):
+//   slot_of[p]   = record slot of ORIGINAL point p, the spare slot for a rejected one; `indices` holds the
+//                  point index of every record for the plain k_scatter with point weights, else nothing
+//   run_map      (Plan::run_map: one pose at a time through the write-combining scatter) the map is kept in
+//                  SORTED order instead, per scatter sub-chunk of `sub` points starting at point g * sub:
+//                    slot_of region, uint32 [g * sub + i] = record slot of sorted position i of the
+//                                                           sub-chunk, kRunEnd from the first position no
+//                                                           record owns (rejected points own none)
+//                    indices region, uint16 [g * sub + i] = index inside the sub-chunk (< sub) of the point
+//                                                           that owns sorted position i
+//                  2 + 4 bytes per point: the uint16 half fills at most half of `indices`.
+constexpr uint32_t kRunEnd = 0xffffffffu;  // (no record slot: slots are < P < 2^32)
 struct Plan {
     int bg;          // poses binned together (pose group, a power of two; 1 = per-pose pipeline)
     int nblk;
@@ -139,6 +151,7 @@ struct Plan {
     uint32_t cap;    // records per work item above which a tile is split
     int max_items;   // NT + worst-case number of extra parts
     int max_slabs;   // overflow slabs (parts of split tiles)
+    bool run_map;    // the pullback's map is kept in sorted order (see the layout above); part of plan_layout_id
     size_t off_hdr, off_counts, off_totals, off_tile_start, off_items, off_nitems, off_nzbins, off_tparts, off_tslab,
         off_split, off_rec, off_idx, off_slot, off_aux, total;
     // Cell sort of the cloud inside the call (dpr_coarse.h; batched poses on grids with more than

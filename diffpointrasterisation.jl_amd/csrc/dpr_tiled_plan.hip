@@ -194,6 +194,10 @@ Plan make_plan(const PlanRequest& rq) {
     pl.off_tslab = take((size_t)NT * 4);
     pl.off_split = take((size_t)(pl.max_slabs / 2 + 2) * 4);  // [0] = n_split, [1..] = split tile ids (at most max_slabs / 2)
     pl.sub = elem == 4 ? 4096 : 2048;
+    // The un-permute map in sorted order (dpr_tiled_impl.h, the layout): wherever one pose at a time goes
+    // through the write-combining scatter and its gradient records are read once per point -- no pose
+    // group, no local binning, no kept batch (whose poses are un-permuted together through slot_of[p]).
+    pl.run_map = pl.bg == 1 && !pl.local && NT1 <= 4096 && pl.copies == 1;
     pl.nsub = (P1 + pl.sub - 1) / pl.sub;
     if (pl.nsub < 1) pl.nsub = 1;
     pl.max_desc = 0;
@@ -262,6 +266,7 @@ uint32_t plan_layout_id(const Plan& pl) {
     mix(pl.pose_stride);
     mix(pl.off_iperm);
     mix((uint64_t)pl.lb);
+    mix(pl.run_map ? 1 : 0);
     const uint32_t id = (uint32_t)(h ^ (h >> 32));
     return id ? id : 1u;
 }
