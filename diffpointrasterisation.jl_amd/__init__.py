@@ -32,6 +32,8 @@ from .smooth_channels import (raster_pullback_smooth_channels_, raster_smooth_ch
 from .bodies import (raster_bodies, raster_bodies_, raster_bodies_ad, raster_pullback_bodies_, resolve_algo_bodies)
 from .smooth_bodies import (raster_pullback_smooth_bodies_, raster_smooth_bodies, raster_smooth_bodies_,
                             raster_smooth_bodies_ad, resolve_algo_smooth_bodies)
+from .smooth_bodies_jvp import (raster_smooth_bodies_jvp, raster_smooth_bodies_jvp_,
+                                resolve_algo_smooth_bodies_jvp)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -60,4 +62,5 @@ __all__ = [
     "raster_bodies", "raster_bodies_", "raster_pullback_bodies_", "raster_bodies_ad", "resolve_algo_bodies",
     "raster_smooth_bodies", "raster_smooth_bodies_", "raster_pullback_smooth_bodies_", "raster_smooth_bodies_ad",
     "resolve_algo_smooth_bodies",
+    "raster_smooth_bodies_jvp", "raster_smooth_bodies_jvp_", "resolve_algo_smooth_bodies_jvp",
 ]

@@ -85,6 +85,9 @@ EXPORTS = [
     "dpr_resolve_algo_smooth_bodies", "dpr_workspace_bytes_smooth_bodies_ex_f32",
     "dpr_workspace_bytes_smooth_bodies_ex_f64", "dpr_raster_smooth_bodies_ex_f32", "dpr_raster_smooth_bodies_ex_f64",
     "dpr_raster_pullback_smooth_bodies_ex_f32", "dpr_raster_pullback_smooth_bodies_ex_f64",
+    "dpr_resolve_algo_smooth_bodies_jvp", "dpr_workspace_bytes_smooth_bodies_jvp_ex_f32",
+    "dpr_workspace_bytes_smooth_bodies_jvp_ex_f64", "dpr_raster_smooth_bodies_jvp_ex_f32",
+    "dpr_raster_smooth_bodies_jvp_ex_f64",
 ]
 
 _lib = None
@@ -311,6 +314,17 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, f"dpr_raster_pullback_smooth_bodies_ex_{suf}")
         f.restype = i
         f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 13 + [vp, sz]
+    L.dpr_resolve_algo_smooth_bodies_jvp.restype = i
+    L.dpr_resolve_algo_smooth_bodies_jvp.argtypes = [i, i, vp, i64, i64, i64, i64]
+    for suf in ("f32", "f64"):
+        f = getattr(L, f"dpr_workspace_bytes_smooth_bodies_jvp_ex_{suf}")
+        f.restype = sz
+        f.argtypes = [i, ctypes.c_uint, i, i, vp, i64, i64, i64, i64]
+        # stream, algo, flags, n_in, n_out, grid, P, B, K, V, out_dot, points, body, rot, trans, ow, pw,
+        # points_dot, rot_dot, trans_dot, bg_dot, ow_dot, pw_dot, ws, ws_bytes
+        f = getattr(L, f"dpr_raster_smooth_bodies_jvp_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64, i64] + [vp] * 13 + [vp, sz]
     L.dpr_comm_unique_id.restype = i
     L.dpr_comm_unique_id.argtypes = [vp, sz]
     L.dpr_comm_init.restype = i

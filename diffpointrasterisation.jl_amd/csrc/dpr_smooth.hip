@@ -455,28 +455,10 @@ __global__ __launch_bounds__(kSmBlock) void k_smooth_tile(GridDesc<NO> gd, Smoot
 //   deposit(s) = a * prod_d e_d + sum_n f_n * prod_{d != n} e_d = e_0 * X + f_0 * Y
 //   2-D: X = a * e_1 + f_1,                  Y = e_1
 //   3-D: X = e_1 * (a * e_2 + f_2) + f_1 * e_2,  Y = e_1 * e_2
-// X and Y are formed once per (k1, k2).  out_dot holds the background tangent already (k_jvp_fill); plane (b, k) is
-// at (b * K + k) * G.  These kernels are copies of k_smooth_fwd_atomic / k_smooth_tile, not shared bodies: the
-// forward kernels keep their registers.
-template <typename T, int NO> struct SmoothJvpRows {
-    T X[NO == 3 ? 3 : 1][3], Y[NO == 3 ? 3 : 1][3];
-};
-template <typename T, int NO>
-__device__ __forceinline__ SmoothJvpRows<T, NO> smooth_jvp_rows(T a, const T (&bc)[NO], const T (&w)[NO][3],
-                                                                const T (&dw)[NO][3]) {
-    SmoothJvpRows<T, NO> r;
-#pragma unroll
-    for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
-        const T e2 = NO == 3 ? w[NO - 1][k2] : T(1);
-        const T a2 = NO == 3 ? a * e2 + bc[NO - 1] * dw[NO - 1][k2] : a;  // a * e_2 + f_2
-#pragma unroll
-        for (int k1 = 0; k1 < 3; ++k1) {
-            r.X[k2][k1] = w[1][k1] * a2 + (bc[1] * dw[1][k1]) * e2;
-            r.Y[k2][k1] = w[1][k1] * e2;
-        }
-    }
-    return r;
-}
+// X and Y are formed once per (k1, k2): smooth_jvp_rows (dpr_smooth_device.h, shared with dpr_smooth_bodies.hip).
+// out_dot holds the background tangent already (k_jvp_fill); plane (b, k) is at (b * K + k) * G.  These kernels are
+// copies of k_smooth_fwd_atomic / k_smooth_tile, not shared bodies: the forward kernels keep their registers
+// (DESIGN.md 4.15).
 
 // One thread per point, the poses strided over gridDim.y (k_smooth_fwd_atomic's shape).  The cell, the weights and
 // their derivatives once per accepted (point, pose); the K tangents are a run-time loop of 3^N atomics each.  A

@@ -11,11 +11,15 @@
 //                             (key = b_local * tiles + tile, value = b_local * P + p) -> one stable radix sort ->
 //                             k_smooth_ranges -> k_smooth_bodies_tile, one workgroup per (image, tile), which takes
 //                             p = q - b_local * P, checks body[p] and gathers its pose per lane
+//   forward mode              (include/dpr.h, "SMOOTH SPLAT, RIGID BODIES, FORWARD MODE") jvp_fill, then
+//                             k_smooth_bodies_jvp_atomic, or the binning above once per group of images and
+//                             k_smooth_bodies_tile_jvp, one workgroup per (image, tile, tangent)
 // These are copies of the smooth and the rigid-body kernels, not shared bodies: those kernels keep their registers.
 // A body index outside [0, K) is checked per lane before it addresses a pose, in every kernel.
 #include <hip/hip_runtime.h>
 
 #include "dpr_host.h"
+#include "dpr_jvp.h"
 #include "dpr_kernels_bodies.h"
 #include "dpr_ordered.h"
 #include "dpr_ordered_index.h"
@@ -337,6 +341,196 @@ __global__ __launch_bounds__(kSmBlock) void k_smooth_bodies_tile(
     }
 }
 
+// ---------------------------------------------------------------- forward mode
+// include/dpr.h, "SMOOTH SPLAT, RIGID BODIES, FORWARD MODE": out_dot = J . v for V tangents.  Pose tangent (v, b, k)
+// sits at (v * B + b) * K + k, out_weight_dot and background_dot at v * B + b, plane (b, v) of out_dot at
+// (b * V + v) * G; out_dot holds the background tangent already (jvp_fill).  The per-tangent arithmetic is that of
+// k_smooth_jvp_atomic / k_smooth_tile_jvp: jvp_coeffs (dpr_jvp.h), smooth_jvp_rows (dpr_smooth_device.h).
+
+// The tangent of pose (b, k) of a lane, vb = v * B + b: loaded as load_body_pose loads the primal -- scalar loads
+// where the wave's ok lanes share a body, a per-lane gather otherwise; out_weight_dot is per (tangent, image).
+template <typename T, int NI, int NO>
+__device__ __forceinline__ JvpPose<T, NI, NO> load_body_jvp_pose(const T* __restrict__ rot_dot,
+                                                                const T* __restrict__ trans_dot,
+                                                                const T* __restrict__ ow_dot, int64_t vb, int K,
+                                                                const WaveBodies& w) {
+    JvpPose<T, NI, NO> tp;
+    if (w.distinct <= 1)
+        tp = load_jvp_pose<T, NI, NO>(rot_dot, trans_dot, nullptr, vb * K + __builtin_amdgcn_readfirstlane(w.first));
+    else
+        tp = load_jvp_pose<T, NI, NO>(rot_dot, trans_dot, nullptr, vb * K + w.k);
+    tp.owd = ow_dot ? ow_dot[vb] : T(0);
+    return tp;
+}
+
+// DPR_ALGO_ATOMIC: k_smooth_bodies_fwd_atomic's shape (one thread per point, the images striding over blockIdx.y)
+// around k_smooth_jvp_atomic's run-time loop over the tangents.  The cell, the weights and their derivatives once per
+// accepted (point, image); 3^N atomics per tangent.  A dropped point reads none of its tangents.  There is no
+// equal-cell wave combine here: every lane issues its own atomics.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_bodies_jvp_atomic(
+    GridDesc<NO> gd, int64_t P, int64_t B, int K, int V, T* __restrict__ out_dot, const T* __restrict__ points,
+    const int32_t* __restrict__ body, const T* __restrict__ rot, const T* __restrict__ trans,
+    const T* __restrict__ ow, const T* __restrict__ pw, JvpTangents<T> tan) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    const int64_t p = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    const WaveBodies wb = wave_bodies(body, p, P, K);
+    if (wb.distinct == 0) return;  // (the whole wave: no lane has a point to deposit)
+    T pt[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) pt[j] = T(0);
+    if (wb.ok) load_point<T, NI>(points, p, pt);
+    const T pwi = (wb.ok && pw) ? pw[p] : T(1);
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+        const Pose<T, NI, NO> ps = load_body_pose<T, NI, NO>(rot, trans, ow, b, K, wb);
+        int j0[NO];
+        T u[NO];
+        if (!(wb.ok && smooth_cell<T, NI, NO>(pt, ps, gd, j0, u))) continue;
+        const SmoothAxes<T, NO> ax = smooth_axes<T, NO>(j0, u, gd);
+        T dw[NO][3];
+#pragma unroll
+        for (int d = 0; d < NO; ++d) spline_derivatives<T>(u[d], dw[d]);
+        T* o = out_dot + b * V * gd.G;
+        for (int v = 0; v < V; ++v) {
+            const JvpPose<T, NI, NO> tp =
+                load_body_jvp_pose<T, NI, NO>(tan.rot, tan.trans, tan.ow, (int64_t)v * B + b, K, wb);
+            T pd[NI], pwd;
+            load_jvp_point<T, NI>(tan.points, tan.pw, (int64_t)v * P + p, pd, pwd);
+            T a, bc[NO];
+            jvp_coeffs<T, NI, NO>(pt, pwi, pd, pwd, ps, tp, gd, a, bc);
+            const SmoothJvpRows<T, NO> r = smooth_jvp_rows<T, NO>(a, bc, ax.w, dw);
+            T f0[3];
+#pragma unroll
+            for (int k0 = 0; k0 < 3; ++k0) f0[k0] = bc[0] * dw[0][k0];
+            T* plane = o + (int64_t)v * gd.G;
+#pragma unroll
+            for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+                const bool in2 = NO == 3 ? ax.in[NO - 1][k2] : true;
+                const int off2 = NO == 3 ? ax.off[NO - 1][k2] : 0;
+#pragma unroll
+                for (int k1 = 0; k1 < 3; ++k1) {
+#pragma unroll
+                    for (int k0 = 0; k0 < 3; ++k0)
+                        if (in2 && ax.in[1][k1] && ax.in[0][k0])
+                            atomic_add<T>(plane + (off2 + ax.off[1][k1] + ax.off[0][k0]),
+                                          ax.w[0][k0] * r.X[k2][k1] + f0[k0] * r.Y[k2][k1]);
+                }
+            }
+        }
+    }
+}
+
+// DPR_ALGO_TILED: workgroup (blockIdx.x, blockIdx.y) = (b_local * tiles + tile, v).  k_smooth_bodies_tile's walk over
+// the (image, tile)'s run of the group's sorted flat indices, with its distrust of the workspace (the run clamped to
+// [0, count), the point index to [0, P), the body to [0, K)), its f64 LDS tile + halo and its flush, and the deposit
+// of tangent v in the place of the weight product.  The pose and its tangent are gathered per lane; a and bc are
+// formed before the spline terms, so neither outlives jvp_coeffs.  Deposits have both signs; a cell whose sum is
+// exactly 0 is skipped by the flush, which is right because the plane holds the background tangent already.
+template <typename T, int NI, int NO>
+__global__ __launch_bounds__(kSmBlock) void k_smooth_bodies_tile_jvp(
+    GridDesc<NO> gd, SmoothTiles<NO> tl, uint32_t tiles, uint32_t count, int64_t P, int64_t B, int64_t b0, int K,
+    int V, T* __restrict__ out_dot, const T* __restrict__ points, const int32_t* __restrict__ body,
+    const T* __restrict__ rot, const T* __restrict__ trans, const T* __restrict__ ow, const T* __restrict__ pw,
+    JvpTangents<T> tan, const uint32_t* __restrict__ start, const uint32_t* __restrict__ idx) {
+    static_assert(NO == 2 || NO == 3, "the smooth splat is written for 2-D and 3-D grids");
+    constexpr int NC = smooth_lds_cells<NO>();
+    __shared__ double cells[NC];
+    uint32_t begin, end;
+    ord_cell_range(start, blockIdx.x, count, begin, end);
+    if (begin >= end) return;  // (uniform: an empty (image, tile) adds nothing)
+    const int64_t bl = (int64_t)(blockIdx.x / tiles);
+    const int64_t b = b0 + bl;
+    const int64_t v = blockIdx.y;
+    const int64_t vb = v * B + b;
+    int org[NO];  // first cell of the tile
+    {
+        uint32_t t = blockIdx.x % tiles;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            org[d] = (int)(t % (uint32_t)tl.nt[d]) * SmoothTileShape<NO>::e[d];
+            t /= (uint32_t)tl.nt[d];
+        }
+    }
+    for (int i = threadIdx.x; i < NC; i += kSmBlock) cells[i] = 0.0;
+    __syncthreads();
+
+    const T owb = ow ? ow[b] : T(1);
+    const T owd = tan.ow ? tan.ow[vb] : T(0);
+    for (uint32_t i = begin + threadIdx.x; i < end; i += kSmBlock) {
+        const int64_t p = (int64_t)idx[i] - bl * P;
+        if (p < 0 || p >= P) continue;  // (never for an index k_smooth_bodies_keys wrote into this run)
+        const int kb = body[p];
+        if ((unsigned)kb >= (unsigned)K) continue;  // (its key was all ones: never in a run of the sorted keys)
+        T pt[NI];
+        load_point<T, NI>(points, p, pt);
+        int j0[NO];
+        T u[NO], a, bc[NO];
+        {
+            Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, nullptr, b * K + kb);
+            ps.ow = owb;
+            if (!smooth_cell<T, NI, NO>(pt, ps, gd, j0, u)) continue;
+            JvpPose<T, NI, NO> tp = load_jvp_pose<T, NI, NO>(tan.rot, tan.trans, nullptr, vb * K + kb);
+            tp.owd = owd;
+            T pd[NI], pwd;
+            load_jvp_point<T, NI>(tan.points, tan.pw, v * P + p, pd, pwd);
+            jvp_coeffs<T, NI, NO>(pt, pw ? pw[p] : T(1), pd, pwd, ps, tp, gd, a, bc);
+        }
+        // LDS cell l = (cell - org) + 1 per axis; only cells of the grid that lie on the tile + halo are added
+        T wt[NO][3], dw[NO][3];
+        int loff[NO][3];
+        bool in[NO][3];
+        int lstride = 1;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            spline_weights<T>(u[d], wt[d]);
+            spline_derivatives<T>(u[d], dw[d]);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int c = j0[d] + q - 1, l = c - org[d] + 1;
+                in[d][q] = c >= 0 && c < gd.n[d] && l >= 0 && l < SmoothTileShape<NO>::e[d] + 2;
+                loff[d][q] = in[d][q] ? l * lstride : 0;
+            }
+            lstride *= SmoothTileShape<NO>::e[d] + 2;
+        }
+        const SmoothJvpRows<T, NO> r = smooth_jvp_rows<T, NO>(a, bc, wt, dw);
+        T f0[3];
+#pragma unroll
+        for (int k0 = 0; k0 < 3; ++k0) f0[k0] = bc[0] * dw[0][k0];
+#pragma unroll
+        for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+            const bool in2 = NO == 3 ? in[NO - 1][k2] : true;
+            const int off2 = NO == 3 ? loff[NO - 1][k2] : 0;
+#pragma unroll
+            for (int k1 = 0; k1 < 3; ++k1) {
+#pragma unroll
+                for (int k0 = 0; k0 < 3; ++k0)
+                    if (in2 && in[1][k1] && in[0][k0])
+                        atomicAdd(&cells[off2 + loff[1][k1] + loff[0][k0]],
+                                  (double)(wt[0][k0] * r.X[k2][k1] + f0[k0] * r.Y[k2][k1]));
+            }
+        }
+    }
+    __syncthreads();
+
+    // flush: consecutive threads walk axis 0 of the tile + halo, so a wave's atomics cover rows of the plane
+    T* o = out_dot + (b * V + v) * gd.G;
+    for (int i = threadIdx.x; i < NC; i += kSmBlock) {
+        const double val = cells[i];
+        int rest = i, off = 0, stride = 1;
+        bool in_grid = true;
+#pragma unroll
+        for (int d = 0; d < NO; ++d) {
+            const int ext = SmoothTileShape<NO>::e[d] + 2;
+            const int c = org[d] + (rest % ext) - 1;
+            rest /= ext;
+            in_grid = in_grid && c >= 0 && c < gd.n[d];
+            off += in_grid ? c * stride : 0;
+            stride *= gd.n[d];
+        }
+        if (in_grid && val != 0.0) atomic_add<T>(o + off, (T)val);
+    }
+}
+
 // ---------------------------------------------------------------- launches
 template <typename T, int NI, int NO>
 static int smooth_bodies_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out,
@@ -392,6 +586,66 @@ static int smooth_bodies_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t 
         hipLaunchKernelGGL((k_smooth_bodies_tile<T, NI, NO>), dim3((unsigned)(nb * tiles)), blk, 0, st, gd, tl,
                            (uint32_t)tiles, (uint32_t)count, P, b0, K, out, points, body, rot, trans, ow, pw,
                            (const uint32_t*)start, (const uint32_t*)idx_out);
+        stage_mark(st);
+    }
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+template <typename T, int NI, int NO>
+static int smooth_bodies_jvp_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int V,
+                                    T* out_dot, const T* points, const int32_t* body, const T* rot, const T* trans,
+                                    const T* ow, const T* pw, JvpTangents<T> tan) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)(B < 65535 ? B : 65535));
+    hipLaunchKernelGGL((k_smooth_bodies_jvp_atomic<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, K, V, out_dot,
+                       points, body, rot, trans, ow, pw, tan);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+// smooth_bodies_fwd_tiled's groups, workspace and first three stages -- the keys and the sort depend on the primal
+// only -- then ONE launch of (nb * tiles) x V workgroups: four launches per group, whatever V
+template <typename T, int NI, int NO>
+static int smooth_bodies_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int V,
+                                   int max_group, T* out_dot, const T* points, const int32_t* body, const T* rot,
+                                   const T* trans, const T* ow, const T* pw, JvpTangents<T> tan, void* ws_,
+                                   size_t ws_bytes) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const int64_t bg = smooth_clouds_group(NO, grid, P, B, max_group);
+    if (bg == 0) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
+    const int64_t tiles = smooth_tile_count(NO, grid, P);
+    const SmoothPlan pl = smooth_plan(bg * tiles, bg * P, (B % bg) * P);
+    if (!ws_ || ws_bytes < pl.total)
+        return fail(DPR_ERR_WORKSPACE, "smooth bodies JVP DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
+                    ws_ ? ws_bytes : (size_t)0);
+    char* ws = (char*)ws_;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    const SmoothTiles<NO> tl = smooth_tiles<NO>(grid);
+    uint32_t* keys_in = (uint32_t*)(ws + pl.off_keys_in);
+    uint32_t* keys_out = (uint32_t*)(ws + pl.off_keys_out);
+    uint32_t* idx_in = (uint32_t*)(ws + pl.off_idx_in);
+    uint32_t* idx_out = (uint32_t*)(ws + pl.off_idx_out);
+    uint32_t* start = (uint32_t*)(ws + pl.off_start);
+    const int64_t blocks_per_image = (P + kSmBlock - 1) / kSmBlock;
+    const dim3 blk(kSmBlock);
+    for (int64_t b0 = 0; b0 < B; b0 += bg) {
+        const int64_t nb = B - b0 < bg ? B - b0 : bg;
+        const int64_t count = nb * P, entries = nb * tiles + 1;
+        const int bits = ord_key_bits((uint64_t)(nb * tiles));
+        hipLaunchKernelGGL((k_smooth_bodies_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_image)), blk, 0, st, gd,
+                           tl, (uint32_t)tiles, P, (uint32_t)blocks_per_image, b0, K, points, body, rot, trans,
+                           keys_in, idx_in);
+        stage_mark(st);
+        DPR_HIP(radix_sort_pairs_u32(ws + pl.off_temp, pl.temp_bytes, keys_in, keys_out, idx_in, idx_out,
+                                     (size_t)count, 0u, (unsigned)bits, st));
+        stage_mark(st);
+        if (int rc = smooth_ranges(st, keys_out, (uint32_t)count, (uint64_t)entries, bits, start)) return rc;
+        stage_mark(st);
+        hipLaunchKernelGGL((k_smooth_bodies_tile_jvp<T, NI, NO>), dim3((unsigned)(nb * tiles), (unsigned)V), blk, 0,
+                           st, gd, tl, (uint32_t)tiles, (uint32_t)count, P, B, b0, K, V, out_dot, points, body, rot,
+                           trans, ow, pw, tan, (const uint32_t*)start, (const uint32_t*)idx_out);
         stage_mark(st);
     }
     DPR_HIP(hipGetLastError());
@@ -568,6 +822,106 @@ static int pullback_smooth_bodies_impl(void* stream, int algo, unsigned flags, i
     return DPR_OK;
 }
 
+// ---------------------------------------------------------------- forward mode: host checks and entry point
+// AUTO (dpr_resolve_algo_smooth_bodies_jvp), from the shape and V alone: the forward's rule -- DPR_ALGO_TILED where the
+// default GROUP holds enough work and the cloud at least 4 points per tile -- with the group's work counted as
+// bg * P * V^2.  The rule started as the forward's with bg * P * V (what dpr_resolve_algo_smooth_jvp does with P * K);
+// this op's own rows (profiles/smooth_bodies_jvp_probe.txt, tests/golden/smooth_bodies_jvp_auto.json; fp32, K = 4,
+// ms ATOMIC / TILED) leave no constant for that product: on 128^2 1000 x 4 images at V = 12 (bg * P * V = 4.8e4) is
+// 0.111 / 0.087 -- TILED 1.28x ahead -- and 1e4 x 8 at V = 1 (8e4) 0.095 / 0.122 -- ATOMIC 1.28x ahead; on 64^3 1100 x 2 at
+// V = 12 (2.6e4) 0.205 / 0.122 against 1e4 x 4 at V = 1 (4e4, 128^3) 0.117 / 0.147.  The binning is paid once per group
+// whatever V and costs about what one tangent's atomics cost, so the bg * P from which TILED pays falls faster than
+// 1 / V: at V = 12 TILED is ahead on every row measured with 4 points per tile (down to bg * P = 2200), at V = 1 from about the forward's
+// constants on.  V^2 puts both on one side of one constant each:
+//  - 2-D, 1.6e5 (the forward's, confirmed): V = 1, 128^2, 1e4 x 12 (1.2e5) 0.111 / 0.126, 1e4 x 16 (1.6e5) 0.126 / 0.132 --
+//    1.04x behind --, 3e4 x 16 0.255 / 0.204.
+//  - 3-D, 9.6e4 (the forward's 1e5 lost this op's row 64^3, 24 000 x 4 at V = 1: 0.178 / 0.133, 1.34x): below it 1e4 x 4
+//    (4e4) 0.108 / 0.113 on 64^3 and 0.117 / 0.147 on 128^3.
+//  - 4 points per tile (confirmed): 256^3, 1e4 x 16 (0.6 per tile) 0.44 / 0.80 and 4.39 / 7.65 at V = 12, 3e4 x 4 (1.8)
+//    0.25 / 0.36 and 2.17 / 3.15, 1e5 x 4 (6.1) 0.53 / 0.49 and 5.64 / 4.06.
+// Only V = 1 and V = 12 were measured: between them the square is an interpolation.
+constexpr int64_t kSmoothBodiesJvpTiledMinWork3D = 96000;
+constexpr int64_t kSmoothBodiesJvpTiledMinWork2D = 160000;
+constexpr int64_t kSmoothBodiesJvpTiledMinPointsPerTile = 4;
+static int resolve_algo_smooth_bodies_jvp(int algo, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t V) {
+    if (algo != DPR_ALGO_AUTO) return algo;
+    const int64_t bg = smooth_clouds_group(n_out, grid, P, B, 0);
+    if (bg == 0) return DPR_ALGO_ATOMIC;
+    const int64_t min_work = n_out == 3 ? kSmoothBodiesJvpTiledMinWork3D : kSmoothBodiesJvpTiledMinWork2D;
+    const int64_t tiles = smooth_tile_count(n_out, grid, P);
+    // (bg * P <= 2^24 for bg > 1, P < 2^32 for bg = 1, V <= 16: the product stays inside 64 bits)
+    return bg * P * V * V >= min_work && P / kSmoothBodiesJvpTiledMinPointsPerTile >= tiles ? DPR_ALGO_TILED
+                                                                                          : DPR_ALGO_ATOMIC;
+}
+
+// Every refusal of the forward-mode entry points, shared by them, the workspace query and
+// dpr_resolve_algo_smooth_bodies_jvp; *G, the resolved *algo and the workspace bytes *need come back.
+static int check_smooth_bodies_jvp(int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
+                                   int64_t B, int64_t K, int64_t V, int64_t* G, size_t* need) {
+    if (!smooth_dims_supported(n_in, n_out))
+        return fail(DPR_ERR_UNSUPPORTED_DIMS,
+                    "smooth rigid bodies, forward mode: (n_in, n_out) = (%d, %d); supports (2,2), (3,3), (3,2)", n_in,
+                    n_out);
+    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
+    if (K < 1) return fail(DPR_ERR_INVALID_ARG, "K = %lld: a call needs at least one body", (long long)K);
+    if (K > 0x7fffffffLL || (B > 0 && K > 0x7fffffffLL / B))
+        return fail(DPR_ERR_INVALID_ARG, "B * K = %lld * %lld poses exceed 2^31 - 1", (long long)B, (long long)K);
+    if (int rc = check_jvp(V, flags)) return rc;  // (V in 1 .. kMaxTangents; KEEP / REUSE refused)
+    if (int rc = check_sample_sizes(P, B, *G)) return rc;
+    if (B > 0 && *G * V > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "output too large");
+    if (*algo != DPR_ALGO_AUTO && *algo != DPR_ALGO_ATOMIC && *algo != DPR_ALGO_TILED)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "the smooth rigid-body JVP runs on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d", *algo);
+    *algo = resolve_algo_smooth_bodies_jvp(*algo, n_out, grid, P, B, V);
+    *need = 0;
+    if (*algo == DPR_ALGO_TILED) {
+        *need = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, smooth_bodies_max_group(flags));
+        if (*need == (size_t)-1) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
+    }
+    return DPR_OK;
+}
+
+template <typename T>
+static int raster_smooth_bodies_jvp_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
+                                         const int64_t* grid, int64_t P, int64_t B, int64_t K, int64_t V, T* out_dot,
+                                         const T* points, const int32_t* body, const T* rot, const T* trans,
+                                         const T* ow, const T* pw, JvpTangents<T> tan, const T* bg_dot, void* ws,
+                                         size_t ws_bytes) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_smooth_bodies_jvp(&algo, flags, n_in, n_out, grid, P, B, K, V, &G, &need)) return rc;
+    if (B == 0) return DPR_OK;
+    if (!out_dot) return fail(DPR_ERR_INVALID_ARG, "out_dot is NULL");
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
+    if (P > 0 && (!rot || !trans)) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL with P > 0");
+    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
+        return fail(DPR_ERR_WORKSPACE, "smooth rigid bodies JVP (algorithm %d) needs %zu workspace bytes, got %zu",
+                    algo, need, ws ? ws_bytes : (size_t)0);
+    if (int rc = check_alignment<T>(ws, {out_dot, points, rot, trans, ow, pw, tan.points, tan.rot, tan.trans, tan.ow,
+                                         tan.pw, bg_dot}))
+        return rc;
+    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    // the background tangent (or 0) into every plane; then the deposits, where any other tangent is given
+    jvp_fill(st, out_dot, G, (int)V, B, bg_dot);
+    stage_mark(st);
+    DPR_HIP(hipGetLastError());
+    if (P == 0 || !(tan.points || tan.rot || tan.trans || tan.ow || tan.pw)) return DPR_OK;
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        const int rc = algo == DPR_ALGO_TILED
+                           ? smooth_bodies_jvp_tiled<T, NI, NO>(st, grid, G, P, B, (int)K, (int)V,
+                                                                smooth_bodies_max_group(flags), out_dot, points, body,
+                                                                rot, trans, ow, pw, tan, ws, ws_bytes)
+                           : smooth_bodies_jvp_atomic<T, NI, NO>(st, grid, G, P, B, (int)K, (int)V, out_dot, points,
+                                                                 body, rot, trans, ow, pw, tan);
+        stage_mark(st);
+        return rc;
+    });
+}
+
 }  // namespace dpr
 
 extern "C" {
@@ -613,5 +967,39 @@ int dpr_resolve_algo_smooth_bodies(int op, int n_in, int n_out, const int64_t* g
 DPR_DEFINE_SMOOTH_BODIES(f32, float)
 DPR_DEFINE_SMOOTH_BODIES(f64, double)
 #undef DPR_DEFINE_SMOOTH_BODIES
+
+int dpr_resolve_algo_smooth_bodies_jvp(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t K,
+                                       int64_t V) {
+    int64_t G = 0;
+    size_t need = 0;
+    int algo = DPR_ALGO_AUTO;
+    if (int rc = dpr::check_smooth_bodies_jvp(&algo, 0u, n_in, n_out, grid, P, B, K, V, &G, &need)) return rc;
+    return algo;
+}
+
+#define DPR_DEFINE_SMOOTH_BODIES_JVP(SUF, T)                                                                      \
+    size_t dpr_workspace_bytes_smooth_bodies_jvp_ex_##SUF(int algo, unsigned flags, int n_in, int n_out,          \
+                                                          const int64_t* grid, int64_t P, int64_t B, int64_t K,   \
+                                                          int64_t V) {                                            \
+        int64_t G = 0;                                                                                            \
+        size_t need = 0;                                                                                          \
+        return dpr::check_smooth_bodies_jvp(&algo, flags, n_in, n_out, grid, P, B, K, V, &G, &need) ? (size_t)-1  \
+                                                                                                     : need;      \
+    }                                                                                                             \
+    int dpr_raster_smooth_bodies_jvp_ex_##SUF(                                                                    \
+        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,   \
+        int64_t K, int64_t V, T* out_dot, const T* points, const void* body, const T* rotation,                   \
+        const T* translation, const T* out_weight, const T* point_weight, const T* points_dot,                    \
+        const T* rotation_dot, const T* translation_dot, const T* background_dot, const T* out_weight_dot,        \
+        const T* point_weight_dot, void* workspace, size_t workspace_bytes) {                                     \
+        return dpr::raster_smooth_bodies_jvp_impl<T>(                                                             \
+            stream, algo, flags, n_in, n_out, grid, P, B, K, V, out_dot, points, (const int32_t*)body, rotation,  \
+            translation, out_weight, point_weight,                                                                \
+            dpr::JvpTangents<T>{points_dot, rotation_dot, translation_dot, out_weight_dot, point_weight_dot},     \
+            background_dot, workspace, workspace_bytes);                                                          \
+    }
+DPR_DEFINE_SMOOTH_BODIES_JVP(f32, float)
+DPR_DEFINE_SMOOTH_BODIES_JVP(f64, double)
+#undef DPR_DEFINE_SMOOTH_BODIES_JVP
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Device helpers of the smooth splat (include/dpr.h, "SMOOTH SPLAT") that the kernels of dpr_smooth.hip,
 // dpr_smooth_channels.hip and dpr_smooth_bodies.hip share: the cell of a point, the B-spline weights of an axis and
-// their derivatives, the per-axis offsets of the 3^N cells, and the pullback's sums of one (point, pose).
+// their derivatives, the per-axis offsets of the 3^N cells, the pullback's sums of one (point, pose), and the rows of
+// one tangent's deposits in forward mode.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -126,6 +127,32 @@ __device__ __forceinline__ void smooth_point_backward(const int (&j0)[NO], const
             dcoord[2] += S * dw[2][k2];
         }
     }
+}
+
+// Forward mode (include/dpr.h, "SMOOTH SPLAT, FORWARD MODE"): the rows of one tangent's deposits.  With a and
+// bc_n = ow * pw * cdot_n of jvp_coeffs (dpr_jvp.h), e_d = w_d and f_d = bc_d * w'_d,
+//   deposit(s) = a * prod_d e_d + sum_n f_n * prod_{d != n} e_d = e_0 * X + f_0 * Y
+//   2-D: X = a * e_1 + f_1,                  Y = e_1
+//   3-D: X = e_1 * (a * e_2 + f_2) + f_1 * e_2,  Y = e_1 * e_2
+// X and Y once per (k1, k2); the kernels of dpr_smooth.hip and dpr_smooth_bodies.hip finish with axis 0.
+template <typename T, int NO> struct SmoothJvpRows {
+    T X[NO == 3 ? 3 : 1][3], Y[NO == 3 ? 3 : 1][3];
+};
+template <typename T, int NO>
+__device__ __forceinline__ SmoothJvpRows<T, NO> smooth_jvp_rows(T a, const T (&bc)[NO], const T (&w)[NO][3],
+                                                                const T (&dw)[NO][3]) {
+    SmoothJvpRows<T, NO> r;
+#pragma unroll
+    for (int k2 = 0; k2 < (NO == 3 ? 3 : 1); ++k2) {
+        const T e2 = NO == 3 ? w[NO - 1][k2] : T(1);
+        const T a2 = NO == 3 ? a * e2 + bc[NO - 1] * dw[NO - 1][k2] : a;  // a * e_2 + f_2
+#pragma unroll
+        for (int k1 = 0; k1 < 3; ++k1) {
+            r.X[k2][k1] = w[1][k1] * a2 + (bc[1] * dw[1][k1]) * e2;
+            r.Y[k2][k1] = w[1][k1] * e2;
+        }
+    }
+    return r;
 }
 
 }  // namespace dpr

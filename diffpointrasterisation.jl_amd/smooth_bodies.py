@@ -100,15 +100,40 @@ def raster_pullback_smooth_bodies_(ds_dout, points, body, rotation, translation,
     return PullbackResult(d_pts, rot, d_trans, d_bg, d_ow, d_pw)
 
 
-class _RasterSmoothBodiesFn(torch.autograd.Function):
+class _SmoothBodiesJvpFn(torch.autograd.Function):
+    """`raster_smooth_bodies_jvp` as one opaque call with plain device tensors, for `_RasterSmoothBodiesFn.jvp`: under
+    torch.func transforms the tangents arrive wrapped, and a function is what unwraps them.  Not differentiable."""
+
     @staticmethod
-    def forward(ctx, grid_size, algo, body, points, rotation, translation, background, out_weight, point_weight):
-        out = raster_smooth_bodies(grid_size, _detach(points), body, _detach(rotation), _detach(translation),
-                                   _detach(background), _detach(out_weight), _detach(point_weight), algo=algo)
-        _save(ctx, (points, rotation, translation, body), (background, out_weight, point_weight))
+    def forward(grid_size, algo, body, points, rotation, translation, background, out_weight, point_weight,
+                points_t, rotation_t, translation_t, background_t, out_weight_t, point_weight_t):
+        from .smooth_bodies_jvp import raster_smooth_bodies_jvp  # (smooth_bodies_jvp imports the bodies family)
+
+        return raster_smooth_bodies_jvp(grid_size, points, body, rotation, translation, background, out_weight,
+                                        point_weight, points_dot=points_t, rotation_dot=rotation_t,
+                                        translation_dot=translation_t, background_dot=background_t,
+                                        out_weight_dot=out_weight_t, point_weight_dot=point_weight_t, algo=algo)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+
+class _RasterSmoothBodiesFn(torch.autograd.Function):
+    # (forward and setup_context apart: what torch.func.jvp asks of a function)
+    @staticmethod
+    def forward(grid_size, algo, body, points, rotation, translation, background, out_weight, point_weight):
+        return raster_smooth_bodies(grid_size, _detach(points), body, _detach(rotation), _detach(translation),
+                                    _detach(background), _detach(out_weight), _detach(point_weight), algo=algo)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        grid_size, algo, body, points, rotation, translation, background, out_weight, point_weight = inputs
+        saved = _save(ctx, (points, rotation, translation, body), (background, out_weight, point_weight))
+        ctx.save_for_forward(*saved)
+        ctx.grid_size, ctx.caller_algo = tuple(int(n) for n in grid_size), algo
         # the pullback has DPR_ALGO_ATOMIC only: a forward on "tiled" differentiates on "auto"
         ctx.algo = "auto" if algo == "tiled" else algo
-        return out
 
     @staticmethod
     def backward(ctx, ds_dout):
@@ -119,11 +144,22 @@ class _RasterSmoothBodiesFn(torch.autograd.Function):
                                             point_weight_grad=bool(ctx.opt_is_tensor[2] and need[8]))
         return (None, None, None, *_cast_grads(need[3:], pb, (points, rotation, translation, *opt)))
 
+    @staticmethod
+    def jvp(ctx, _grid_t, _algo_t, _body_t, points_t, rotation_t, translation_t, background_t, out_weight_t,
+            point_weight_t):
+        (points, rotation, translation, body), opt = _restore(ctx, 4)
+        algo = ctx.caller_algo if ctx.caller_algo in ("atomic", "tiled") else "auto"
+        return _SmoothBodiesJvpFn.apply(ctx.grid_size, algo, body, _detach(points), _detach(rotation),
+                                        _detach(translation), *map(_detach, opt), points_t, rotation_t, translation_t,
+                                        background_t, out_weight_t, point_weight_t)
+
 
 def raster_smooth_bodies_ad(grid_size, points, body, rotation, translation, background=None, out_weight=None,
                             point_weight=None, *, algo: str = "auto") -> torch.Tensor:
     """Differentiable `raster_smooth_bodies` (torch autograd) in points, rotation, translation, background,
     out_weight and point_weight (whichever are tensors that require grad); `body` has no gradient.  The tangents are
-    those of `raster_pullback_smooth_bodies_`."""
+    those of `raster_pullback_smooth_bodies_`.  Forward mode (torch.autograd.forward_ad dual tensors, torch.func.jvp)
+    goes through `raster_smooth_bodies_jvp` with one tangent, on the caller's algorithm ("atomic" / "tiled") or
+    AUTO."""
     return _RasterSmoothBodiesFn.apply(tuple(grid_size), algo, body, points, rotation, translation, background,
                                        out_weight, point_weight)

@@ -1443,6 +1443,90 @@ int dpr_raster_pullback_smooth_bodies_ex_f64(void *stream, int algo, unsigned fl
                                              double *ds_dbackground, double *ds_dout_weight,
                                              double *ds_dpoint_weight, void *workspace, size_t workspace_bytes);
 
+/* ---- SMOOTH SPLAT, RIGID BODIES, FORWARD MODE: out_dot = J . v of dpr_raster_smooth_bodies_* for V = 1..16 tangents --
+ * K is the number of bodies, V the number of tangents.  For image b, tangent v and an accepted point p with body
+ * k = body[p] in [0, K), with coord_d, j0_d, u_d, w_d, w'_d of SMOOTH SPLAT under pose (b, k):
+ *     cdot_n     = n_n / 2 * (sum_j Rdot_{v,b,k}[n, j] p_j + sum_j R_{b,k}[n, j] pdot_{v,p}[j] + tdot_{v,b,k}[n])
+ *     a          = owdot_{v,b} * pw_p + ow_b * pwdot_{v,p}
+ *     c          = ow_b * pw_p
+ *     deposit(s) = a * prod_d w_d(s_d) + c * sum_n cdot_n * w'_n(s_n) * prod_{d != n} w_d(s_d),  s in {-1, 0, +1}^n_out
+ *     out_dot[j0 + s, v, b] = bgdot_{v,b} + sum over (p, s) that land on the cell
+ * No cell is held fixed: this is the exact directional derivative of dpr_raster_smooth_bodies_ex_* and the exact
+ * transpose of dpr_raster_pullback_smooth_bodies_ex_*.  A point that dpr_raster_smooth_bodies_ex_* drops (outside the
+ * acceptance range in that image, or body outside [0, K)) deposits nothing and none of its tangents is read: NaN
+ * there leaves no trace.  Any tangent may be NULL (= zero, the same bits as an explicit zero); with all of them NULL
+ * out_dot is zero-filled.  out_weight / point_weight NULL = 1; the primal background does not enter.
+ * Layouts: the primals exactly as dpr_raster_smooth_bodies_ex_* (pose (b, k) at b * K + k, rotation column-major
+ * n_out x n_in per pose, body int32_t).  Every tangent holds V copies of its primal's layout, tangent v first:
+ * points_dot V x P x n_in; rotation_dot and translation_dot with pose tangent (v, b, k) at (v * B + b) * K + k;
+ * out_weight_dot and background_dot at v * B + b; point_weight_dot at v * P + p.  out_dot is the channel layout with
+ * C = V: plane (b, v) at (b * V + v) * G, as dpr_raster_smooth_jvp_ex_* has it.  out_dot is overwritten.
+ * (n_in, n_out): (2,2), (3,3), (3,2).  K >= 1, B * K <= 2^31 - 1, V in 1..16.
+ * Algorithms (DPR_ALGO_CHUNKED, DPR_ALGO_ORDERED: DPR_ERR_UNSUPPORTED_ALGO).
+ *   DPR_ALGO_ATOMIC  background tangent fill, then one thread per point, the images over grid.y: the primal pose as
+ *                    the DPR_ALGO_ATOMIC forward of SMOOTH SPLAT, RIGID BODIES loads it, the cell, the weights and
+ *                    their derivatives once per accepted (point, image), the V tangents a run-time loop of 3^N global
+ *                    float atomics each.  The pose tangent of (v, b, body) is loaded as the primal pose is: scalar
+ *                    loads where a wave's points share a body -- SORT THE CLOUD BY BODY -- a gather per lane
+ *                    otherwise.  No lanes are combined before the atomics.  Workspace 0.
+ *   DPR_ALGO_TILED   background tangent fill, then per GROUP of images the key pass, the stable sort and the start
+ *                    table of the DPR_ALGO_TILED forward of SMOOTH SPLAT, RIGID BODIES ONCE -- they depend on the
+ *                    primal only -- and ONE launch of (bg * tiles) x V workgroups: four launches per group, whatever V.
+ *                    Workgroup (image, tile, v) walks the run of its (image, tile) with the forward's distrust of the
+ *                    workspace (run clamped to the group's entries, point index to [0, P), body to [0, K)), gathers
+ *                    pose and pose tangent per lane, adds the deposits of tangent v into the f64 LDS tile + halo and
+ *                    adds every non-zero cell inside the grid onto plane (b, v) with one float atomic.  GROUP SIZE,
+ *                    LIMITS and workspace: exactly those of dpr_raster_smooth_bodies_ex_*(DPR_ALGO_TILED) for the same
+ *                    (grid, P, B, flags), independent of K and V; 0 for P = 0.  Every piece of the layout is written
+ *                    before it is read, as there.
+ * Flags: DPR_FLAG_MAX_POSE_GROUP(n) is HONOURED by DPR_ALGO_TILED (pass the same flags to the workspace query) and
+ * ignored by DPR_ALGO_ATOMIC; KEEP / REUSE are refused; the others are accepted and ignored.
+ * AUTO (dpr_resolve_algo_smooth_bodies_jvp), from the shape and V alone, never from the points or `body`:
+ * DPR_ALGO_TILED where the default group holds bg * P * V^2 >= 96 000 for a 3-D grid and >= 160 000 for a 2-D grid, the
+ * cloud holds at least 4 points per tile (P >= 4 * tiles) and the LIMITS hold; DPR_ALGO_ATOMIC otherwise.  K does not
+ * enter.  For V = 1 this is the rule of dpr_resolve_algo_smooth_bodies(DPR_OP_RASTER) (with 96 000 for its 100 000).  The
+ * rule started from that one with the group's work multiplied by V; this op's own times
+ * (profiles/smooth_bodies_jvp_probe.txt, tests/golden/smooth_bodies_jvp_auto.json; fp32, uniform clouds, 140 rows, V = 1
+ * and 12) left no constant for bg * P * V: 1000 points x 4 images -> 128^2 at V = 12 (4.8e4) is 1.28x faster TILED while 1e4 x
+ * 8 at V = 1 (8e4) is 1.28x faster ATOMIC.  The binning is paid once per group whatever V and costs about one tangent's
+ * atomics, so the group size from which DPR_ALGO_TILED pays falls faster than 1 / V: at V = 12 it is ahead on every row
+ * measured with 4 points per tile (down to bg * P = 2 200), at V = 1 from the forward's constants on (2-D: 1e4 x 12
+ * 1.14x faster ATOMIC, 1e4 x 16 level; 3-D: 24 000 x 4 -> 64^3 1.34x faster TILED, which moved 100 000 to 96 000).  With
+ * V^2 AUTO is within 1.15x of the faster algorithm on every row (at most 1.06x behind).  Between V = 1 and V = 12
+ * nothing was measured: there the square is an interpolation.
+ * Summation order: both algorithms are at rounding level (float atomics in arrival order; DPR_ALGO_TILED adds a
+ * tile's deposits in f64 first) and agree at that level.
+ * P = 0: only the background tangent is written.  B = 0: nothing is done.  Both DPR_OK.
+ * Errors (status, dpr_last_error text, nothing launched, out_dot untouched): a pair outside the three
+ * DPR_ERR_UNSUPPORTED_DIMS; a bad grid, negative P / B, K < 1, B * K beyond 2^31 - 1, V outside 1..16, a NULL out_dot
+ * while B > 0, NULL points, body, rotation or translation while P * B > 0, a misaligned data pointer
+ * DPR_ERR_INVALID_ARG; KEEP / REUSE, DPR_ALGO_CHUNKED / DPR_ALGO_ORDERED / an unknown algorithm and DPR_ALGO_TILED
+ * outside its LIMITS DPR_ERR_UNSUPPORTED_ALGO; a workspace smaller than dpr_workspace_bytes_smooth_bodies_jvp_ex_* or
+ * not 256-byte aligned DPR_ERR_WORKSPACE.  Every refusal comes from one check that the entry points, the query and
+ * the resolver share: the query returns (size_t)-1 for every refused combination, the resolver a negative status. */
+int dpr_resolve_algo_smooth_bodies_jvp(int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B, int64_t K,
+                                       int64_t V);
+size_t dpr_workspace_bytes_smooth_bodies_jvp_ex_f32(int algo, unsigned flags, int n_in, int n_out,
+                                                    const int64_t *grid, int64_t P, int64_t B, int64_t K, int64_t V);
+size_t dpr_workspace_bytes_smooth_bodies_jvp_ex_f64(int algo, unsigned flags, int n_in, int n_out,
+                                                    const int64_t *grid, int64_t P, int64_t B, int64_t K, int64_t V);
+int dpr_raster_smooth_bodies_jvp_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                        const int64_t *grid, int64_t P, int64_t B, int64_t K, int64_t V,
+                                        float *out_dot, const float *points, const void *body,
+                                        const float *rotation, const float *translation, const float *out_weight,
+                                        const float *point_weight, const float *points_dot,
+                                        const float *rotation_dot, const float *translation_dot,
+                                        const float *background_dot, const float *out_weight_dot,
+                                        const float *point_weight_dot, void *workspace, size_t workspace_bytes);
+int dpr_raster_smooth_bodies_jvp_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                        const int64_t *grid, int64_t P, int64_t B, int64_t K, int64_t V,
+                                        double *out_dot, const double *points, const void *body,
+                                        const double *rotation, const double *translation, const double *out_weight,
+                                        const double *point_weight, const double *points_dot,
+                                        const double *rotation_dot, const double *translation_dot,
+                                        const double *background_dot, const double *out_weight_dot,
+                                        const double *point_weight_dot, void *workspace, size_t workspace_bytes);
+
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
  * not in the reference; every algorithm here is faster on coherent input and the sort only depends
