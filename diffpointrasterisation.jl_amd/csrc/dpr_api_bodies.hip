@@ -27,7 +27,7 @@ static int check_bodies(int op, int algo, unsigned flags, int n_in, int n_out, c
     // the B * K pose gradients and their offsets stay far inside both with this bound
     if (K > 0x7fffffffLL || (B > 0 && K > 0x7fffffffLL / B))
         return fail(DPR_ERR_INVALID_ARG, "B * K = %lld * %lld poses exceed 2^31 - 1", (long long)B, (long long)K);
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (int rc = check_point_blocks(P)) return rc;
     if (flags & 3u)
         return fail(DPR_ERR_UNSUPPORTED_ALGO,
                     "rigid bodies keep / reuse no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");

@@ -66,7 +66,7 @@ static int raster_channels_impl(void* stream, int algo, unsigned flags, int n_in
     if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
     if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
     if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (int rc = check_point_blocks(P)) return rc;
     if (G * C * B / B != G * C || G * C > ((int64_t)1 << 62) / (B > 0 ? B : 1))
         return fail(DPR_ERR_INVALID_ARG, "output too large");
     if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
@@ -132,7 +132,7 @@ static int pullback_channels_impl(void* stream, int algo, unsigned flags, int n_
     if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
     if (!d_rot || !d_trans || !d_bg || !d_ow)
         return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (int rc = check_point_blocks(P)) return rc;
     if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
         return rc;
     stage_mark(st);

@@ -24,7 +24,7 @@ static int check_clouds_op(int op, unsigned flags) {
 
 // 64-bit offsets: cloud b starts at b * P * n_in, plane b at b * G
 static int check_clouds_sizes(int n_in, int64_t P, int64_t B, int64_t G) {
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (int rc = check_point_blocks(P)) return rc;
     if (B > 0 && (P > ((int64_t)1 << 60) / B / n_in || G > ((int64_t)1 << 62) / B))
         return fail(DPR_ERR_INVALID_ARG, "B * P * n_in or the image (G * B) too large");
     return DPR_OK;

@@ -39,7 +39,7 @@ static size_t sample_tiled_workspace_bytes(size_t elem, unsigned flags, int n_in
 }
 
 int check_sample_sizes(int64_t P, int64_t B, int64_t G) {
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (int rc = check_point_blocks(P)) return rc;
     if (B > 0 && (P > ((int64_t)1 << 62) / B || G > ((int64_t)1 << 62) / B))
         return fail(DPR_ERR_INVALID_ARG, "P * B or the image (G * B) too large");
     if (B > (int64_t)65535 * 0x7fffffff) return fail(DPR_ERR_INVALID_ARG, "B too large");

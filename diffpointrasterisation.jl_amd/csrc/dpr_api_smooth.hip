@@ -1,5 +1,6 @@
 // The smooth entry points of libdpr -- splat, sampling, forward mode, per-pose clouds and weight channels: host checks,
-// AUTO rules and C ABI (core: dpr_api.hip; kernels and their launches: dpr_smooth.hip, dpr_smooth_channels.hip).
+// AUTO rules and C ABI (core: dpr_api.hip; kernels and their launches: dpr_smooth.hip, dpr_smooth_channels.hip; the
+// smooth splat of rigid bodies: dpr_api_smooth_bodies.hip).
 #include <hip/hip_runtime.h>
 
 #include "dpr_host.h"
@@ -64,13 +65,6 @@ static size_t smooth_workspace_bytes(int op, int algo, int n_out, const int64_t*
     return n;
 }
 
-template <class F> static int with_smooth_dims(int n_in, int n_out, F&& f) {
-    if (n_in == 2 && n_out == 2) return f(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
-    if (n_in == 3 && n_out == 3) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
-    if (n_in == 3 && n_out == 2) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{});
-    return fail(DPR_ERR_UNSUPPORTED_DIMS, "smooth splat: unsupported (n_in, n_out) = (%d, %d)", n_in, n_out);
-}
-
 template <typename T>
 static int raster_smooth_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
                               int64_t P, int64_t B, T* out, const T* points, const T* rot, const T* trans,
@@ -79,7 +73,7 @@ static int raster_smooth_impl(void* stream, int algo, unsigned flags, int n_in, 
     if (int rc = check_smooth_dims(n_in, n_out)) return rc;
     if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
     if (int rc = check_smooth(DPR_OP_RASTER, flags)) return rc;
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (int rc = check_point_blocks(P)) return rc;
     algo = resolve_algo_smooth(algo, DPR_OP_RASTER, n_out, grid, P);
     const size_t need = smooth_workspace_bytes(DPR_OP_RASTER, algo, n_out, grid, P);
     if (need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
@@ -115,7 +109,7 @@ static int pullback_smooth_impl(void* stream, int algo, unsigned flags, int n_in
     if (int rc = check_smooth_dims(n_in, n_out)) return rc;
     if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
     if (int rc = check_smooth(DPR_OP_PULLBACK, flags)) return rc;
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (int rc = check_point_blocks(P)) return rc;
     if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
     algo = resolve_algo_smooth(algo, DPR_OP_PULLBACK, n_out, grid, P);
     if (smooth_workspace_bytes(DPR_OP_PULLBACK, algo, n_out, grid, P) == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
@@ -380,7 +374,6 @@ static size_t workspace_smooth_jvp_impl(int algo, unsigned flags, int n_in, int 
 // dpr_raster_smooth_clouds_ex_* / dpr_raster_pullback_smooth_clouds_ex_* (include/dpr.h, "SMOOTH SPLAT, PER-POSE
 // CLOUDS"; kernels: dpr_smooth.hip).  DPR_ALGO_ATOMIC: forward and pullback, one thread per (point, pose).
 // DPR_ALGO_TILED: forward, the poses binned in groups (smooth_clouds_group; DPR_FLAG_MAX_POSE_GROUP honoured).
-static int smooth_clouds_max_group(unsigned flags) { return (int)((flags >> 8) & 0xffu); }
 
 // AUTO (dpr_resolve_algo_smooth_clouds), from the shape alone (profiles/smooth_clouds_probe.txt, fp32, uniform clouds
 // in generation order, times in ms TILED / ATOMIC).  The pullback is DPR_ALGO_ATOMIC.  The forward is DPR_ALGO_TILED
@@ -421,7 +414,7 @@ static size_t smooth_clouds_workspace_bytes(int op, int algo, unsigned flags, in
         fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth pullback runs on DPR_ALGO_ATOMIC only");
         return (size_t)-1;
     }
-    const size_t n = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, smooth_clouds_max_group(flags));
+    const size_t n = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, max_pose_group(flags));
     if (n == (size_t)-1)
         fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
     return n;
@@ -435,7 +428,7 @@ static int check_smooth_clouds(int op, int* algo, unsigned flags, int n_in, int 
     if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
     if (int rc = check_smooth(op, flags)) return rc;
     // 64-bit offsets: cloud b starts at b * P * n_in, plane b at b * G
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (int rc = check_point_blocks(P)) return rc;
     if (B > 0 && (P > ((int64_t)1 << 60) / B / n_in || *G > ((int64_t)1 << 62) / B))
         return fail(DPR_ERR_INVALID_ARG, "B * P * n_in or the image (G * B) too large");
     *algo = resolve_algo_smooth_clouds(*algo, op, n_out, grid, P, B);
@@ -465,7 +458,7 @@ static int raster_smooth_clouds_impl(void* stream, int algo, unsigned flags, int
     return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
         constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
         const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_clouds_fwd_tiled<T, NI, NO>(st, grid, G, P, B, smooth_clouds_max_group(flags), out,
+                           ? smooth_clouds_fwd_tiled<T, NI, NO>(st, grid, G, P, B, max_pose_group(flags), out,
                                                                 points, rot, trans, ow, pw, ws, ws_bytes)
                            : smooth_clouds_fwd_atomic<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, ow, pw);
         stage_mark(st);
@@ -551,7 +544,7 @@ static int check_smooth_channels(int op, int* algo, unsigned flags, int n_in, in
     if (C < 1 || C > kMaxChannels)
         return fail(DPR_ERR_INVALID_ARG, "channels C = %lld out of range [1, %d]", (long long)C, kMaxChannels);
     // 64-bit offsets: plane (c, b) starts at (b * C + c) * G, the weights of point p at p * C
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
+    if (int rc = check_point_blocks(P)) return rc;
     if (B > 0 && *G * C > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "output too large");
     *algo = resolve_algo_smooth_channels(*algo, op, n_out, grid, P, C);
     *need = smooth_workspace_bytes(op, *algo, n_out, grid, P);

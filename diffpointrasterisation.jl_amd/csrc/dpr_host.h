@@ -52,6 +52,10 @@ int check_alignment(const void* ws, std::initializer_list<const void*> data) {
 }
 
 int check_common(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t* G_out);
+// (a launch of one thread per point counts its blocks of kBlock points in 31 bits)
+inline int check_point_blocks(int64_t P) {
+    return (P + kBlock - 1) / kBlock > 0x7fffffffLL ? fail(DPR_ERR_INVALID_ARG, "P too large") : DPR_OK;
+}
 int resolve_algo(int algo, int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t G,
                  unsigned* flags);
 int pose_slices(int64_t P, int64_t B, int64_t* slices_out);

@@ -1,7 +1,10 @@
 // The smooth splat (include/dpr.h, "SMOOTH SPLAT"): quadratic B-spline weights on 3^N cells per point.
-// Index arithmetic shared by the host plan and the kernels of dpr_smooth.hip, and the entry points
-// dpr_api_smooth.hip calls.
+// Index arithmetic shared by the host plan and the kernels of dpr_smooth.hip, and the launchers of dpr_smooth.hip,
+// dpr_smooth_channels.hip and dpr_smooth_bodies.hip that dpr_api_smooth.hip and dpr_api_smooth_bodies.hip call.
 #pragma once
+#include <type_traits>
+
+#include "../../include/dpr.h"
 #include "dpr_tiled.h"
 
 namespace dpr {
@@ -44,13 +47,22 @@ constexpr uint32_t kSmoothNoKey = 0xffffffffu;  // a rejected point; sorts behin
 constexpr bool smooth_dims_supported(int n_in, int n_out) {
     return (n_in == 2 && n_out == 2) || (n_in == 3 && n_out == 3) || (n_in == 3 && n_out == 2);
 }
+// f(std::integral_constant<int, NI>{}, std::integral_constant<int, NO>{}) for the runtime pair.  Callers have refused
+// every other pair with their family's own message.
+template <class F> int with_smooth_dims(int n_in, int n_out, F&& f) {
+    if (n_in == 2 && n_out == 2) return f(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
+    if (n_in == 3 && n_out == 3) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
+    if (n_in == 3 && n_out == 2) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{});
+    return fail(DPR_ERR_UNSUPPORTED_DIMS, "smooth splat: unsupported (n_in, n_out) = (%d, %d)", n_in, n_out);
+}
 
 // tiles of the grid, or 0 where DPR_ALGO_TILED cannot run the call: tile ids 0 .. tiles - 1 must stay below the
 // all-ones key and the index of a point must fit 32 bits (P <= 2^32 - 2)
 int64_t smooth_tile_count(int n_out, const int64_t* grid, int64_t P);
 // the message of every refusal that follows from smooth_tile_count == 0
 constexpr char kSmoothTiledRefused[] = "smooth DPR_ALGO_TILED: too many tiles for a 32-bit key or P > 2^32 - 2";
-// bytes of workspace of the tiled forward (0 for P = 0); independent of B
+// bytes of workspace of the tiled forward (0 for P = 0; (size_t)-1 where refused); independent of B:
+// smooth_clouds_tiled_workspace_bytes (below) for a group of one
 size_t smooth_tiled_workspace_bytes(int n_out, const int64_t* grid, int64_t P);
 
 // The point kernels.  `out` holds the background already; the pullback's per-pose sums are zeroed and
@@ -68,35 +80,34 @@ int smooth_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
                       const T* points, const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts, T* d_rot,
                       T* d_trans, T* d_ow, T* d_pw, int poses_per_slice, int64_t slices);
 
-// The binning of DPR_ALGO_TILED, for the launchers of dpr_smooth.hip and dpr_smooth_channels.hip (k_smooth_keys and
-// k_smooth_ranges are compiled in dpr_smooth.hip only).  smooth_binning: the tiles of a call and the pieces of its
-// workspace (DPR_ERR_UNSUPPORTED_ALGO / DPR_ERR_WORKSPACE where the call cannot run).  smooth_bin_pose: keys -> stable
-// sort -> start table of pose b, which depend on the primal only; afterwards sb.start[t] .. sb.start[t + 1] is the
-// run of tile t in sb.idx_out.
+// The binning of DPR_ALGO_TILED, shared by every tiled launcher of dpr_smooth.hip, dpr_smooth_channels.hip and
+// dpr_smooth_bodies.hip (the plan of the workspace, k_smooth_keys and k_smooth_ranges are compiled in dpr_smooth.hip
+// only).  A call bins `group` images at a time: 1 for the families that bin pose by pose, smooth_clouds_group(...) for
+// per-pose clouds and rigid bodies.
+// smooth_binning: the tiles of a call and the pieces of its workspace, laid out for (group * tiles, group * P) and
+//   reused from group to group -- the last may hold B % group images.  DPR_ERR_UNSUPPORTED_ALGO with
+//   kSmoothTiledRefused where group is 0 or smooth_tile_count refuses, DPR_ERR_WORKSPACE where ws is too small.
+// smooth_sort_group: what follows the key kernel of a family for nb images of P points: mark, stable radix sort of
+//   the nb * P (key, index) pairs over the bits of nb * tiles, mark, start table (k_smooth_ranges: start[k] = first
+//   sorted position with key >= k, k = 0 .. nb * tiles), mark.  Afterwards sb.start[k] .. sb.start[k + 1] is the run
+//   of key k in sb.idx_out.
+// smooth_bin_pose: k_smooth_keys of pose b, then smooth_sort_group of one image; depends on the primal only.
 template <int NO> struct SmoothBinning {
     GridDesc<NO> gd;
     SmoothTiles<NO> tl;
-    int64_t tiles;
-    int bits;  // of a key
+    int64_t tiles;  // of one image
+    int64_t group;  // images binned at a time
     char* temp;
     size_t temp_bytes;
     uint32_t *keys_in, *keys_out, *idx_in, *idx_out, *start;
 };
 template <int NO>
-int smooth_binning(const int64_t* grid, int64_t G, int64_t P, void* ws, size_t ws_bytes, SmoothBinning<NO>* sb);
+int smooth_binning(const int64_t* grid, int64_t G, int64_t P, int64_t B, int64_t group, void* ws, size_t ws_bytes,
+                   SmoothBinning<NO>* sb);
+template <int NO> int smooth_sort_group(hipStream_t st, const SmoothBinning<NO>& sb, int64_t nb, int64_t P);
 template <typename T, int NI, int NO>
 int smooth_bin_pose(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int64_t b, const T* points, const T* rot,
                     const T* trans);
-
-// The workspace of one binning of `P` sorted entries over `tiles` keys (offsets of its pieces, `total` bytes; all 0
-// for P <= 0), and the start table over sorted keys (k_smooth_ranges, compiled in dpr_smooth.hip only): start[k] =
-// first position with key >= k for k = 0 .. entries - 1.  For the grouped launchers of dpr_smooth.hip and
-// dpr_smooth_bodies.hip.
-struct SmoothPlan {
-    size_t off_keys_in, off_keys_out, off_idx_in, off_idx_out, off_temp, temp_bytes, off_start, total;
-};
-SmoothPlan smooth_plan(int64_t tiles, int64_t P, int64_t P_last = 0);
-int smooth_ranges(hipStream_t st, const uint32_t* keys, uint32_t count, uint64_t entries, int bits, uint32_t* start);
 
 // C weights per point (include/dpr.h, "SMOOTH SPLAT, MULTI-CHANNEL"; kernels: dpr_smooth_channels.hip): pw is
 // P x C with a point's weights contiguous, plane (c, b) of out / g at (b * C + c) * G.  The same contract with the
@@ -124,8 +135,8 @@ int smooth_channels_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, i
 // reason for it: include/dpr.h.)
 constexpr int64_t kSmoothCloudsGroupWork = (int64_t)1 << 24;
 int64_t smooth_clouds_group(int n_out, const int64_t* grid, int64_t P, int64_t B, int max_group);
-// bytes of workspace of the tiled forward: smooth_tiled_workspace_bytes' layout for (bg * tiles, bg * P), reused from
-// group to group; equal to smooth_tiled_workspace_bytes(n_out, grid, P) for a group of one; (size_t)-1 where refused
+// bytes of workspace of the tiled forward: the plan smooth_binning lays out for a group of smooth_clouds_group(...)
+// images, reused from group to group; (size_t)-1 where refused
 size_t smooth_clouds_tiled_workspace_bytes(int n_out, const int64_t* grid, int64_t P, int64_t B, int max_group);
 template <typename T, int NI, int NO>
 int smooth_clouds_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* out,
@@ -150,6 +161,33 @@ template <typename T, int NI, int NO>
 int smooth_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out_dot,
                      const T* points, const T* rot, const T* trans, const T* ow, const T* pw, JvpTangents<T> tan,
                      void* ws, size_t ws_bytes);
+
+// Rigid bodies (include/dpr.h, "SMOOTH SPLAT, RIGID BODIES" and "... FORWARD MODE"; kernels: dpr_smooth_bodies.hip):
+// point p is seen in image b through pose b * K + body[p]; V tangents.  The same contract with the caller as above
+// (dpr_api_smooth_bodies.hip).  The tiled forms bin the images in groups as smooth_clouds_fwd_tiled bins poses and
+// take its workspace; the JVP's binning serves all V tangents.  The pullback slices the images as smooth_bwd_atomic
+// slices the poses, and zeroes d_pts / d_pw here with more than one slice.
+template <typename T, int NI, int NO>
+int smooth_bodies_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out,
+                             const T* points, const int32_t* body, const T* rot, const T* trans, const T* ow,
+                             const T* pw);
+template <typename T, int NI, int NO>
+int smooth_bodies_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int max_group,
+                            T* out, const T* points, const int32_t* body, const T* rot, const T* trans, const T* ow,
+                            const T* pw, void* ws, size_t ws_bytes);
+template <typename T, int NI, int NO>
+int smooth_bodies_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, const T* g,
+                             const T* points, const int32_t* body, const T* rot, const T* trans, const T* ow,
+                             const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_ow, T* d_pw, int poses_per_slice,
+                             int64_t slices);
+template <typename T, int NI, int NO>
+int smooth_bodies_jvp_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int V,
+                             T* out_dot, const T* points, const int32_t* body, const T* rot, const T* trans,
+                             const T* ow, const T* pw, JvpTangents<T> tan);
+template <typename T, int NI, int NO>
+int smooth_bodies_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int V,
+                            int max_group, T* out_dot, const T* points, const int32_t* body, const T* rot,
+                            const T* trans, const T* ow, const T* pw, JvpTangents<T> tan, void* ws, size_t ws_bytes);
 
 // Smooth sampling (include/dpr.h, "SMOOTH SAMPLING"), with the same pose slicing.  Forward: values (P x B, point
 // index fastest) are stored, no atomics.  Pullback: any of d_img, d_pts, d_rot, d_trans may be NULL (none: nothing

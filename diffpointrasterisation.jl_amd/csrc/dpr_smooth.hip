@@ -23,6 +23,8 @@
 //                             k_smooth_clouds_tile (include/dpr.h, "SMOOTH SPLAT, PER-POSE CLOUDS"): pose b reads
 //                             cloud b; a thread per (point, pose); the tiled forward bins a GROUP of poses with one
 //                             key pass, one sort, one start table and one launch of (poses x tiles) workgroups
+//   host side of the binning  smooth_plan (the workspace), smooth_binning, smooth_sort_group, smooth_bin_pose: one copy
+//                             for every tiled launcher here, in dpr_smooth_channels.hip and in dpr_smooth_bodies.hip
 #include <hip/hip_runtime.h>
 
 #include "../../include/dpr.h"
@@ -938,29 +940,33 @@ int64_t smooth_tile_count(int n_out, const int64_t* grid, int64_t P) {
     return tiles < (int64_t)0x7fffffffLL ? tiles : 0;  // (also the largest launch: one workgroup per tile)
 }
 
-// (declared in dpr_smooth.h; P_last: a second, smaller count the same storage must sort -- the last group of a
-// grouped call)
-SmoothPlan smooth_plan(int64_t tiles, int64_t P, int64_t P_last) {
+// The workspace of a call of B images that bins `group` of them at a time, `tiles` tiles and P points each: offsets of
+// its pieces and `total` bytes (all 0 for P <= 0).  The storage sorts group * P pairs, and (B % group) * P in a
+// shorter last group, whose sort may ask for more temporary bytes.  The one plan of every tiled smooth launcher
+// (smooth_binning) and of both workspace queries below.
+struct SmoothPlan {
+    size_t off_keys_in, off_keys_out, off_idx_in, off_idx_out, off_temp, temp_bytes, off_start, total;
+};
+static SmoothPlan smooth_plan(int64_t tiles, int64_t P, int64_t B, int64_t group) {
     SmoothPlan pl{};
     if (P <= 0) return pl;
+    const int64_t count = group * P, last = (B % group) * P;
     size_t o = 0;
-    pl.off_keys_in = o;  o += align_up((size_t)P * 4);
-    pl.off_keys_out = o; o += align_up((size_t)P * 4);
-    pl.off_idx_in = o;   o += align_up((size_t)P * 4);
-    pl.off_idx_out = o;  o += align_up((size_t)P * 4);
+    pl.off_keys_in = o;  o += align_up((size_t)count * 4);
+    pl.off_keys_out = o; o += align_up((size_t)count * 4);
+    pl.off_idx_in = o;   o += align_up((size_t)count * 4);
+    pl.off_idx_out = o;  o += align_up((size_t)count * 4);
     pl.off_temp = o;
-    pl.temp_bytes = radix_pairs_temp_bytes(P);
-    if (P_last > 0 && radix_pairs_temp_bytes(P_last) > pl.temp_bytes) pl.temp_bytes = radix_pairs_temp_bytes(P_last);
+    pl.temp_bytes = radix_pairs_temp_bytes(count);
+    if (last > 0 && radix_pairs_temp_bytes(last) > pl.temp_bytes) pl.temp_bytes = radix_pairs_temp_bytes(last);
     o += align_up(pl.temp_bytes);
-    pl.off_start = o;    o += align_up((size_t)(tiles + 1) * 4);
+    pl.off_start = o;    o += align_up((size_t)(group * tiles + 1) * 4);
     pl.total = o;
     return pl;
 }
 
 size_t smooth_tiled_workspace_bytes(int n_out, const int64_t* grid, int64_t P) {
-    const int64_t tiles = smooth_tile_count(n_out, grid, P);
-    if (tiles == 0) return (size_t)-1;
-    return smooth_plan(tiles, P).total;
+    return smooth_clouds_tiled_workspace_bytes(n_out, grid, P, 1, 1);
 }
 
 template <typename T, int NI, int NO>
@@ -976,13 +982,14 @@ int smooth_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
 }
 
 // What the tiled launchers share (declared in dpr_smooth.h): the tiles and workspace pieces of a call
-// (smooth_binning), and the binning of one pose (smooth_bin_pose): keys -> sort -> ranges, which depend on the
-// primal only.
+// (smooth_binning), what follows a key kernel (smooth_sort_group), and the binning of one pose (smooth_bin_pose).
+// (No entry point reaches the workspace message: each has compared ws_bytes with the query's answer, the same plan.)
 template <int NO>
-int smooth_binning(const int64_t* grid, int64_t G, int64_t P, void* ws_, size_t ws_bytes, SmoothBinning<NO>* sb) {
+int smooth_binning(const int64_t* grid, int64_t G, int64_t P, int64_t B, int64_t group, void* ws_, size_t ws_bytes,
+                   SmoothBinning<NO>* sb) {
     const int64_t tiles = smooth_tile_count(NO, grid, P);
-    if (tiles == 0) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    const SmoothPlan pl = smooth_plan(tiles, P);
+    if (tiles == 0 || group == 0) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
+    const SmoothPlan pl = smooth_plan(tiles, P, B, group);
     if (!ws_ || ws_bytes < pl.total)
         return fail(DPR_ERR_WORKSPACE, "smooth DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
                     ws_ ? ws_bytes : (size_t)0);
@@ -990,7 +997,7 @@ int smooth_binning(const int64_t* grid, int64_t G, int64_t P, void* ws_, size_t 
     sb->gd = make_grid_desc<NO>(grid, G);
     sb->tl = smooth_tiles<NO>(grid);
     sb->tiles = tiles;
-    sb->bits = ord_key_bits((uint64_t)tiles);
+    sb->group = group;
     sb->temp = ws + pl.off_temp;
     sb->temp_bytes = pl.temp_bytes;
     sb->keys_in = (uint32_t*)(ws + pl.off_keys_in);
@@ -1000,29 +1007,25 @@ int smooth_binning(const int64_t* grid, int64_t G, int64_t P, void* ws_, size_t 
     sb->start = (uint32_t*)(ws + pl.off_start);
     return DPR_OK;
 }
-template <typename T, int NI, int NO>
-int smooth_bin_pose(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int64_t b, const T* points,
-                    const T* rot, const T* trans) {
-    const dim3 blk(kSmBlock);
-    const dim3 pgrid((unsigned)((P + kSmBlock - 1) / kSmBlock));
-    const dim3 rgrid((unsigned)((sb.tiles + 1 + kSmBlock - 1) / kSmBlock));
-    hipLaunchKernelGGL((k_smooth_keys<T, NI, NO>), pgrid, blk, 0, st, sb.gd, sb.tl, P, b, points, rot, trans,
-                       sb.keys_in, sb.idx_in);
+template <int NO> int smooth_sort_group(hipStream_t st, const SmoothBinning<NO>& sb, int64_t nb, int64_t P) {
+    const int64_t count = nb * P, entries = nb * sb.tiles + 1;
+    const int bits = ord_key_bits((uint64_t)(nb * sb.tiles));
     stage_mark(st);
-    DPR_HIP(radix_sort_pairs_u32(sb.temp, sb.temp_bytes, sb.keys_in, sb.keys_out, sb.idx_in, sb.idx_out, (size_t)P,
-                                 0u, (unsigned)sb.bits, st));
+    DPR_HIP(radix_sort_pairs_u32(sb.temp, sb.temp_bytes, sb.keys_in, sb.keys_out, sb.idx_in, sb.idx_out,
+                                 (size_t)count, 0u, (unsigned)bits, st));
     stage_mark(st);
-    hipLaunchKernelGGL(k_smooth_ranges, rgrid, blk, 0, st, (const uint32_t*)sb.keys_out, (uint32_t)P,
-                       (uint64_t)(sb.tiles + 1), sb.bits, sb.start);
+    hipLaunchKernelGGL(k_smooth_ranges, dim3((unsigned)((entries + kSmBlock - 1) / kSmBlock)), dim3(kSmBlock), 0, st,
+                       (const uint32_t*)sb.keys_out, (uint32_t)count, (uint64_t)entries, bits, sb.start);
+    DPR_HIP(hipGetLastError());
     stage_mark(st);
     return DPR_OK;
 }
-
-int smooth_ranges(hipStream_t st, const uint32_t* keys, uint32_t count, uint64_t entries, int bits, uint32_t* start) {
-    hipLaunchKernelGGL(k_smooth_ranges, dim3((unsigned)((entries + kSmBlock - 1) / kSmBlock)), dim3(kSmBlock), 0, st,
-                       keys, count, entries, bits, start);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
+template <typename T, int NI, int NO>
+int smooth_bin_pose(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int64_t b, const T* points,
+                    const T* rot, const T* trans) {
+    hipLaunchKernelGGL((k_smooth_keys<T, NI, NO>), dim3((unsigned)((P + kSmBlock - 1) / kSmBlock)), dim3(kSmBlock), 0,
+                       st, sb.gd, sb.tl, P, b, points, rot, trans, sb.keys_in, sb.idx_in);
+    return smooth_sort_group<NO>(st, sb, 1, P);
 }
 
 template <typename T, int NI, int NO>
@@ -1030,7 +1033,7 @@ int smooth_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, 
                      const T* rot, const T* trans, const T* ow, const T* pw, void* ws, size_t ws_bytes) {
     if (P <= 0 || B <= 0) return DPR_OK;
     SmoothBinning<NO> sb;
-    if (int rc = smooth_binning<NO>(grid, G, P, ws, ws_bytes, &sb)) return rc;
+    if (int rc = smooth_binning<NO>(grid, G, P, B, 1, ws, ws_bytes, &sb)) return rc;
     for (int64_t b = 0; b < B; ++b) {
         if (int rc = smooth_bin_pose<T, NI, NO>(st, sb, P, b, points, rot, trans)) return rc;
         hipLaunchKernelGGL((k_smooth_tile<T, NI, NO>), dim3((unsigned)sb.tiles), dim3(kSmBlock), 0, st, sb.gd, sb.tl,
@@ -1056,7 +1059,7 @@ int64_t smooth_clouds_group(int n_out, const int64_t* grid, int64_t P, int64_t B
 size_t smooth_clouds_tiled_workspace_bytes(int n_out, const int64_t* grid, int64_t P, int64_t B, int max_group) {
     const int64_t bg = smooth_clouds_group(n_out, grid, P, B, max_group);
     if (bg == 0) return (size_t)-1;
-    return smooth_plan(bg * smooth_tile_count(n_out, grid, P), bg * P, (B % bg) * P).total;
+    return smooth_plan(smooth_tile_count(n_out, grid, P), P, B, bg).total;
 }
 
 template <typename T, int NI, int NO>
@@ -1084,48 +1087,29 @@ int smooth_clouds_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int
     return DPR_OK;
 }
 
-// group after group of `bg` poses: keys -> sort -> start table -> tiles, four launches per GROUP; the workspace is
-// smooth_plan of (bg * tiles, bg * P), reused from group to group (the last group may hold fewer poses)
+// group after group of sb.group poses: keys -> sort -> start table -> tiles, four launches per GROUP (the last group
+// may hold fewer poses)
 template <typename T, int NI, int NO>
 int smooth_clouds_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int max_group,
                             T* out, const T* points, const T* rot, const T* trans, const T* ow, const T* pw,
-                            void* ws_, size_t ws_bytes) {
+                            void* ws, size_t ws_bytes) {
     if (P <= 0 || B <= 0) return DPR_OK;
-    const int64_t bg = smooth_clouds_group(NO, grid, P, B, max_group);
-    if (bg == 0) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    const int64_t tiles = smooth_tile_count(NO, grid, P);
-    const SmoothPlan pl = smooth_plan(bg * tiles, bg * P, (B % bg) * P);
-    if (!ws_ || ws_bytes < pl.total)
-        return fail(DPR_ERR_WORKSPACE, "smooth clouds DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
-                    ws_ ? ws_bytes : (size_t)0);
-    char* ws = (char*)ws_;
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    const SmoothTiles<NO> tl = smooth_tiles<NO>(grid);
-    uint32_t* keys_in = (uint32_t*)(ws + pl.off_keys_in);
-    uint32_t* keys_out = (uint32_t*)(ws + pl.off_keys_out);
-    uint32_t* idx_in = (uint32_t*)(ws + pl.off_idx_in);
-    uint32_t* idx_out = (uint32_t*)(ws + pl.off_idx_out);
-    uint32_t* start = (uint32_t*)(ws + pl.off_start);
+    SmoothBinning<NO> sb;
+    if (int rc = smooth_binning<NO>(grid, G, P, B, smooth_clouds_group(NO, grid, P, B, max_group), ws, ws_bytes, &sb))
+        return rc;
     const int64_t blocks_per_pose = (P + kSmBlock - 1) / kSmBlock;
     const dim3 blk(kSmBlock);
-    for (int64_t b0 = 0; b0 < B; b0 += bg) {
-        const int64_t nb = B - b0 < bg ? B - b0 : bg;
-        const int64_t count = nb * P, entries = nb * tiles + 1;
-        const int bits = ord_key_bits((uint64_t)(nb * tiles));
+    for (int64_t b0 = 0; b0 < B; b0 += sb.group) {
+        const int64_t nb = B - b0 < sb.group ? B - b0 : sb.group;
         const T* gpts = points + b0 * P * NI;
         const T* gpw = pw ? pw + b0 * P : nullptr;
-        hipLaunchKernelGGL((k_smooth_clouds_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_pose)), blk, 0, st, gd,
-                           tl, (uint32_t)tiles, P, (uint32_t)blocks_per_pose, b0, gpts, rot, trans, keys_in, idx_in);
-        stage_mark(st);
-        DPR_HIP(radix_sort_pairs_u32(ws + pl.off_temp, pl.temp_bytes, keys_in, keys_out, idx_in, idx_out,
-                                     (size_t)count, 0u, (unsigned)bits, st));
-        stage_mark(st);
-        hipLaunchKernelGGL(k_smooth_ranges, dim3((unsigned)((entries + kSmBlock - 1) / kSmBlock)), blk, 0, st,
-                           (const uint32_t*)keys_out, (uint32_t)count, (uint64_t)entries, bits, start);
-        stage_mark(st);
-        hipLaunchKernelGGL((k_smooth_clouds_tile<T, NI, NO>), dim3((unsigned)(nb * tiles)), blk, 0, st, gd, tl,
-                           (uint32_t)tiles, (uint32_t)count, b0, out, gpts, rot, trans, ow, gpw,
-                           (const uint32_t*)start, (const uint32_t*)idx_out);
+        hipLaunchKernelGGL((k_smooth_clouds_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_pose)), blk, 0, st,
+                           sb.gd, sb.tl, (uint32_t)sb.tiles, P, (uint32_t)blocks_per_pose, b0, gpts, rot, trans,
+                           sb.keys_in, sb.idx_in);
+        if (int rc = smooth_sort_group<NO>(st, sb, nb, P)) return rc;
+        hipLaunchKernelGGL((k_smooth_clouds_tile<T, NI, NO>), dim3((unsigned)(nb * sb.tiles)), blk, 0, st, sb.gd,
+                           sb.tl, (uint32_t)sb.tiles, (uint32_t)(nb * P), b0, out, gpts, rot, trans, ow, gpw,
+                           (const uint32_t*)sb.start, (const uint32_t*)sb.idx_out);
         stage_mark(st);
     }
     DPR_HIP(hipGetLastError());
@@ -1151,7 +1135,7 @@ int smooth_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, 
                      void* ws, size_t ws_bytes) {
     if (P <= 0 || B <= 0) return DPR_OK;
     SmoothBinning<NO> sb;
-    if (int rc = smooth_binning<NO>(grid, G, P, ws, ws_bytes, &sb)) return rc;
+    if (int rc = smooth_binning<NO>(grid, G, P, B, 1, ws, ws_bytes, &sb)) return rc;
     for (int64_t b = 0; b < B; ++b) {
         if (int rc = smooth_bin_pose<T, NI, NO>(st, sb, P, b, points, rot, trans)) return rc;
         hipLaunchKernelGGL((k_smooth_tile_jvp<T, NI, NO>), dim3((unsigned)sb.tiles, (unsigned)K), dim3(kSmBlock), 0,
@@ -1208,8 +1192,10 @@ int sample_smooth_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P,
     return DPR_OK;
 }
 
-template int smooth_binning<2>(const int64_t*, int64_t, int64_t, void*, size_t, SmoothBinning<2>*);
-template int smooth_binning<3>(const int64_t*, int64_t, int64_t, void*, size_t, SmoothBinning<3>*);
+template int smooth_binning<2>(const int64_t*, int64_t, int64_t, int64_t, int64_t, void*, size_t, SmoothBinning<2>*);
+template int smooth_binning<3>(const int64_t*, int64_t, int64_t, int64_t, int64_t, void*, size_t, SmoothBinning<3>*);
+template int smooth_sort_group<2>(hipStream_t, const SmoothBinning<2>&, int64_t, int64_t);
+template int smooth_sort_group<3>(hipStream_t, const SmoothBinning<3>&, int64_t, int64_t);
 
 #define DPR_SMOOTH_INSTANTIATE(T, NI, NO)                                                                           \
     template int smooth_bin_pose<T, NI, NO>(hipStream_t, const SmoothBinning<NO>&, int64_t, int64_t, const T*,      \

@@ -1,6 +1,7 @@
 // The smooth splat of rigid bodies (include/dpr.h, "SMOOTH SPLAT, RIGID BODIES"): RIGID BODIES with the quadratic
 // B-spline weights of SMOOTH SPLAT.  Point p belongs to body[p] in [0, K) and is seen in image b through pose
-// b * K + body[p]; kernels, launches, host checks, the AUTO rule and the C ABI of the family.
+// b * K + body[p]; the kernels of the family and their launches (declared in dpr_smooth.h; host checks, AUTO rules and
+// the C ABI: dpr_api_smooth_bodies.hip).
 //
 //   DPR_ALGO_ATOMIC forward   k_smooth_bodies_fwd_atomic: k_smooth_fwd_atomic with the pose of wave_bodies /
 //                             load_body_pose (dpr_kernels_bodies.h): scalar loads where a wave's accepted lanes share
@@ -8,9 +9,9 @@
 //   DPR_ALGO_ATOMIC pullback  k_smooth_bodies_bwd: k_bodies_bwd's per-(image, body) reduction around the point term of
 //                             k_smooth_bwd (smooth_point_backward, the same operation order)
 //   DPR_ALGO_TILED forward    the images binned in GROUPS as smooth_clouds_fwd_tiled bins poses: k_smooth_bodies_keys
-//                             (key = b_local * tiles + tile, value = b_local * P + p) -> one stable radix sort ->
-//                             k_smooth_ranges -> k_smooth_bodies_tile, one workgroup per (image, tile), which takes
-//                             p = q - b_local * P, checks body[p] and gathers its pose per lane
+//                             (key = b_local * tiles + tile, value = b_local * P + p) -> smooth_sort_group (one stable
+//                             radix sort, k_smooth_ranges) -> k_smooth_bodies_tile, one workgroup per (image, tile),
+//                             which takes p = q - b_local * P, checks body[p] and gathers its pose per lane
 //   forward mode              (include/dpr.h, "SMOOTH SPLAT, RIGID BODIES, FORWARD MODE") jvp_fill, then
 //                             k_smooth_bodies_jvp_atomic, or the binning above once per group of images and
 //                             k_smooth_bodies_tile_jvp, one workgroup per (image, tile, tangent)
@@ -18,7 +19,7 @@
 // A body index outside [0, K) is checked per lane before it addresses a pose, in every kernel.
 #include <hip/hip_runtime.h>
 
-#include "dpr_host.h"
+#include "../../include/dpr.h"
 #include "dpr_jvp.h"
 #include "dpr_kernels_bodies.h"
 #include "dpr_ordered.h"
@@ -533,9 +534,9 @@ __global__ __launch_bounds__(kSmBlock) void k_smooth_bodies_tile_jvp(
 
 // ---------------------------------------------------------------- launches
 template <typename T, int NI, int NO>
-static int smooth_bodies_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out,
-                                    const T* points, const int32_t* body, const T* rot, const T* trans, const T* ow,
-                                    const T* pw) {
+int smooth_bodies_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* out,
+                             const T* points, const int32_t* body, const T* rot, const T* trans, const T* ow,
+                             const T* pw) {
     if (P <= 0 || B <= 0) return DPR_OK;
     const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)(B < 65535 ? B : 65535));
@@ -545,57 +546,58 @@ static int smooth_bodies_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t
     return DPR_OK;
 }
 
-// group after group of `bg` images: keys -> sort -> start table -> tiles, four launches per GROUP; the workspace is
-// smooth_plan of (bg * tiles, bg * P), reused from group to group (the last group may hold fewer images): the layout,
-// the group rule and the byte count of smooth_clouds_fwd_tiled
+// group after group of sb.group images: keys -> sort -> start table -> tiles, four launches per GROUP (the last group
+// may hold fewer images): the group rule, the workspace and the byte count of smooth_clouds_fwd_tiled
 template <typename T, int NI, int NO>
-static int smooth_bodies_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K,
-                                   int max_group, T* out, const T* points, const int32_t* body, const T* rot,
-                                   const T* trans, const T* ow, const T* pw, void* ws_, size_t ws_bytes) {
+int smooth_bodies_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int max_group,
+                            T* out, const T* points, const int32_t* body, const T* rot, const T* trans, const T* ow,
+                            const T* pw, void* ws, size_t ws_bytes) {
     if (P <= 0 || B <= 0) return DPR_OK;
-    const int64_t bg = smooth_clouds_group(NO, grid, P, B, max_group);
-    if (bg == 0) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    const int64_t tiles = smooth_tile_count(NO, grid, P);
-    const SmoothPlan pl = smooth_plan(bg * tiles, bg * P, (B % bg) * P);
-    if (!ws_ || ws_bytes < pl.total)
-        return fail(DPR_ERR_WORKSPACE, "smooth bodies DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
-                    ws_ ? ws_bytes : (size_t)0);
-    char* ws = (char*)ws_;
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    const SmoothTiles<NO> tl = smooth_tiles<NO>(grid);
-    uint32_t* keys_in = (uint32_t*)(ws + pl.off_keys_in);
-    uint32_t* keys_out = (uint32_t*)(ws + pl.off_keys_out);
-    uint32_t* idx_in = (uint32_t*)(ws + pl.off_idx_in);
-    uint32_t* idx_out = (uint32_t*)(ws + pl.off_idx_out);
-    uint32_t* start = (uint32_t*)(ws + pl.off_start);
+    SmoothBinning<NO> sb;
+    if (int rc = smooth_binning<NO>(grid, G, P, B, smooth_clouds_group(NO, grid, P, B, max_group), ws, ws_bytes, &sb))
+        return rc;
     const int64_t blocks_per_image = (P + kSmBlock - 1) / kSmBlock;
     const dim3 blk(kSmBlock);
-    for (int64_t b0 = 0; b0 < B; b0 += bg) {
-        const int64_t nb = B - b0 < bg ? B - b0 : bg;
-        const int64_t count = nb * P, entries = nb * tiles + 1;
-        const int bits = ord_key_bits((uint64_t)(nb * tiles));
-        hipLaunchKernelGGL((k_smooth_bodies_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_image)), blk, 0, st, gd,
-                           tl, (uint32_t)tiles, P, (uint32_t)blocks_per_image, b0, K, points, body, rot, trans,
-                           keys_in, idx_in);
-        stage_mark(st);
-        DPR_HIP(radix_sort_pairs_u32(ws + pl.off_temp, pl.temp_bytes, keys_in, keys_out, idx_in, idx_out,
-                                     (size_t)count, 0u, (unsigned)bits, st));
-        stage_mark(st);
-        if (int rc = smooth_ranges(st, keys_out, (uint32_t)count, (uint64_t)entries, bits, start)) return rc;
-        stage_mark(st);
-        hipLaunchKernelGGL((k_smooth_bodies_tile<T, NI, NO>), dim3((unsigned)(nb * tiles)), blk, 0, st, gd, tl,
-                           (uint32_t)tiles, (uint32_t)count, P, b0, K, out, points, body, rot, trans, ow, pw,
-                           (const uint32_t*)start, (const uint32_t*)idx_out);
+    for (int64_t b0 = 0; b0 < B; b0 += sb.group) {
+        const int64_t nb = B - b0 < sb.group ? B - b0 : sb.group;
+        hipLaunchKernelGGL((k_smooth_bodies_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_image)), blk, 0, st,
+                           sb.gd, sb.tl, (uint32_t)sb.tiles, P, (uint32_t)blocks_per_image, b0, K, points, body, rot,
+                           trans, sb.keys_in, sb.idx_in);
+        if (int rc = smooth_sort_group<NO>(st, sb, nb, P)) return rc;
+        hipLaunchKernelGGL((k_smooth_bodies_tile<T, NI, NO>), dim3((unsigned)(nb * sb.tiles)), blk, 0, st, sb.gd,
+                           sb.tl, (uint32_t)sb.tiles, (uint32_t)(nb * P), P, b0, K, out, points, body, rot, trans, ow,
+                           pw, (const uint32_t*)sb.start, (const uint32_t*)sb.idx_out);
         stage_mark(st);
     }
     DPR_HIP(hipGetLastError());
     return DPR_OK;
 }
 
+// Pre-zeroed by the caller: d_rot, d_trans, d_ow; with more than one slice of images d_pts and d_pw are zeroed here
+// and added with atomics (smooth_bwd_atomic's shape)
 template <typename T, int NI, int NO>
-static int smooth_bodies_jvp_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int V,
-                                    T* out_dot, const T* points, const int32_t* body, const T* rot, const T* trans,
-                                    const T* ow, const T* pw, JvpTangents<T> tan) {
+int smooth_bodies_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, const T* g,
+                             const T* points, const int32_t* body, const T* rot, const T* trans, const T* ow,
+                             const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_ow, T* d_pw, int poses_per_slice,
+                             int64_t slices) {
+    if (P <= 0 || B <= 0) return DPR_OK;
+    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
+    const int accumulate = slices > 1;
+    if (accumulate) {
+        DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * NI)));
+        if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)P));
+    }
+    dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)slices);
+    hipLaunchKernelGGL((k_smooth_bodies_bwd<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, K, g, points, body, rot,
+                       trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice, accumulate);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+template <typename T, int NI, int NO>
+int smooth_bodies_jvp_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int V,
+                             T* out_dot, const T* points, const int32_t* body, const T* rot, const T* trans,
+                             const T* ow, const T* pw, JvpTangents<T> tan) {
     if (P <= 0 || B <= 0) return DPR_OK;
     const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
     dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)(B < 65535 ? B : 65535));
@@ -608,398 +610,52 @@ static int smooth_bodies_jvp_atomic(hipStream_t st, const int64_t* grid, int64_t
 // smooth_bodies_fwd_tiled's groups, workspace and first three stages -- the keys and the sort depend on the primal
 // only -- then ONE launch of (nb * tiles) x V workgroups: four launches per group, whatever V
 template <typename T, int NI, int NO>
-static int smooth_bodies_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int V,
-                                   int max_group, T* out_dot, const T* points, const int32_t* body, const T* rot,
-                                   const T* trans, const T* ow, const T* pw, JvpTangents<T> tan, void* ws_,
-                                   size_t ws_bytes) {
+int smooth_bodies_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int V,
+                            int max_group, T* out_dot, const T* points, const int32_t* body, const T* rot,
+                            const T* trans, const T* ow, const T* pw, JvpTangents<T> tan, void* ws, size_t ws_bytes) {
     if (P <= 0 || B <= 0) return DPR_OK;
-    const int64_t bg = smooth_clouds_group(NO, grid, P, B, max_group);
-    if (bg == 0) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    const int64_t tiles = smooth_tile_count(NO, grid, P);
-    const SmoothPlan pl = smooth_plan(bg * tiles, bg * P, (B % bg) * P);
-    if (!ws_ || ws_bytes < pl.total)
-        return fail(DPR_ERR_WORKSPACE, "smooth bodies JVP DPR_ALGO_TILED needs %zu workspace bytes, got %zu", pl.total,
-                    ws_ ? ws_bytes : (size_t)0);
-    char* ws = (char*)ws_;
-    const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-    const SmoothTiles<NO> tl = smooth_tiles<NO>(grid);
-    uint32_t* keys_in = (uint32_t*)(ws + pl.off_keys_in);
-    uint32_t* keys_out = (uint32_t*)(ws + pl.off_keys_out);
-    uint32_t* idx_in = (uint32_t*)(ws + pl.off_idx_in);
-    uint32_t* idx_out = (uint32_t*)(ws + pl.off_idx_out);
-    uint32_t* start = (uint32_t*)(ws + pl.off_start);
+    SmoothBinning<NO> sb;
+    if (int rc = smooth_binning<NO>(grid, G, P, B, smooth_clouds_group(NO, grid, P, B, max_group), ws, ws_bytes, &sb))
+        return rc;
     const int64_t blocks_per_image = (P + kSmBlock - 1) / kSmBlock;
     const dim3 blk(kSmBlock);
-    for (int64_t b0 = 0; b0 < B; b0 += bg) {
-        const int64_t nb = B - b0 < bg ? B - b0 : bg;
-        const int64_t count = nb * P, entries = nb * tiles + 1;
-        const int bits = ord_key_bits((uint64_t)(nb * tiles));
-        hipLaunchKernelGGL((k_smooth_bodies_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_image)), blk, 0, st, gd,
-                           tl, (uint32_t)tiles, P, (uint32_t)blocks_per_image, b0, K, points, body, rot, trans,
-                           keys_in, idx_in);
-        stage_mark(st);
-        DPR_HIP(radix_sort_pairs_u32(ws + pl.off_temp, pl.temp_bytes, keys_in, keys_out, idx_in, idx_out,
-                                     (size_t)count, 0u, (unsigned)bits, st));
-        stage_mark(st);
-        if (int rc = smooth_ranges(st, keys_out, (uint32_t)count, (uint64_t)entries, bits, start)) return rc;
-        stage_mark(st);
-        hipLaunchKernelGGL((k_smooth_bodies_tile_jvp<T, NI, NO>), dim3((unsigned)(nb * tiles), (unsigned)V), blk, 0,
-                           st, gd, tl, (uint32_t)tiles, (uint32_t)count, P, B, b0, K, V, out_dot, points, body, rot,
-                           trans, ow, pw, tan, (const uint32_t*)start, (const uint32_t*)idx_out);
+    for (int64_t b0 = 0; b0 < B; b0 += sb.group) {
+        const int64_t nb = B - b0 < sb.group ? B - b0 : sb.group;
+        hipLaunchKernelGGL((k_smooth_bodies_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_image)), blk, 0, st,
+                           sb.gd, sb.tl, (uint32_t)sb.tiles, P, (uint32_t)blocks_per_image, b0, K, points, body, rot,
+                           trans, sb.keys_in, sb.idx_in);
+        if (int rc = smooth_sort_group<NO>(st, sb, nb, P)) return rc;
+        hipLaunchKernelGGL((k_smooth_bodies_tile_jvp<T, NI, NO>), dim3((unsigned)(nb * sb.tiles), (unsigned)V), blk,
+                           0, st, sb.gd, sb.tl, (uint32_t)sb.tiles, (uint32_t)(nb * P), P, B, b0, K, V, out_dot,
+                           points, body, rot, trans, ow, pw, tan, (const uint32_t*)sb.start,
+                           (const uint32_t*)sb.idx_out);
         stage_mark(st);
     }
     DPR_HIP(hipGetLastError());
     return DPR_OK;
 }
 
-// ---------------------------------------------------------------- host checks
-static int smooth_bodies_max_group(unsigned flags) { return (int)((flags >> 8) & 0xffu); }
-
-// AUTO (dpr_resolve_algo_smooth_bodies), from the shape alone.  The pullback is DPR_ALGO_ATOMIC.  The forward is
-// DPR_ALGO_TILED where the default GROUP of images holds bg * P >= the constant below and the cloud holds at least
-// kSmoothBodiesTiledMinPointsPerTile points per tile of the grid, DPR_ALGO_ATOMIC otherwise: the shape of
-// dpr_resolve_algo_smooth_clouds' rule, because the tiled path pays its four launches per group here too.  K does not
-// enter: TILED / ATOMIC move by less than 10 % from K = 1 to 64 and between a sorted and a shuffled cloud.  From this
-// op's own rows (profiles/smooth_bodies_probe.txt, tests/golden/smooth_bodies_auto.json; fp32, ms TILED / ATOMIC):
-//  - 3-D, 1e5 (the smooth clouds' constant, confirmed): 128^3, 1e4 x 4 images (bg * P = 4e4) 0.130 / 0.130 and
-//    0.128 / 0.114, 3e4 x 4 (1.2e5) 0.155 / 0.214, 1e4 x 16 0.235 / 0.271, 1e6 x 4 0.35 / 4.4.
-//  - 2-D, 1.6e5 (the smooth clouds' 4e5 lost this op's two lowest rows): 128^2, 1e4 x 16 (1.6e5) 0.121 / 0.144 --
-//    1.19x, beyond the 1.15 margin -- 1e4 x 32 0.176 / 0.200, 3e4 x 16 0.192 / 0.266; 512^2, 3e4 x 16 0.203 / 0.269,
-//    1e6 x 16 0.91 / 6.2.  TILED is ahead on every 2-D row measured; nothing was measured below 1.6e5.
-//  - 4 points per tile (confirmed): 256^3 (16 384 tiles), 1e4 x 16 (0.6 per tile) 0.685 / 0.426, 3e4 x 4 (1.8)
-//    0.309 / 0.244, 1e5 x 4 (6.1) 0.424 / 0.534; 128^3, 1e4 x 16 (4.9) 0.235 / 0.271.
-constexpr int64_t kSmoothBodiesTiledMinWork3D = 100000;
-constexpr int64_t kSmoothBodiesTiledMinWork2D = 160000;
-constexpr int64_t kSmoothBodiesTiledMinPointsPerTile = 4;
-static int resolve_algo_smooth_bodies(int algo, int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    if (op != DPR_OP_RASTER) return DPR_ALGO_ATOMIC;
-    const int64_t bg = smooth_clouds_group(n_out, grid, P, B, 0);
-    if (bg == 0) return DPR_ALGO_ATOMIC;
-    const int64_t min_work = n_out == 3 ? kSmoothBodiesTiledMinWork3D : kSmoothBodiesTiledMinWork2D;
-    const int64_t tiles = smooth_tile_count(n_out, grid, P);
-    return bg * P >= min_work && P / kSmoothBodiesTiledMinPointsPerTile >= tiles ? DPR_ALGO_TILED : DPR_ALGO_ATOMIC;
-}
-
-// Every refusal of the family, shared by the entry points, the workspace query and dpr_resolve_algo_smooth_bodies;
-// *G, the resolved *algo and the workspace bytes *need come back.
-static int check_smooth_bodies(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                               int64_t B, int64_t K, int64_t* G, size_t* need) {
-    // (a pair outside the three is refused before the grid is looked at)
-    if (!smooth_dims_supported(n_in, n_out))
-        return fail(DPR_ERR_UNSUPPORTED_DIMS,
-                    "smooth rigid bodies: (n_in, n_out) = (%d, %d); supports (2,2), (3,3), (3,2)", n_in, n_out);
-    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
-    if (op == DPR_OP_RESIDUAL_PULLBACK)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth rigid bodies have no residual pullback");
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
-        return fail(DPR_ERR_INVALID_ARG, "smooth bodies: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
-    if (K < 1) return fail(DPR_ERR_INVALID_ARG, "K = %lld: a call needs at least one body", (long long)K);
-    // the kernels compare a body index with K as 32-bit values and count poses b * K + k in 64 bits; the zeroing of
-    // the B * K pose gradients and their offsets stay far inside both with this bound
-    if (K > 0x7fffffffLL || (B > 0 && K > 0x7fffffffLL / B))
-        return fail(DPR_ERR_INVALID_ARG, "B * K = %lld * %lld poses exceed 2^31 - 1", (long long)B, (long long)K);
-    if ((P + kBlock - 1) / kBlock > 0x7fffffffLL) return fail(DPR_ERR_INVALID_ARG, "P too large");
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "smooth rigid bodies keep / reuse no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    if (op == DPR_OP_PULLBACK && (flags & 0xff00u))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "the smooth rigid-body pullback forms no groups of images (DPR_FLAG_MAX_POSE_GROUP)");
-    if (*algo != DPR_ALGO_AUTO && *algo != DPR_ALGO_ATOMIC && *algo != DPR_ALGO_TILED)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "smooth rigid bodies run on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d", *algo);
-    if (*algo == DPR_ALGO_TILED && op != DPR_OP_RASTER)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth rigid-body pullback runs on DPR_ALGO_ATOMIC only");
-    *algo = resolve_algo_smooth_bodies(*algo, op, n_out, grid, P, B);
-    *need = 0;
-    if (*algo == DPR_ALGO_TILED) {
-        *need = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, smooth_bodies_max_group(flags));
-        if (*need == (size_t)-1) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    }
-    return DPR_OK;
-}
-
-template <class F> static int with_smooth_dims(int n_in, int n_out, F&& f) {
-    if (n_in == 2 && n_out == 2) return f(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
-    if (n_in == 3 && n_out == 3) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
-    if (n_in == 3 && n_out == 2) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{});
-    return fail(DPR_ERR_UNSUPPORTED_DIMS, "smooth bodies: unsupported (n_in, n_out) = (%d, %d)", n_in, n_out);
-}
-
-template <typename T>
-static int raster_smooth_bodies_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                     int64_t P, int64_t B, int64_t K, T* out, const T* points, const int32_t* body,
-                                     const T* rot, const T* trans, const T* bg, const T* ow, const T* pw, void* ws,
-                                     size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_bodies(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
-    if (B == 0) return DPR_OK;
-    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
-    if (P > 0 && (!rot || !trans)) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "smooth rigid bodies (algorithm %d) need %zu workspace bytes, got %zu", algo,
-                    need, ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
-    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    fill_background(st, out, G, B, bg);
-    stage_mark(st);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_bodies_fwd_tiled<T, NI, NO>(st, grid, G, P, B, (int)K,
-                                                                smooth_bodies_max_group(flags), out, points, body, rot,
-                                                                trans, ow, pw, ws, ws_bytes)
-                           : smooth_bodies_fwd_atomic<T, NI, NO>(st, grid, G, P, B, (int)K, out, points, body, rot,
-                                                                 trans, ow, pw);
-        stage_mark(st);
-        return rc;
-    });
-}
-
-template <typename T>
-static int pullback_smooth_bodies_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
-                                       const int64_t* grid, int64_t P, int64_t B, int64_t K, const T* g,
-                                       const T* points, const int32_t* body, const T* rot, const T* trans,
-                                       const T* ow, const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow,
-                                       T* d_pw, void* ws) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_bodies(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
-    if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
-    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
-        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
-    if (B > 0) {
-        if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
-        if (!d_rot || !d_trans || !d_bg || !d_ow)
-            return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
-        if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-        if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
-        if (P > 0 && (!rot || !trans)) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL with P > 0");
-    }
-    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
-        return rc;
-    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    if (B == 0) {  // no image: the sums over the images are empty
-        if (P > 0) {
-            DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
-            if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)P));
-        }
-        return DPR_OK;
-    }
-    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * K * n_out * n_in)));
-    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * K * n_out)));
-    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
-    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)B));
-    grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
-    stage_mark(st);
-    if (P == 0) return DPR_OK;  // (the pose sums are 0, ds_dbackground is done)
-    int64_t slices = 1;
-    const int poses_per_slice = pose_slices(P, B, &slices);  // (the smooth pullback's: SUMMATION ORDER, note 1)
-    const int accumulate = slices > 1;
-    if (accumulate) {
-        DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
-        if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)P));
-    }
-    const int rc = with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const GridDesc<NO> gd = make_grid_desc<NO>(grid, G);
-        dim3 gg((unsigned)((P + kSmBlock - 1) / kSmBlock), (unsigned)slices);
-        hipLaunchKernelGGL((k_smooth_bodies_bwd<T, NI, NO>), gg, dim3(kSmBlock), 0, st, gd, P, B, (int)K, g, points,
-                           body, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice, accumulate);
-        return DPR_OK;
-    });
-    if (rc) return rc;
-    stage_mark(st);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-
-// ---------------------------------------------------------------- forward mode: host checks and entry point
-// AUTO (dpr_resolve_algo_smooth_bodies_jvp), from the shape and V alone: the forward's rule -- DPR_ALGO_TILED where the
-// default GROUP holds enough work and the cloud at least 4 points per tile -- with the group's work counted as
-// bg * P * V^2.  The rule started as the forward's with bg * P * V (what dpr_resolve_algo_smooth_jvp does with P * K);
-// this op's own rows (profiles/smooth_bodies_jvp_probe.txt, tests/golden/smooth_bodies_jvp_auto.json; fp32, K = 4,
-// ms ATOMIC / TILED) leave no constant for that product: on 128^2 1000 x 4 images at V = 12 (bg * P * V = 4.8e4) is
-// 0.111 / 0.087 -- TILED 1.28x ahead -- and 1e4 x 8 at V = 1 (8e4) 0.095 / 0.122 -- ATOMIC 1.28x ahead; on 64^3 1100 x 2 at
-// V = 12 (2.6e4) 0.205 / 0.122 against 1e4 x 4 at V = 1 (4e4, 128^3) 0.117 / 0.147.  The binning is paid once per group
-// whatever V and costs about what one tangent's atomics cost, so the bg * P from which TILED pays falls faster than
-// 1 / V: at V = 12 TILED is ahead on every row measured with 4 points per tile (down to bg * P = 2200), at V = 1 from about the forward's
-// constants on.  V^2 puts both on one side of one constant each:
-//  - 2-D, 1.6e5 (the forward's, confirmed): V = 1, 128^2, 1e4 x 12 (1.2e5) 0.111 / 0.126, 1e4 x 16 (1.6e5) 0.126 / 0.132 --
-//    1.04x behind --, 3e4 x 16 0.255 / 0.204.
-//  - 3-D, 9.6e4 (the forward's 1e5 lost this op's row 64^3, 24 000 x 4 at V = 1: 0.178 / 0.133, 1.34x): below it 1e4 x 4
-//    (4e4) 0.108 / 0.113 on 64^3 and 0.117 / 0.147 on 128^3.
-//  - 4 points per tile (confirmed): 256^3, 1e4 x 16 (0.6 per tile) 0.44 / 0.80 and 4.39 / 7.65 at V = 12, 3e4 x 4 (1.8)
-//    0.25 / 0.36 and 2.17 / 3.15, 1e5 x 4 (6.1) 0.53 / 0.49 and 5.64 / 4.06.
-// Only V = 1 and V = 12 were measured: between them the square is an interpolation.
-constexpr int64_t kSmoothBodiesJvpTiledMinWork3D = 96000;
-constexpr int64_t kSmoothBodiesJvpTiledMinWork2D = 160000;
-constexpr int64_t kSmoothBodiesJvpTiledMinPointsPerTile = 4;
-static int resolve_algo_smooth_bodies_jvp(int algo, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t V) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    const int64_t bg = smooth_clouds_group(n_out, grid, P, B, 0);
-    if (bg == 0) return DPR_ALGO_ATOMIC;
-    const int64_t min_work = n_out == 3 ? kSmoothBodiesJvpTiledMinWork3D : kSmoothBodiesJvpTiledMinWork2D;
-    const int64_t tiles = smooth_tile_count(n_out, grid, P);
-    // (bg * P <= 2^24 for bg > 1, P < 2^32 for bg = 1, V <= 16: the product stays inside 64 bits)
-    return bg * P * V * V >= min_work && P / kSmoothBodiesJvpTiledMinPointsPerTile >= tiles ? DPR_ALGO_TILED
-                                                                                          : DPR_ALGO_ATOMIC;
-}
-
-// Every refusal of the forward-mode entry points, shared by them, the workspace query and
-// dpr_resolve_algo_smooth_bodies_jvp; *G, the resolved *algo and the workspace bytes *need come back.
-static int check_smooth_bodies_jvp(int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                                   int64_t B, int64_t K, int64_t V, int64_t* G, size_t* need) {
-    if (!smooth_dims_supported(n_in, n_out))
-        return fail(DPR_ERR_UNSUPPORTED_DIMS,
-                    "smooth rigid bodies, forward mode: (n_in, n_out) = (%d, %d); supports (2,2), (3,3), (3,2)", n_in,
-                    n_out);
-    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
-    if (K < 1) return fail(DPR_ERR_INVALID_ARG, "K = %lld: a call needs at least one body", (long long)K);
-    if (K > 0x7fffffffLL || (B > 0 && K > 0x7fffffffLL / B))
-        return fail(DPR_ERR_INVALID_ARG, "B * K = %lld * %lld poses exceed 2^31 - 1", (long long)B, (long long)K);
-    if (int rc = check_jvp(V, flags)) return rc;  // (V in 1 .. kMaxTangents; KEEP / REUSE refused)
-    if (int rc = check_sample_sizes(P, B, *G)) return rc;
-    if (B > 0 && *G * V > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "output too large");
-    if (*algo != DPR_ALGO_AUTO && *algo != DPR_ALGO_ATOMIC && *algo != DPR_ALGO_TILED)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "the smooth rigid-body JVP runs on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d", *algo);
-    *algo = resolve_algo_smooth_bodies_jvp(*algo, n_out, grid, P, B, V);
-    *need = 0;
-    if (*algo == DPR_ALGO_TILED) {
-        *need = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, smooth_bodies_max_group(flags));
-        if (*need == (size_t)-1) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    }
-    return DPR_OK;
-}
-
-template <typename T>
-static int raster_smooth_bodies_jvp_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
-                                         const int64_t* grid, int64_t P, int64_t B, int64_t K, int64_t V, T* out_dot,
-                                         const T* points, const int32_t* body, const T* rot, const T* trans,
-                                         const T* ow, const T* pw, JvpTangents<T> tan, const T* bg_dot, void* ws,
-                                         size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_bodies_jvp(&algo, flags, n_in, n_out, grid, P, B, K, V, &G, &need)) return rc;
-    if (B == 0) return DPR_OK;
-    if (!out_dot) return fail(DPR_ERR_INVALID_ARG, "out_dot is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
-    if (P > 0 && (!rot || !trans)) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "smooth rigid bodies JVP (algorithm %d) needs %zu workspace bytes, got %zu",
-                    algo, need, ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out_dot, points, rot, trans, ow, pw, tan.points, tan.rot, tan.trans, tan.ow,
-                                         tan.pw, bg_dot}))
-        return rc;
-    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    // the background tangent (or 0) into every plane; then the deposits, where any other tangent is given
-    jvp_fill(st, out_dot, G, (int)V, B, bg_dot);
-    stage_mark(st);
-    DPR_HIP(hipGetLastError());
-    if (P == 0 || !(tan.points || tan.rot || tan.trans || tan.ow || tan.pw)) return DPR_OK;
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_bodies_jvp_tiled<T, NI, NO>(st, grid, G, P, B, (int)K, (int)V,
-                                                                smooth_bodies_max_group(flags), out_dot, points, body,
-                                                                rot, trans, ow, pw, tan, ws, ws_bytes)
-                           : smooth_bodies_jvp_atomic<T, NI, NO>(st, grid, G, P, B, (int)K, (int)V, out_dot, points,
-                                                                 body, rot, trans, ow, pw, tan);
-        stage_mark(st);
-        return rc;
-    });
-}
+#define DPR_SMOOTH_BODIES_INSTANTIATE(T, NI, NO)                                                                     \
+    template int smooth_bodies_fwd_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, int,    \
+                                                     T*, const T*, const int32_t*, const T*, const T*, const T*,    \
+                                                     const T*);                                                     \
+    template int smooth_bodies_fwd_tiled<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, int,     \
+                                                    int, T*, const T*, const int32_t*, const T*, const T*,          \
+                                                    const T*, const T*, void*, size_t);                             \
+    template int smooth_bodies_bwd_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, int,    \
+                                                     const T*, const T*, const int32_t*, const T*, const T*,        \
+                                                     const T*, const T*, T*, T*, T*, T*, T*, int, int64_t);         \
+    template int smooth_bodies_jvp_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, int,    \
+                                                     int, T*, const T*, const int32_t*, const T*, const T*,         \
+                                                     const T*, const T*, JvpTangents<T>);                           \
+    template int smooth_bodies_jvp_tiled<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, int,     \
+                                                    int, int, T*, const T*, const int32_t*, const T*, const T*,     \
+                                                    const T*, const T*, JvpTangents<T>, void*, size_t);
+#define DPR_SMOOTH_BODIES_INSTANTIATE_T(T)                                           \
+    DPR_SMOOTH_BODIES_INSTANTIATE(T, 2, 2) DPR_SMOOTH_BODIES_INSTANTIATE(T, 3, 3) \
+    DPR_SMOOTH_BODIES_INSTANTIATE(T, 3, 2)
+DPR_SMOOTH_BODIES_INSTANTIATE_T(float)
+DPR_SMOOTH_BODIES_INSTANTIATE_T(double)
 
 }  // namespace dpr
 
-extern "C" {
-
-int dpr_resolve_algo_smooth_bodies(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
-                                   int64_t K) {
-    int64_t G = 0;
-    size_t need = 0;
-    int algo = DPR_ALGO_AUTO;
-    if (int rc = dpr::check_smooth_bodies(op, &algo, 0u, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
-    return algo;
-}
-
-#define DPR_DEFINE_SMOOTH_BODIES(SUF, T)                                                                          \
-    size_t dpr_workspace_bytes_smooth_bodies_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,      \
-                                                      const int64_t* grid, int64_t P, int64_t B, int64_t K) {     \
-        int64_t G = 0;                                                                                            \
-        size_t need = 0;                                                                                          \
-        return dpr::check_smooth_bodies(op, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need) ? (size_t)-1     \
-                                                                                                  : need;         \
-    }                                                                                                             \
-    int dpr_raster_smooth_bodies_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,            \
-                                          const int64_t* grid, int64_t P, int64_t B, int64_t K, T* out,           \
-                                          const T* points, const void* body, const T* rotation,                   \
-                                          const T* translation, const T* background, const T* out_weight,         \
-                                          const T* point_weight, void* workspace, size_t workspace_bytes) {       \
-        return dpr::raster_smooth_bodies_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, K, out, points,    \
-                                                 (const int32_t*)body, rotation, translation, background,         \
-                                                 out_weight, point_weight, workspace, workspace_bytes);           \
-    }                                                                                                             \
-    int dpr_raster_pullback_smooth_bodies_ex_##SUF(                                                               \
-        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,   \
-        int64_t K, const T* ds_dout, const T* points, const void* body, const T* rotation, const T* translation,  \
-        const T* out_weight, const T* point_weight, T* ds_dpoints, T* ds_drotation, T* ds_dtranslation,           \
-        T* ds_dbackground, T* ds_dout_weight, T* ds_dpoint_weight, void* workspace, size_t workspace_bytes) {     \
-        (void)workspace_bytes;                                                                                    \
-        return dpr::pullback_smooth_bodies_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, K, ds_dout,      \
-                                                   points, (const int32_t*)body, rotation, translation,           \
-                                                   out_weight, point_weight, ds_dpoints, ds_drotation,            \
-                                                   ds_dtranslation, ds_dbackground, ds_dout_weight,               \
-                                                   ds_dpoint_weight, workspace);                                  \
-    }
-DPR_DEFINE_SMOOTH_BODIES(f32, float)
-DPR_DEFINE_SMOOTH_BODIES(f64, double)
-#undef DPR_DEFINE_SMOOTH_BODIES
-
-int dpr_resolve_algo_smooth_bodies_jvp(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t K,
-                                       int64_t V) {
-    int64_t G = 0;
-    size_t need = 0;
-    int algo = DPR_ALGO_AUTO;
-    if (int rc = dpr::check_smooth_bodies_jvp(&algo, 0u, n_in, n_out, grid, P, B, K, V, &G, &need)) return rc;
-    return algo;
-}
-
-#define DPR_DEFINE_SMOOTH_BODIES_JVP(SUF, T)                                                                      \
-    size_t dpr_workspace_bytes_smooth_bodies_jvp_ex_##SUF(int algo, unsigned flags, int n_in, int n_out,          \
-                                                          const int64_t* grid, int64_t P, int64_t B, int64_t K,   \
-                                                          int64_t V) {                                            \
-        int64_t G = 0;                                                                                            \
-        size_t need = 0;                                                                                          \
-        return dpr::check_smooth_bodies_jvp(&algo, flags, n_in, n_out, grid, P, B, K, V, &G, &need) ? (size_t)-1  \
-                                                                                                     : need;      \
-    }                                                                                                             \
-    int dpr_raster_smooth_bodies_jvp_ex_##SUF(                                                                    \
-        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,   \
-        int64_t K, int64_t V, T* out_dot, const T* points, const void* body, const T* rotation,                   \
-        const T* translation, const T* out_weight, const T* point_weight, const T* points_dot,                    \
-        const T* rotation_dot, const T* translation_dot, const T* background_dot, const T* out_weight_dot,        \
-        const T* point_weight_dot, void* workspace, size_t workspace_bytes) {                                     \
-        return dpr::raster_smooth_bodies_jvp_impl<T>(                                                             \
-            stream, algo, flags, n_in, n_out, grid, P, B, K, V, out_dot, points, (const int32_t*)body, rotation,  \
-            translation, out_weight, point_weight,                                                                \
-            dpr::JvpTangents<T>{points_dot, rotation_dot, translation_dot, out_weight_dot, point_weight_dot},     \
-            background_dot, workspace, workspace_bytes);                                                          \
-    }
-DPR_DEFINE_SMOOTH_BODIES_JVP(f32, float)
-DPR_DEFINE_SMOOTH_BODIES_JVP(f64, double)
-#undef DPR_DEFINE_SMOOTH_BODIES_JVP
-
-}  // extern "C"

@@ -398,7 +398,7 @@ int smooth_channels_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, in
                               size_t ws_bytes) {
     if (P <= 0 || B <= 0) return DPR_OK;
     SmoothBinning<NO> sb;
-    if (int rc = smooth_binning<NO>(grid, G, P, ws, ws_bytes, &sb)) return rc;
+    if (int rc = smooth_binning<NO>(grid, G, P, B, 1, ws, ws_bytes, &sb)) return rc;
     const dim3 tgrid((unsigned)sb.tiles, (unsigned)((C + kSmChTile - 1) / kSmChTile));  // (y <= kMaxChannels)
     for (int64_t b = 0; b < B; ++b) {
         if (int rc = smooth_bin_pose<T, NI, NO>(st, sb, P, b, points, rot, trans)) return rc;

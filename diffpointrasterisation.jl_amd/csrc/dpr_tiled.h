@@ -20,6 +20,9 @@ int fail(int code, const char* fmt, ...);
             return fail(DPR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// n of DPR_FLAG_MAX_POSE_GROUP(n) (include/dpr.h: bits 8 .. 15 of the flags; 0: the library's limit)
+inline int max_pose_group(unsigned flags) { return (int)((flags >> 8) & 0xffu); }
+
 // workspace pieces start on 256-byte boundaries
 inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 

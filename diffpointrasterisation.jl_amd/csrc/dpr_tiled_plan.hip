@@ -93,7 +93,7 @@ PlanRequest plan_request(size_t elem, int op, unsigned flags, int n_in, int n_ou
     rq.tiles = slab_max_tiles(sc);
     rq.P = P;
     rq.B = B;
-    rq.max_group = (int)((flags >> 8) & 0xffu);
+    rq.max_group = max_pose_group(flags);
     rq.coherent = (flags & DPR_FLAG_COHERENT_POINTS) != 0;
     rq.share_batch = (flags & 3u) != 0;
     rq.slabbed = sc.nslab > 1;
