@@ -34,6 +34,8 @@ from .smooth_bodies import (raster_pullback_smooth_bodies_, raster_smooth_bodies
                             raster_smooth_bodies_ad, resolve_algo_smooth_bodies)
 from .smooth_bodies_jvp import (raster_smooth_bodies_jvp, raster_smooth_bodies_jvp_,
                                 resolve_algo_smooth_bodies_jvp)
+from .sample_smooth_bodies import (resolve_algo_sample_smooth_bodies, sample_smooth_bodies, sample_smooth_bodies_,
+                                   sample_smooth_bodies_ad, sample_smooth_bodies_pullback_)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -63,4 +65,6 @@ __all__ = [
     "raster_smooth_bodies", "raster_smooth_bodies_", "raster_pullback_smooth_bodies_", "raster_smooth_bodies_ad",
     "resolve_algo_smooth_bodies",
     "raster_smooth_bodies_jvp", "raster_smooth_bodies_jvp_", "resolve_algo_smooth_bodies_jvp",
+    "sample_smooth_bodies", "sample_smooth_bodies_", "sample_smooth_bodies_pullback_", "sample_smooth_bodies_ad",
+    "resolve_algo_sample_smooth_bodies",
 ]

@@ -88,6 +88,10 @@ EXPORTS = [
     "dpr_resolve_algo_smooth_bodies_jvp", "dpr_workspace_bytes_smooth_bodies_jvp_ex_f32",
     "dpr_workspace_bytes_smooth_bodies_jvp_ex_f64", "dpr_raster_smooth_bodies_jvp_ex_f32",
     "dpr_raster_smooth_bodies_jvp_ex_f64",
+    "dpr_resolve_algo_sample_smooth_bodies", "dpr_workspace_bytes_sample_smooth_bodies_ex_f32",
+    "dpr_workspace_bytes_sample_smooth_bodies_ex_f64", "dpr_sample_smooth_bodies_ex_f32",
+    "dpr_sample_smooth_bodies_ex_f64", "dpr_sample_smooth_bodies_pullback_ex_f32",
+    "dpr_sample_smooth_bodies_pullback_ex_f64",
 ]
 
 _lib = None
@@ -325,6 +329,20 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, f"dpr_raster_smooth_bodies_jvp_ex_{suf}")
         f.restype = i
         f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64, i64] + [vp] * 13 + [vp, sz]
+    L.dpr_resolve_algo_sample_smooth_bodies.restype = i
+    L.dpr_resolve_algo_sample_smooth_bodies.argtypes = [i, i, i, vp, i64, i64, i64]
+    for suf in ("f32", "f64"):
+        f = getattr(L, f"dpr_workspace_bytes_sample_smooth_bodies_ex_{suf}")
+        f.restype = sz
+        f.argtypes = [i, i, ctypes.c_uint, i, i, vp, i64, i64, i64]
+        # stream, algo, flags, n_in, n_out, grid, P, B, K, values, image, points, body, rot, trans, ws, ws_bytes
+        f = getattr(L, f"dpr_sample_smooth_bodies_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 6 + [vp, sz]
+        # ..., K, ds_dvalues, image, points, body, rot, trans, ds_dimage, ds_dpoints, ds_drot, ds_dtrans, ws, ws_bytes
+        f = getattr(L, f"dpr_sample_smooth_bodies_pullback_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 10 + [vp, sz]
     L.dpr_comm_unique_id.restype = i
     L.dpr_comm_unique_id.argtypes = [vp, sz]
     L.dpr_comm_init.restype = i

@@ -1,6 +1,7 @@
-// The smooth rigid-body entry points of libdpr -- splat, pullback and forward mode: host checks, AUTO rules and C ABI
-// (include/dpr.h, "SMOOTH SPLAT, RIGID BODIES" and "SMOOTH SPLAT, RIGID BODIES, FORWARD MODE"; core: dpr_api.hip;
-// kernels and their launches: dpr_smooth_bodies.hip).
+// The smooth rigid-body entry points of libdpr -- splat, pullback, forward mode and sampling: host checks, AUTO rules
+// and C ABI (include/dpr.h, "SMOOTH SPLAT, RIGID BODIES", "SMOOTH SPLAT, RIGID BODIES, FORWARD MODE" and "SMOOTH
+// SAMPLING, RIGID BODIES"; core: dpr_api.hip; kernels and their launches: dpr_smooth_bodies.hip,
+// dpr_sample_smooth_bodies.hip).
 #include <hip/hip_runtime.h>
 
 #include "dpr_host.h"
@@ -259,9 +260,179 @@ static int raster_smooth_bodies_jvp_impl(void* stream, int algo, unsigned flags,
     });
 }
 
+// ---------------------------------------------------------------- smooth sampling at the points of rigid bodies
+// dpr_sample_smooth_bodies_ex_* / dpr_sample_smooth_bodies_pullback_ex_* (include/dpr.h, "SMOOTH SAMPLING, RIGID
+// BODIES"; kernels: dpr_sample_smooth_bodies.hip).  Forward: DPR_ALGO_ATOMIC.  Pullback: DPR_ALGO_ATOMIC, the fused
+// point kernel with image atomics; DPR_ALGO_TILED, the same kernel without them, then ds_dimage group by group of
+// images through the binning of the tiled smooth rigid-body forward.
+// AUTO: the forward is ATOMIC; the pullback is TILED exactly where the smooth rigid-body forward of the shape would
+// be (resolve_algo_smooth_bodies above; dpr_resolve_algo_sample_smooth's precedent).
+static int resolve_algo_sample_smooth_bodies(int algo, int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
+    if (algo != DPR_ALGO_AUTO) return algo;
+    if (op != DPR_OP_PULLBACK) return DPR_ALGO_ATOMIC;
+    return resolve_algo_smooth_bodies(DPR_ALGO_AUTO, DPR_OP_RASTER, n_out, grid, P, B);
+}
+
+// Every refusal of the family, shared by the entry points, the workspace query and
+// dpr_resolve_algo_sample_smooth_bodies; *G, the resolved *algo and the workspace bytes *need come back.
+static int check_sample_smooth_bodies(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                      int64_t P, int64_t B, int64_t K, int64_t* G, size_t* need) {
+    if (!smooth_dims_supported(n_in, n_out))
+        return fail(DPR_ERR_UNSUPPORTED_DIMS,
+                    "smooth rigid-body sampling: (n_in, n_out) = (%d, %d); supports (2,2), (3,3), (3,2)", n_in, n_out);
+    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
+    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
+        return fail(DPR_ERR_INVALID_ARG, "smooth rigid-body sampling: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK",
+                    op);
+    if (K < 1) return fail(DPR_ERR_INVALID_ARG, "K = %lld: a call needs at least one body", (long long)K);
+    if (K > 0x7fffffffLL || (B > 0 && K > 0x7fffffffLL / B))  // (check_smooth_bodies' bound, for its reasons)
+        return fail(DPR_ERR_INVALID_ARG, "B * K = %lld * %lld poses exceed 2^31 - 1", (long long)B, (long long)K);
+    if (int rc = check_point_blocks(P)) return rc;
+    if (flags & 3u)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "smooth rigid-body sampling keeps / reuses no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
+    if (*algo != DPR_ALGO_AUTO && *algo != DPR_ALGO_ATOMIC && *algo != DPR_ALGO_TILED)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "smooth rigid-body sampling runs on DPR_ALGO_ATOMIC and, the pullback, DPR_ALGO_TILED, not "
+                    "algorithm %d", *algo);
+    if (*algo == DPR_ALGO_TILED && op != DPR_OP_PULLBACK)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth rigid-body sampling forward runs on DPR_ALGO_ATOMIC only");
+    *algo = resolve_algo_sample_smooth_bodies(*algo, op, n_out, grid, P, B);
+    if ((flags & 0xff00u) && *algo != DPR_ALGO_TILED)
+        return fail(DPR_ERR_UNSUPPORTED_ALGO,
+                    "smooth rigid-body sampling forms groups of images on the DPR_ALGO_TILED pullback only "
+                    "(DPR_FLAG_MAX_POSE_GROUP)");
+    *need = 0;
+    if (*algo == DPR_ALGO_TILED) {
+        *need = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, max_pose_group(flags));
+        if (*need == (size_t)-1) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
+    }
+    return check_sample_sizes(P, B, *G);
+}
+
+template <typename T>
+static int sample_smooth_bodies_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                     int64_t P, int64_t B, int64_t K, T* values, const T* image, const T* points,
+                                     const int32_t* body, const T* rot, const T* trans, void* ws) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_sample_smooth_bodies(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need))
+        return rc;
+    if (P == 0 || B == 0) return DPR_OK;
+    if (!values) return fail(DPR_ERR_INVALID_ARG, "values is NULL");
+    if (!image) return fail(DPR_ERR_INVALID_ARG, "image is NULL");
+    if (!points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (!body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
+    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+    if (int rc = check_alignment<T>(ws, {values, image, points, rot, trans})) return rc;
+    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    int64_t slices = 1;
+    const int pps = pose_slices(P, B, &slices);
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        const int rc = sample_smooth_bodies_fwd<T, decltype(ni)::value, decltype(no)::value>(
+            st, grid, G, P, B, (int)K, values, image, points, body, rot, trans, pps, slices);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+template <typename T>
+static int sample_smooth_bodies_pullback_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
+                                              const int64_t* grid, int64_t P, int64_t B, int64_t K, const T* dv,
+                                              const T* image, const T* points, const int32_t* body, const T* rot,
+                                              const T* trans, T* d_img, T* d_pts, T* d_rot, T* d_trans, void* ws,
+                                              size_t ws_bytes) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_sample_smooth_bodies(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need))
+        return rc;
+    if (!d_img && !d_pts && !d_rot && !d_trans)
+        return fail(DPR_ERR_INVALID_ARG, "smooth rigid-body sampling pullback: every output is NULL");
+    const bool tiled = algo == DPR_ALGO_TILED;
+    if (tiled && d_img && P > 0 && B > 0 && need > 0 && (!ws || ws_bytes < need))
+        return fail(DPR_ERR_WORKSPACE,
+                    "DPR_ALGO_TILED smooth rigid-body sampling pullback needs %zu workspace bytes, got %zu", need,
+                    ws ? ws_bytes : (size_t)0);
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
+    if (P > 0 && B > 0) {
+        if (!dv) return fail(DPR_ERR_INVALID_ARG, "ds_dvalues is NULL");
+        if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+        if ((d_pts || d_rot || d_trans) && !image)
+            return fail(DPR_ERR_INVALID_ARG, "image is NULL (needed for ds_dpoints / ds_drotation / ds_dtranslation)");
+    }
+    if (int rc = check_alignment<T>(ws, {dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans})) return rc;
+    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    if (d_rot) DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * K * n_out * n_in)));
+    if (d_trans) DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * K * n_out)));
+    if (d_img) DPR_HIP(zero_async(st, d_img, sizeof(T) * (size_t)(B * G)));
+    if (d_pts && B == 0) DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
+    if (P == 0 || B == 0) return DPR_OK;
+    int64_t slices = 1;
+    const int pps = pose_slices(P, B, &slices);
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        if (int rc = sample_smooth_bodies_bwd<T, NI, NO>(st, grid, G, P, B, (int)K, dv, image, points, body, rot,
+                                                         trans, tiled ? nullptr : d_img, d_pts, d_rot, d_trans, pps,
+                                                         slices))
+            return rc;
+        stage_mark(st);
+        if (tiled && d_img)  // (the planes are zeroed above)
+            return sample_smooth_bodies_image_tiled<T, NI, NO>(st, grid, G, P, B, (int)K, max_pose_group(flags),
+                                                               d_img, dv, points, body, rot, trans, ws, ws_bytes);
+        return DPR_OK;
+    });
+}
+
 }  // namespace dpr
 
 extern "C" {
+
+int dpr_resolve_algo_sample_smooth_bodies(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
+                                          int64_t K) {
+    int64_t G = 0;
+    size_t need = 0;
+    int algo = DPR_ALGO_AUTO;
+    if (int rc = dpr::check_sample_smooth_bodies(op, &algo, 0u, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
+    return algo;
+}
+
+#define DPR_DEFINE_SAMPLE_SMOOTH_BODIES(SUF, T)                                                                     \
+    size_t dpr_workspace_bytes_sample_smooth_bodies_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out, \
+                                                             const int64_t* grid, int64_t P, int64_t B,             \
+                                                             int64_t K) {                                           \
+        int64_t G = 0;                                                                                              \
+        size_t need = 0;                                                                                            \
+        return dpr::check_sample_smooth_bodies(op, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need)             \
+                   ? (size_t)-1                                                                                     \
+                   : need;                                                                                          \
+    }                                                                                                               \
+    int dpr_sample_smooth_bodies_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,              \
+                                          const int64_t* grid, int64_t P, int64_t B, int64_t K, T* values,          \
+                                          const T* image, const T* points, const void* body, const T* rotation,     \
+                                          const T* translation, void* workspace, size_t workspace_bytes) {          \
+        (void)workspace_bytes;                                                                                      \
+        return dpr::sample_smooth_bodies_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, K, values, image,    \
+                                                 points, (const int32_t*)body, rotation, translation, workspace);   \
+    }                                                                                                               \
+    int dpr_sample_smooth_bodies_pullback_ex_##SUF(                                                                 \
+        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,     \
+        int64_t K, const T* ds_dvalues, const T* image, const T* points, const void* body, const T* rotation,       \
+        const T* translation, T* ds_dimage, T* ds_dpoints, T* ds_drotation, T* ds_dtranslation, void* workspace,    \
+        size_t workspace_bytes) {                                                                                   \
+        return dpr::sample_smooth_bodies_pullback_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, K,          \
+                                                          ds_dvalues, image, points, (const int32_t*)body,          \
+                                                          rotation, translation, ds_dimage, ds_dpoints,             \
+                                                          ds_drotation, ds_dtranslation, workspace,                 \
+                                                          workspace_bytes);                                         \
+    }
+DPR_DEFINE_SAMPLE_SMOOTH_BODIES(f32, float)
+DPR_DEFINE_SAMPLE_SMOOTH_BODIES(f64, double)
+#undef DPR_DEFINE_SAMPLE_SMOOTH_BODIES
 
 int dpr_resolve_algo_smooth_bodies(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
                                    int64_t K) {

@@ -1,6 +1,7 @@
 // The smooth splat (include/dpr.h, "SMOOTH SPLAT"): quadratic B-spline weights on 3^N cells per point.
 // Index arithmetic shared by the host plan and the kernels of dpr_smooth.hip, and the launchers of dpr_smooth.hip,
-// dpr_smooth_channels.hip and dpr_smooth_bodies.hip that dpr_api_smooth.hip and dpr_api_smooth_bodies.hip call.
+// dpr_smooth_channels.hip, dpr_smooth_bodies.hip and dpr_sample_smooth_bodies.hip that dpr_api_smooth.hip and
+// dpr_api_smooth_bodies.hip call.
 #pragma once
 #include <type_traits>
 
@@ -175,6 +176,11 @@ template <typename T, int NI, int NO>
 int smooth_bodies_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, int max_group,
                             T* out, const T* points, const int32_t* body, const T* rot, const T* trans, const T* ow,
                             const T* pw, void* ws, size_t ws_bytes);
+// the binning of the images b0 .. b0 + nb - 1 (k_smooth_bodies_keys, then smooth_sort_group): what the tiled launchers
+// of dpr_smooth_bodies.hip and of dpr_sample_smooth_bodies.hip run before their tile kernels
+template <typename T, int NI, int NO>
+int smooth_bodies_bin_group(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int64_t b0, int64_t nb, int K,
+                            const T* points, const int32_t* body, const T* rot, const T* trans);
 template <typename T, int NI, int NO>
 int smooth_bodies_bwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, const T* g,
                              const T* points, const int32_t* body, const T* rot, const T* trans, const T* ow,
@@ -200,5 +206,23 @@ template <typename T, int NI, int NO>
 int sample_smooth_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* dv,
                       const T* image, const T* points, const T* rot, const T* trans, T* d_img, T* d_pts, T* d_rot,
                       T* d_trans, int poses_per_slice, int64_t slices);
+
+// Smooth sampling at the points of rigid bodies (include/dpr.h, "SMOOTH SAMPLING, RIGID BODIES"; kernels:
+// dpr_sample_smooth_bodies.hip): smooth sampling through pose b * K + body[p].  The same contract with the caller
+// (dpr_api_smooth_bodies.hip) as sample_smooth_fwd / sample_smooth_bwd; d_rot and d_trans hold B * K poses.
+// sample_smooth_bodies_image_tiled adds ds_dimage onto zeroed planes: the images binned in groups as
+// smooth_bodies_fwd_tiled bins them, with its workspace, the weight of (point, image) read from dv.
+template <typename T, int NI, int NO>
+int sample_smooth_bodies_fwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, T* values,
+                             const T* image, const T* points, const int32_t* body, const T* rot, const T* trans,
+                             int poses_per_slice, int64_t slices);
+template <typename T, int NI, int NO>
+int sample_smooth_bodies_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K, const T* dv,
+                             const T* image, const T* points, const int32_t* body, const T* rot, const T* trans,
+                             T* d_img, T* d_pts, T* d_rot, T* d_trans, int poses_per_slice, int64_t slices);
+template <typename T, int NI, int NO>
+int sample_smooth_bodies_image_tiled(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int K,
+                                     int max_group, T* d_img, const T* dv, const T* points, const int32_t* body,
+                                     const T* rot, const T* trans, void* ws, size_t ws_bytes);
 
 }  // namespace dpr

@@ -24,7 +24,8 @@
 //                             cloud b; a thread per (point, pose); the tiled forward bins a GROUP of poses with one
 //                             key pass, one sort, one start table and one launch of (poses x tiles) workgroups
 //   host side of the binning  smooth_plan (the workspace), smooth_binning, smooth_sort_group, smooth_bin_pose: one copy
-//                             for every tiled launcher here, in dpr_smooth_channels.hip and in dpr_smooth_bodies.hip
+//                             for every tiled launcher here, in dpr_smooth_channels.hip, in dpr_smooth_bodies.hip and
+//                             in dpr_sample_smooth_bodies.hip
 #include <hip/hip_runtime.h>
 
 #include "../../include/dpr.h"

@@ -546,6 +546,18 @@ int smooth_bodies_fwd_atomic(hipStream_t st, const int64_t* grid, int64_t G, int
     return DPR_OK;
 }
 
+// The binning of the group of nb images b0 .. b0 + nb - 1: k_smooth_bodies_keys, then smooth_sort_group.  Depends on
+// the primal only; afterwards sb.start / sb.idx_out hold the runs of the group's (image, tile) pairs.
+template <typename T, int NI, int NO>
+int smooth_bodies_bin_group(hipStream_t st, const SmoothBinning<NO>& sb, int64_t P, int64_t b0, int64_t nb, int K,
+                            const T* points, const int32_t* body, const T* rot, const T* trans) {
+    const int64_t blocks_per_image = (P + kSmBlock - 1) / kSmBlock;
+    hipLaunchKernelGGL((k_smooth_bodies_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_image)), dim3(kSmBlock), 0,
+                       st, sb.gd, sb.tl, (uint32_t)sb.tiles, P, (uint32_t)blocks_per_image, b0, K, points, body, rot,
+                       trans, sb.keys_in, sb.idx_in);
+    return smooth_sort_group<NO>(st, sb, nb, P);
+}
+
 // group after group of sb.group images: keys -> sort -> start table -> tiles, four launches per GROUP (the last group
 // may hold fewer images): the group rule, the workspace and the byte count of smooth_clouds_fwd_tiled
 template <typename T, int NI, int NO>
@@ -556,14 +568,10 @@ int smooth_bodies_fwd_tiled(hipStream_t st, const int64_t* grid, int64_t G, int6
     SmoothBinning<NO> sb;
     if (int rc = smooth_binning<NO>(grid, G, P, B, smooth_clouds_group(NO, grid, P, B, max_group), ws, ws_bytes, &sb))
         return rc;
-    const int64_t blocks_per_image = (P + kSmBlock - 1) / kSmBlock;
     const dim3 blk(kSmBlock);
     for (int64_t b0 = 0; b0 < B; b0 += sb.group) {
         const int64_t nb = B - b0 < sb.group ? B - b0 : sb.group;
-        hipLaunchKernelGGL((k_smooth_bodies_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_image)), blk, 0, st,
-                           sb.gd, sb.tl, (uint32_t)sb.tiles, P, (uint32_t)blocks_per_image, b0, K, points, body, rot,
-                           trans, sb.keys_in, sb.idx_in);
-        if (int rc = smooth_sort_group<NO>(st, sb, nb, P)) return rc;
+        if (int rc = smooth_bodies_bin_group<T, NI, NO>(st, sb, P, b0, nb, K, points, body, rot, trans)) return rc;
         hipLaunchKernelGGL((k_smooth_bodies_tile<T, NI, NO>), dim3((unsigned)(nb * sb.tiles)), blk, 0, st, sb.gd,
                            sb.tl, (uint32_t)sb.tiles, (uint32_t)(nb * P), P, b0, K, out, points, body, rot, trans, ow,
                            pw, (const uint32_t*)sb.start, (const uint32_t*)sb.idx_out);
@@ -617,14 +625,10 @@ int smooth_bodies_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int6
     SmoothBinning<NO> sb;
     if (int rc = smooth_binning<NO>(grid, G, P, B, smooth_clouds_group(NO, grid, P, B, max_group), ws, ws_bytes, &sb))
         return rc;
-    const int64_t blocks_per_image = (P + kSmBlock - 1) / kSmBlock;
     const dim3 blk(kSmBlock);
     for (int64_t b0 = 0; b0 < B; b0 += sb.group) {
         const int64_t nb = B - b0 < sb.group ? B - b0 : sb.group;
-        hipLaunchKernelGGL((k_smooth_bodies_keys<T, NI, NO>), dim3((unsigned)(nb * blocks_per_image)), blk, 0, st,
-                           sb.gd, sb.tl, (uint32_t)sb.tiles, P, (uint32_t)blocks_per_image, b0, K, points, body, rot,
-                           trans, sb.keys_in, sb.idx_in);
-        if (int rc = smooth_sort_group<NO>(st, sb, nb, P)) return rc;
+        if (int rc = smooth_bodies_bin_group<T, NI, NO>(st, sb, P, b0, nb, K, points, body, rot, trans)) return rc;
         hipLaunchKernelGGL((k_smooth_bodies_tile_jvp<T, NI, NO>), dim3((unsigned)(nb * sb.tiles), (unsigned)V), blk,
                            0, st, sb.gd, sb.tl, (uint32_t)sb.tiles, (uint32_t)(nb * P), P, B, b0, K, V, out_dot,
                            points, body, rot, trans, ow, pw, tan, (const uint32_t*)sb.start,
@@ -636,6 +640,8 @@ int smooth_bodies_jvp_tiled(hipStream_t st, const int64_t* grid, int64_t G, int6
 }
 
 #define DPR_SMOOTH_BODIES_INSTANTIATE(T, NI, NO)                                                                     \
+    template int smooth_bodies_bin_group<T, NI, NO>(hipStream_t, const SmoothBinning<NO>&, int64_t, int64_t,         \
+                                                    int64_t, int, const T*, const int32_t*, const T*, const T*);    \
     template int smooth_bodies_fwd_atomic<T, NI, NO>(hipStream_t, const int64_t*, int64_t, int64_t, int64_t, int,    \
                                                      T*, const T*, const int32_t*, const T*, const T*, const T*,    \
                                                      const T*);                                                     \

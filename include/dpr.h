@@ -1527,6 +1527,108 @@ int dpr_raster_smooth_bodies_jvp_ex_f64(void *stream, int algo, unsigned flags, 
                                         const double *background_dot, const double *out_weight_dot,
                                         const double *point_weight_dot, void *workspace, size_t workspace_bytes);
 
+/* ---- SMOOTH SAMPLING, RIGID BODIES: quadratic B-spline interpolation of images at the points of K rigid bodies -------
+ * SMOOTH SAMPLING through the poses of RIGID BODIES: the transpose of dpr_raster_smooth_bodies_* with respect to the
+ * point weights, with one weight per (point, image).  Point p belongs to body[p] in [0, K) and is seen in image b
+ * through pose b * K + body[p].  With coord_d, j0_d, u_d, w_d and w'_d of SMOOTH SPLAT under that pose and its
+ * acceptance rule (-1 <= coord_d < n_d + 1 on every axis, tested in floating point; NaN / Inf rejected):
+ *     values[p, b] = sum over s in {-1, 0, +1}^n_out with j0 + s inside the grid of
+ *                    image[j0 + s, b] * prod_d w_d(s_d)
+ *     values[p, b] = 0 for a point rejected in image b, or whose body lies outside [0, K)
+ * So for every image b and every weight vector pw
+ *     sum_v raster_smooth_bodies(pw; background 0, out_weight 1)[v, b] * image[v, b] = sum_p pw[p] * values[p, b],
+ * and column b of `values` restricted to the points of body k is what dpr_sample_smooth_ex_* returns for that subset
+ * under pose (b, k).  `values` is C1 in the points and in all B * K poses.  Not in the reference.
+ * The pullback takes ds_dvalues (P x B) and writes
+ *   ds_dimage[.., b]       dpr_raster_smooth_bodies_ex_* of image b alone with point_weight = ds_dvalues[:, b],
+ *                          background 0 and out_weight 1
+ *   and, with scaled_k = ds_dvalues[p, b] * n_k / 2 * sum_s image[j0 + s, b] * w'_k(s_k) * prod_{d != k} w_d(s_d)
+ *   (that of SMOOTH SAMPLING, with ds_dout = image_b),
+ *   ds_dtranslation[b, k]  sum of scaled over the points of body k
+ *   ds_drotation[b, k]     sum of scaled * p^T over the same points
+ *   ds_dpoints[p]          sum_b R[b, body[p]]^T * scaled
+ * -- the exact derivative; no cell is held fixed.  A body without accepted points gets exact zeros; a dropped point
+ * gets exact zero gradients and deposits nothing.
+ * Layouts: values, ds_dvalues   P x B, point index fastest (image b is the contiguous column at b * P);
+ *          image, ds_dimage     (n_1, .., n_N, B) as `out` of dpr_raster_ex_*;
+ *          body                 P values of int32_t, declared const void *, 4-byte aligned;
+ *          rotation, translation, ds_drotation, ds_dtranslation   those of RIGID BODIES (n_out x n_in x K x B and
+ *                               n_out x K x B, pose (b, k) at index b * K + k; ds_drotation as
+ *                               dpr_raster_pullback_bodies_ex_* writes it).
+ * (n_in, n_out): (2,2), (3,3) and (3,2).  K >= 1 and B * K <= 2^31 - 1.  op: DPR_OP_RASTER (the forward) or
+ * DPR_OP_PULLBACK.  Outputs are overwritten, not accumulated.  Any pullback output may be NULL (not wanted, no work
+ * done for it); at least one must be given; `image` may be NULL when only ds_dimage is wanted.  P = 0 and B = 0 are
+ * valid: nothing is sampled, the per-pose gradients and ds_dimage are 0 (ds_dpoints too when B = 0).
+ * Algorithms (DPR_ALGO_CHUNKED, DPR_ALGO_ORDERED: DPR_ERR_UNSUPPORTED_ALGO).
+ *   Forward  DPR_ALGO_ATOMIC (= AUTO; DPR_ALGO_TILED: DPR_ERR_UNSUPPORTED_ALGO): one thread per point, the point in
+ *            registers across a slice of the images (sliced as SMOOTH SAMPLING slices its poses), the pose read with
+ *            scalar loads where a wave's points share a body -- SORT THE CLOUD BY BODY -- and gathered per lane
+ *            otherwise; the 3^N gathers one 3^(N-1) plane at a time; every values[p, b] stored coalesced, 0 for a
+ *            dropped point.  No atomics and no sum across threads: values[p, b] has the same bits wherever the point
+ *            stands in the cloud.  Workspace 0.
+ *   Pullback DPR_ALGO_ATOMIC: one fused kernel per (point, image slice): from one set of gathers the point gradient
+ *            (kept in registers across the images of a slice; stored with one slice, added atomically with several),
+ *            the per-(image, body) sums, and ds_dvalues * prod w into ds_dimage with global float atomics.  The
+ *            per-(image, body) sums of a block of 256 consecutive points: where its accepted points share one body,
+ *            wave -> block -> one float atomic per value; otherwise every wave reduces per body (masked wave sums over
+ *            the lanes of each body in turn) and, while K <= 64, adds these into a table of the block's bodies in LDS,
+ *            from which ONE global atomic leaves per non-zero (body, value) of the block; with K > 64 one global
+ *            atomic leaves per value, wave and body.  Workspace 0.
+ *   Pullback DPR_ALGO_TILED: the same kernel without the image atomics, then ds_dimage: the planes zeroed and filled
+ *            by GROUPS of images exactly as the DPR_ALGO_TILED forward of SMOOTH SPLAT, RIGID BODIES fills `out` -- its
+ *            key pass, sort and start table per group, and one launch of bg * tiles workgroups on the f64 LDS tile +
+ *            halo, which take the weight of the flat index b_local * P + p from ds_dvalues[(b0 + b_local) * P + p] and
+ *            keep every check of that forward on the run, the point index and the body (the workspace contents are
+ *            not trusted).  Plane b is what dpr_raster_smooth_bodies_ex_*(DPR_ALGO_TILED) returns for image b with
+ *            those weights.  GROUP SIZE, LIMITS and workspace: those of
+ *            dpr_workspace_bytes_smooth_bodies_ex_*(DPR_OP_RASTER, DPR_ALGO_TILED, flags, ..) for the same shape and
+ *            DPR_FLAG_MAX_POSE_GROUP; 0 for P = 0.  The query cannot know whether ds_dimage is wanted and sizes for
+ *            it; a call without ds_dimage reads no workspace.
+ * AUTO (dpr_resolve_algo_sample_smooth_bodies), from the shape alone: the forward DPR_ALGO_ATOMIC; the pullback
+ * DPR_ALGO_TILED exactly where dpr_resolve_algo_smooth_bodies(DPR_OP_RASTER, .., P, B, K) returns it, DPR_ALGO_ATOMIC
+ * otherwise.  That rule was measured for the forward splat, not for this pullback.
+ * Flags: KEEP / REUSE are refused; DPR_FLAG_MAX_POSE_GROUP(n) is HONOURED by the DPR_ALGO_TILED pullback (pass the same
+ * flags to the workspace query) and REFUSED wherever the resolved algorithm is not the DPR_ALGO_TILED pullback, which
+ * alone forms groups; the others are accepted and ignored.
+ * Summation order.  values: plane by plane in the order of SMOOTH SAMPLING, no sum across threads.  Point gradients:
+ * summed over the images of a slice in image order, slices added atomically.  Per-(image, body) sums and ds_dimage:
+ * float atomics (LDS and global), unordered; DPR_ALGO_TILED adds a tile's deposits in f64 first.
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): a pair outside the three
+ * DPR_ERR_UNSUPPORTED_DIMS (the grid is not looked at first); a bad op, negative P / B, a bad grid, K < 1, B * K beyond
+ * 2^31 - 1, all pullback outputs NULL, a NULL input that the call would read, a misaligned data pointer
+ * DPR_ERR_INVALID_ARG; KEEP / REUSE, DPR_ALGO_CHUNKED / DPR_ALGO_ORDERED / an unknown algorithm, a DPR_ALGO_TILED
+ * forward, DPR_FLAG_MAX_POSE_GROUP as above and a DPR_ALGO_TILED pullback outside the LIMITS DPR_ERR_UNSUPPORTED_ALGO; a
+ * workspace smaller than dpr_workspace_bytes_sample_smooth_bodies_ex_* (with ds_dimage wanted) or not 256-byte aligned
+ * DPR_ERR_WORKSPACE.  Every refusal comes from one check that the entry points, the query and the resolver share:
+ * dpr_workspace_bytes_sample_smooth_bodies_ex_* returns (size_t)-1 for every refused combination,
+ * dpr_resolve_algo_sample_smooth_bodies a negative status. */
+int dpr_resolve_algo_sample_smooth_bodies(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B,
+                                          int64_t K);
+size_t dpr_workspace_bytes_sample_smooth_bodies_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                       const int64_t *grid, int64_t P, int64_t B, int64_t K);
+size_t dpr_workspace_bytes_sample_smooth_bodies_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                       const int64_t *grid, int64_t P, int64_t B, int64_t K);
+int dpr_sample_smooth_bodies_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                                    int64_t P, int64_t B, int64_t K, float *values, const float *image,
+                                    const float *points, const void *body, const float *rotation,
+                                    const float *translation, void *workspace, size_t workspace_bytes);
+int dpr_sample_smooth_bodies_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                                    int64_t P, int64_t B, int64_t K, double *values, const double *image,
+                                    const double *points, const void *body, const double *rotation,
+                                    const double *translation, void *workspace, size_t workspace_bytes);
+int dpr_sample_smooth_bodies_pullback_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t *grid, int64_t P, int64_t B, int64_t K,
+                                             const float *ds_dvalues, const float *image, const float *points,
+                                             const void *body, const float *rotation, const float *translation,
+                                             float *ds_dimage, float *ds_dpoints, float *ds_drotation,
+                                             float *ds_dtranslation, void *workspace, size_t workspace_bytes);
+int dpr_sample_smooth_bodies_pullback_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t *grid, int64_t P, int64_t B, int64_t K,
+                                             const double *ds_dvalues, const double *image, const double *points,
+                                             const void *body, const double *rotation, const double *translation,
+                                             double *ds_dimage, double *ds_dpoints, double *ds_drotation,
+                                             double *ds_dtranslation, void *workspace, size_t workspace_bytes);
+
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
  * not in the reference; every algorithm here is faster on coherent input and the sort only depends
