@@ -36,6 +36,9 @@ from .smooth_bodies_jvp import (raster_smooth_bodies_jvp, raster_smooth_bodies_j
                                 resolve_algo_smooth_bodies_jvp)
 from .sample_smooth_bodies import (resolve_algo_sample_smooth_bodies, sample_smooth_bodies, sample_smooth_bodies_,
                                    sample_smooth_bodies_ad, sample_smooth_bodies_pullback_)
+from .sample_smooth_channels import (resolve_algo_sample_smooth_channels, sample_smooth_channels,
+                                     sample_smooth_channels_, sample_smooth_channels_ad,
+                                     sample_smooth_channels_pullback_)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -67,4 +70,6 @@ __all__ = [
     "raster_smooth_bodies_jvp", "raster_smooth_bodies_jvp_", "resolve_algo_smooth_bodies_jvp",
     "sample_smooth_bodies", "sample_smooth_bodies_", "sample_smooth_bodies_pullback_", "sample_smooth_bodies_ad",
     "resolve_algo_sample_smooth_bodies",
+    "sample_smooth_channels", "sample_smooth_channels_", "sample_smooth_channels_pullback_",
+    "sample_smooth_channels_ad", "resolve_algo_sample_smooth_channels",
 ]

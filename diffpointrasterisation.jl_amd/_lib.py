@@ -92,6 +92,10 @@ EXPORTS = [
     "dpr_workspace_bytes_sample_smooth_bodies_ex_f64", "dpr_sample_smooth_bodies_ex_f32",
     "dpr_sample_smooth_bodies_ex_f64", "dpr_sample_smooth_bodies_pullback_ex_f32",
     "dpr_sample_smooth_bodies_pullback_ex_f64",
+    "dpr_resolve_algo_sample_smooth_channels", "dpr_workspace_bytes_sample_smooth_channels_ex_f32",
+    "dpr_workspace_bytes_sample_smooth_channels_ex_f64", "dpr_sample_smooth_channels_ex_f32",
+    "dpr_sample_smooth_channels_ex_f64", "dpr_sample_smooth_channels_pullback_ex_f32",
+    "dpr_sample_smooth_channels_pullback_ex_f64",
 ]
 
 _lib = None
@@ -343,6 +347,20 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, f"dpr_sample_smooth_bodies_pullback_ex_{suf}")
         f.restype = i
         f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 10 + [vp, sz]
+    L.dpr_resolve_algo_sample_smooth_channels.restype = i
+    L.dpr_resolve_algo_sample_smooth_channels.argtypes = [i, i, i, vp, i64, i64, i64]
+    for suf in ("f32", "f64"):
+        f = getattr(L, f"dpr_workspace_bytes_sample_smooth_channels_ex_{suf}")
+        f.restype = sz
+        f.argtypes = [i, i, ctypes.c_uint, i, i, vp, i64, i64, i64]
+        # stream, algo, flags, n_in, n_out, grid, P, B, C, values, image, points, rot, trans, ws, ws_bytes
+        f = getattr(L, f"dpr_sample_smooth_channels_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 5 + [vp, sz]
+        # ..., C, ds_dvalues, image, points, rot, trans, ds_dimage, ds_dpoints, ds_drot, ds_dtrans, ws, ws_bytes
+        f = getattr(L, f"dpr_sample_smooth_channels_pullback_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 9 + [vp, sz]
     L.dpr_comm_unique_id.restype = i
     L.dpr_comm_unique_id.argtypes = [vp, sz]
     L.dpr_comm_init.restype = i

@@ -1,6 +1,6 @@
-// The smooth entry points of libdpr -- splat, sampling, forward mode, per-pose clouds and weight channels: host checks,
-// AUTO rules and C ABI (core: dpr_api.hip; kernels and their launches: dpr_smooth.hip, dpr_smooth_channels.hip; the
-// smooth splat of rigid bodies: dpr_api_smooth_bodies.hip).
+// The smooth entry points of libdpr -- splat, sampling, forward mode, per-pose clouds, weight channels and sampling of
+// channel images: host checks, AUTO rules and C ABI (core: dpr_api.hip; kernels and their launches: dpr_smooth.hip,
+// dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip; the smooth splat of rigid bodies: dpr_api_smooth_bodies.hip).
 #include <hip/hip_runtime.h>
 
 #include "dpr_host.h"
@@ -638,6 +638,130 @@ static size_t workspace_smooth_channels_impl(int op, int algo, unsigned flags, i
     return need;
 }
 
+// ---------------------------------------------------------------- smooth sampling of C-channel images
+// dpr_sample_smooth_channels_ex_* / dpr_sample_smooth_channels_pullback_ex_* (include/dpr.h, "SMOOTH SAMPLING,
+// MULTI-CHANNEL"; kernels: dpr_sample_smooth_channels.hip).  Forward: DPR_ALGO_ATOMIC.  Pullback: DPR_ALGO_ATOMIC, the
+// fused kernel with C image atomics per cell; DPR_ALGO_TILED, the same kernel without them, then ds_dimage pose by
+// pose from the tiled smooth channel forward -- one binning per pose for all C channels.
+// AUTO: the forward is ATOMIC; the pullback is TILED where the smooth channel forward of one pose of the shape would
+// be (resolve_algo_smooth_channels; the measured rows: profiles/sample_smooth_channels_probe.txt).
+static int resolve_algo_sample_smooth_channels(int algo, int op, int n_out, const int64_t* grid, int64_t P,
+                                               int64_t C) {
+    if (algo != DPR_ALGO_AUTO) return algo;
+    if (op == DPR_OP_PULLBACK) return resolve_algo_smooth_channels(DPR_ALGO_AUTO, DPR_OP_RASTER, n_out, grid, P, C);
+    return DPR_ALGO_ATOMIC;
+}
+
+// the host checks both entry points and the queries share: smooth sampling's, then C and the 64-bit offsets of the
+// channel layouts; *G and the resolved *algo come back, *need: workspace (sample_smooth_workspace_bytes: the tiled
+// smooth forward's for one pose, whatever B and C)
+static int check_sample_smooth_channels(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                        int64_t P, int64_t B, int64_t C, int64_t* G, size_t* need) {
+    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
+    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
+    if (int rc = check_sample_smooth_op(op, flags)) return rc;
+    if (C < 1 || C > kMaxChannels)
+        return fail(DPR_ERR_INVALID_ARG, "channels C = %lld out of range [1, %d]", (long long)C, kMaxChannels);
+    *algo = resolve_algo_sample_smooth_channels(*algo, op, n_out, grid, P, C);
+    *need = sample_smooth_workspace_bytes(op, *algo, n_out, grid, P);
+    if (*need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
+    if (int rc = check_sample_sizes(P, B, *G)) return rc;
+    // 64-bit offsets: plane (c, b) starts at (b * C + c) * G, the values of (point p, pose b) at (b * P + p) * C
+    if (B > 0 && (P > ((int64_t)1 << 62) / (B * C) || *G > ((int64_t)1 << 62) / (B * C)))
+        return fail(DPR_ERR_INVALID_ARG, "P * C * B or the image (G * C * B) too large");
+    return DPR_OK;
+}
+
+template <typename T>
+static int sample_smooth_channels_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
+                                       const int64_t* grid, int64_t P, int64_t B, int64_t C, T* values, const T* image,
+                                       const T* points, const T* rot, const T* trans, void* ws, size_t ws_bytes) {
+    (void)ws_bytes;
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_sample_smooth_channels(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need))
+        return rc;
+    if (P == 0 || B == 0) return DPR_OK;
+    if (!values) return fail(DPR_ERR_INVALID_ARG, "values is NULL");
+    if (!image) return fail(DPR_ERR_INVALID_ARG, "image is NULL");
+    if (!points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+    if (int rc = check_alignment<T>(ws, {values, image, points, rot, trans})) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    int64_t slices = 1;
+    const int pps = pose_slices(P, B, &slices);
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        const int rc = sample_smooth_channels_fwd<T, decltype(ni)::value, decltype(no)::value>(
+            st, grid, G, P, B, (int)C, values, image, points, rot, trans, pps, slices);
+        stage_mark(st);
+        return rc;
+    });
+}
+
+template <typename T>
+static int sample_smooth_channels_pullback_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
+                                                const int64_t* grid, int64_t P, int64_t B, int64_t C, const T* dv,
+                                                const T* image, const T* points, const T* rot, const T* trans,
+                                                T* d_img, T* d_pts, T* d_rot, T* d_trans, void* ws, size_t ws_bytes) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (int rc = check_sample_smooth_channels(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need))
+        return rc;
+    if (!d_img && !d_pts && !d_rot && !d_trans)
+        return fail(DPR_ERR_INVALID_ARG, "smooth channel sampling pullback: every output is NULL");
+    const bool tiled = algo == DPR_ALGO_TILED;
+    if (tiled && d_img && P > 0 && B > 0 && need > 0 && (!ws || ws_bytes < need))
+        return fail(DPR_ERR_WORKSPACE,
+                    "DPR_ALGO_TILED smooth channel sampling pullback needs %zu workspace bytes, got %zu", need,
+                    ws ? ws_bytes : (size_t)0);
+    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
+    if (P > 0 && B > 0) {
+        if (!dv) return fail(DPR_ERR_INVALID_ARG, "ds_dvalues is NULL");
+        if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
+        if ((d_pts || d_rot || d_trans) && !image)
+            return fail(DPR_ERR_INVALID_ARG, "image is NULL (needed for ds_dpoints / ds_drotation / ds_dtranslation)");
+    }
+    if (int rc = check_alignment<T>(ws, {dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans})) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    stage_mark(st);
+    if (d_rot) DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * n_out * n_in)));
+    if (d_trans) DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * n_out)));
+    if (d_img) DPR_HIP(zero_async(st, d_img, sizeof(T) * (size_t)(B * C * G)));
+    if (d_pts && B == 0) DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
+    if (P == 0 || B == 0) return DPR_OK;
+    int64_t slices = 1;
+    const int pps = pose_slices(P, B, &slices);
+    const int c = (int)C;
+    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
+        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+        if (int rc = sample_smooth_channels_bwd<T, NI, NO>(st, grid, G, P, B, c, dv, image, points, rot, trans,
+                                                           tiled ? nullptr : d_img, d_pts, d_rot, d_trans, pps,
+                                                           slices))
+            return rc;
+        stage_mark(st);
+        if (tiled && d_img) {
+            // the C planes of pose b (zeroed above): the single-pose tiled smooth channel forward of the weights
+            // ds_dvalues[:, :, b] (P x C, contiguous), out_weight 1 -- what
+            // dpr_raster_smooth_channels_ex_*(DPR_ALGO_TILED) returns for them
+            for (int64_t b = 0; b < B; ++b)
+                if (int rc = smooth_channels_fwd_tiled<T, NI, NO>(st, grid, G, P, 1, c, d_img + b * C * G, points,
+                                                                  rot + b * (NO * NI), trans + b * NO, nullptr,
+                                                                  dv + b * P * C, ws, ws_bytes))
+                    return rc;
+        }
+        return DPR_OK;
+    });
+}
+
+static size_t workspace_sample_smooth_channels_impl(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                    const int64_t* grid, int64_t P, int64_t B, int64_t C) {
+    int64_t G = 0;
+    size_t need = 0;
+    if (check_sample_smooth_channels(op, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need)) return (size_t)-1;
+    return need;
+}
+
 }  // namespace dpr
 
 extern "C" {
@@ -816,5 +940,42 @@ int dpr_resolve_algo_smooth_channels(int op, int n_in, int n_out, const int64_t*
 DPR_DEFINE_SMOOTH_CHANNELS(f32, float)
 DPR_DEFINE_SMOOTH_CHANNELS(f64, double)
 #undef DPR_DEFINE_SMOOTH_CHANNELS
+
+int dpr_resolve_algo_sample_smooth_channels(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
+                                            int64_t C) {
+    int64_t G = 0;
+    size_t need = 0;
+    int algo = DPR_ALGO_AUTO;
+    if (int rc = dpr::check_sample_smooth_channels(op, &algo, 0u, n_in, n_out, grid, P, B, C, &G, &need)) return rc;
+    return algo;
+}
+
+#define DPR_DEFINE_SAMPLE_SMOOTH_CHANNELS(SUF, T)                                                              \
+    size_t dpr_workspace_bytes_sample_smooth_channels_ex_##SUF(int op, int algo, unsigned flags, int n_in,     \
+                                                               int n_out, const int64_t* grid, int64_t P,      \
+                                                               int64_t B, int64_t C) {                         \
+        return dpr::workspace_sample_smooth_channels_impl(op, algo, flags, n_in, n_out, grid, P, B, C);        \
+    }                                                                                                          \
+    int dpr_sample_smooth_channels_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,       \
+                                            const int64_t* grid, int64_t P, int64_t B, int64_t C, T* values,   \
+                                            const T* image, const T* points, const T* rotation,                \
+                                            const T* translation, void* workspace, size_t workspace_bytes) {   \
+        return dpr::sample_smooth_channels_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, C, values,    \
+                                                   image, points, rotation, translation, workspace,            \
+                                                   workspace_bytes);                                           \
+    }                                                                                                          \
+    int dpr_sample_smooth_channels_pullback_ex_##SUF(                                                          \
+        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, \
+        int64_t C, const T* ds_dvalues, const T* image, const T* points, const T* rotation,                    \
+        const T* translation, T* ds_dimage, T* ds_dpoints, T* ds_drotation, T* ds_dtranslation,                \
+        void* workspace, size_t workspace_bytes) {                                                             \
+        return dpr::sample_smooth_channels_pullback_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, C,   \
+                                                            ds_dvalues, image, points, rotation, translation,  \
+                                                            ds_dimage, ds_dpoints, ds_drotation,               \
+                                                            ds_dtranslation, workspace, workspace_bytes);      \
+    }
+DPR_DEFINE_SAMPLE_SMOOTH_CHANNELS(f32, float)
+DPR_DEFINE_SAMPLE_SMOOTH_CHANNELS(f64, double)
+#undef DPR_DEFINE_SAMPLE_SMOOTH_CHANNELS
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // The smooth splat (include/dpr.h, "SMOOTH SPLAT"): quadratic B-spline weights on 3^N cells per point.
 // Index arithmetic shared by the host plan and the kernels of dpr_smooth.hip, and the launchers of dpr_smooth.hip,
-// dpr_smooth_channels.hip, dpr_smooth_bodies.hip and dpr_sample_smooth_bodies.hip that dpr_api_smooth.hip and
-// dpr_api_smooth_bodies.hip call.
+// dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip, dpr_smooth_bodies.hip and dpr_sample_smooth_bodies.hip that
+// dpr_api_smooth.hip and dpr_api_smooth_bodies.hip call.
 #pragma once
 #include <type_traits>
 
@@ -206,6 +206,20 @@ template <typename T, int NI, int NO>
 int sample_smooth_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* dv,
                       const T* image, const T* points, const T* rot, const T* trans, T* d_img, T* d_pts, T* d_rot,
                       T* d_trans, int poses_per_slice, int64_t slices);
+
+// Smooth sampling of C-channel images (include/dpr.h, "SMOOTH SAMPLING, MULTI-CHANNEL"; kernels:
+// dpr_sample_smooth_channels.hip): image / d_img as `out` of the smooth channel splat (plane (c, b) at
+// (b * C + c) * G), values / dv with a point's C values contiguous and the pose slowest ((b * P + p) * C + c), so that
+// column b of dv is a `pw` of smooth_channels_fwd_tiled.  The same contract with the caller (dpr_api_smooth.hip) as
+// sample_smooth_fwd / sample_smooth_bwd: d_img (B * C planes), d_rot and d_trans are zeroed by the caller.
+template <typename T, int NI, int NO>
+int sample_smooth_channels_fwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C, T* values,
+                               const T* image, const T* points, const T* rot, const T* trans, int poses_per_slice,
+                               int64_t slices);
+template <typename T, int NI, int NO>
+int sample_smooth_channels_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C,
+                               const T* dv, const T* image, const T* points, const T* rot, const T* trans, T* d_img,
+                               T* d_pts, T* d_rot, T* d_trans, int poses_per_slice, int64_t slices);
 
 // Smooth sampling at the points of rigid bodies (include/dpr.h, "SMOOTH SAMPLING, RIGID BODIES"; kernels:
 // dpr_sample_smooth_bodies.hip): smooth sampling through pose b * K + body[p].  The same contract with the caller

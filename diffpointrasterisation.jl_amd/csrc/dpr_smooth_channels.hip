@@ -197,53 +197,7 @@ __global__ __launch_bounds__(kSmBlock) void k_smooth_ch_tile(GridDesc<NO> gd, Sm
 }
 
 // ---------------------------------------------------------------- DPR_ALGO_ATOMIC pullback
-// smooth_point_backward (dpr_smooth.hip) for axes and derivatives the caller has formed already: the sums of one
-// (point, pose, channel) without out_weight * point_weight,
-//   W = sum_s g[j0 + s] prod_d w_d(s_d),   dcoord[k] = sum_s g[j0 + s] w'_k(s_k) prod_{d != k} w_d(s_d),
-// with the nine gathers of a plane requested before the first is used and a dropped cell replaced by 0.
-template <typename T, int NO, typename Fetch>
-__device__ __forceinline__ void smooth_point_backward_axes(const SmoothAxes<T, NO>& ax, const T (&dw)[NO][3],
-                                                           Fetch fetch, T (&dcoord)[NO], T& W) {
-    auto plane = [&](int base, bool vb, T& S, T& S0, T& S1) {
-        T gq[3][3];
-#pragma unroll
-        for (int k1 = 0; k1 < 3; ++k1)
-#pragma unroll
-            for (int k0 = 0; k0 < 3; ++k0) {
-                const bool v = vb && ax.in[1][k1] && ax.in[0][k0];
-                const T x = fetch(v ? base + ax.off[1][k1] + ax.off[0][k0] : 0);
-                gq[k1][k0] = v ? x : T(0);
-            }
-        S = T(0);
-        S0 = T(0);
-        S1 = T(0);
-#pragma unroll
-        for (int k1 = 0; k1 < 3; ++k1) {
-            const T a = (gq[k1][0] * ax.w[0][0] + gq[k1][1] * ax.w[0][1]) + gq[k1][2] * ax.w[0][2];
-            const T da = (gq[k1][0] * dw[0][0] + gq[k1][1] * dw[0][1]) + gq[k1][2] * dw[0][2];
-            S += a * ax.w[1][k1];
-            S0 += da * ax.w[1][k1];
-            S1 += a * dw[1][k1];
-        }
-    };
-    if constexpr (NO == 2) {
-        plane(0, true, W, dcoord[0], dcoord[1]);
-    } else {
-        W = T(0);
-#pragma unroll
-        for (int d = 0; d < NO; ++d) dcoord[d] = T(0);
-#pragma unroll
-        for (int k2 = 0; k2 < 3; ++k2) {
-            T S, S0, S1;
-            plane(ax.off[2][k2], ax.in[2][k2], S, S0, S1);
-            W += S * ax.w[2][k2];
-            dcoord[0] += S0 * ax.w[2][k2];
-            dcoord[1] += S1 * ax.w[2][k2];
-            dcoord[2] += S * dw[2][k2];
-        }
-    }
-}
-
+// (the point term of a channel, smooth_point_backward_axes: dpr_smooth_device.h)
 // CB: compile-time bound of C (4 or kMaxChannels): the channel weights and the ds_dpoint_weight accumulators live in
 // registers.  Pre-zeroed: ds_drotation, ds_dtranslation, ds_dout_weight; with accumulate_points also ds_dpoints and
 // ds_dpoint_weight (the poses are cut into slices on grid.y, every slice adds its share with atomics).

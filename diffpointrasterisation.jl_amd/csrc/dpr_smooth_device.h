@@ -1,7 +1,7 @@
 // Device helpers of the smooth splat (include/dpr.h, "SMOOTH SPLAT") that the kernels of dpr_smooth.hip,
-// dpr_smooth_channels.hip and dpr_smooth_bodies.hip share: the cell of a point, the B-spline weights of an axis and
-// their derivatives, the per-axis offsets of the 3^N cells, the pullback's sums of one (point, pose), and the rows of
-// one tangent's deposits in forward mode.
+// dpr_smooth_channels.hip, dpr_smooth_bodies.hip and dpr_sample_smooth_channels.hip share: the cell of a point, the
+// B-spline weights of an axis and their derivatives, the per-axis offsets of the 3^N cells, the pullback's sums of one
+// (point, pose), and the rows of one tangent's deposits in forward mode.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -82,6 +82,52 @@ __device__ __forceinline__ SmoothAxes<T, NO> smooth_axes(const int (&j0)[NO], co
 // The nine gathers of a plane (axes 0 and 1) are requested before the first is used; a dropped cell fetches cell 0
 // of the pose and is replaced by 0 (a select, not a multiplication).  3-D: plane after plane, so that nine values
 // are live at a time, not 27.
+// smooth_point_backward_axes: the same sums, operation for operation, for axes and derivatives the caller has formed
+// already -- the kernels with C planes per (point, pose) (dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip) form
+// them once and call this per plane.  (Two bodies, not one calling the other: the kernels compiled before the second
+// user of the _axes form keep their code objects byte for byte.)
+template <typename T, int NO, typename Fetch>
+__device__ __forceinline__ void smooth_point_backward_axes(const SmoothAxes<T, NO>& ax, const T (&dw)[NO][3],
+                                                           Fetch fetch, T (&dcoord)[NO], T& W) {
+    auto plane = [&](int base, bool vb, T& S, T& S0, T& S1) {
+        T gq[3][3];
+#pragma unroll
+        for (int k1 = 0; k1 < 3; ++k1)
+#pragma unroll
+            for (int k0 = 0; k0 < 3; ++k0) {
+                const bool v = vb && ax.in[1][k1] && ax.in[0][k0];
+                const T x = fetch(v ? base + ax.off[1][k1] + ax.off[0][k0] : 0);
+                gq[k1][k0] = v ? x : T(0);
+            }
+        S = T(0);
+        S0 = T(0);
+        S1 = T(0);
+#pragma unroll
+        for (int k1 = 0; k1 < 3; ++k1) {
+            const T a = (gq[k1][0] * ax.w[0][0] + gq[k1][1] * ax.w[0][1]) + gq[k1][2] * ax.w[0][2];
+            const T da = (gq[k1][0] * dw[0][0] + gq[k1][1] * dw[0][1]) + gq[k1][2] * dw[0][2];
+            S += a * ax.w[1][k1];
+            S0 += da * ax.w[1][k1];
+            S1 += a * dw[1][k1];
+        }
+    };
+    if constexpr (NO == 2) {
+        plane(0, true, W, dcoord[0], dcoord[1]);
+    } else {
+        W = T(0);
+#pragma unroll
+        for (int d = 0; d < NO; ++d) dcoord[d] = T(0);
+#pragma unroll
+        for (int k2 = 0; k2 < 3; ++k2) {
+            T S, S0, S1;
+            plane(ax.off[2][k2], ax.in[2][k2], S, S0, S1);
+            W += S * ax.w[2][k2];
+            dcoord[0] += S0 * ax.w[2][k2];
+            dcoord[1] += S1 * ax.w[2][k2];
+            dcoord[2] += S * dw[2][k2];
+        }
+    }
+}
 template <typename T, int NO, typename Fetch>
 __device__ __forceinline__ void smooth_point_backward(const int (&j0)[NO], const T (&u)[NO], const GridDesc<NO>& gd,
                                                       Fetch fetch, T (&dcoord)[NO], T& W) {

@@ -338,6 +338,17 @@ extern "C" {
  *                        cell receives <= 3^N such partials as float atomics in T onto the background tangent:
  *                        rounding level, not bit-reproducible
  *
+ *   smooth sampling of C-channel images (dpr_sample_smooth_channels_ex_* / dpr_sample_smooth_channels_pullback_ex_*, see
+ *   SMOOTH SAMPLING, MULTI-CHANNEL below):
+ *   values               no sum across threads, no atomics: plane (c, b) in the order of SMOOTH SAMPLING -- the BITS of
+ *                        dpr_sample_smooth_ex_* on that plane, fp32 and fp64
+ *   ds_dpoints           a thread adds its C channels in index order, then the poses of its slice in index order; one
+ *                        slice: one plain store, bit-reproducible; several: float atomics, rounding level (note 1)
+ *   per-pose sums        the C channels in index order inside the thread, then wave -> block -> one float atomic per
+ *                        block: rounding level
+ *   ds_dimage            DPR_ALGO_ATOMIC: global float atomics in T, unordered: rounding level.  DPR_ALGO_TILED: the
+ *                        smooth channel splat's tiled forward per (pose, tile, channel): rounding level
+ *
  * Note 1, pose slices.  A per-point kernel that would leave the device idle cuts the B poses into slices on
  * the second grid axis; every slice adds its share of ds_dpoints / ds_dpoint_weight with float atomics onto
  * zeroed buffers.  DPR_ALGO_ATOMIC and its channel form: fewer than 2048 blocks of 256 points (P <= 523 776)
@@ -1628,6 +1639,93 @@ int dpr_sample_smooth_bodies_pullback_ex_f64(void *stream, int algo, unsigned fl
                                              const void *body, const double *rotation, const double *translation,
                                              double *ds_dimage, double *ds_dpoints, double *ds_drotation,
                                              double *ds_dtranslation, void *workspace, size_t workspace_bytes);
+
+/* ---- SMOOTH SAMPLING, MULTI-CHANNEL: quadratic B-spline interpolation of C-channel images at the points, C1 ----------
+ * SMOOTH SAMPLING of the images SMOOTH SPLAT, MULTI-CHANNEL writes: C values per (point, pose), C = 1..16.  With coord_d,
+ * j0_d, u_d, w_d and w'_d of SMOOTH SPLAT and its acceptance rule (-1 <= coord_d < n_d + 1 on every axis, tested in
+ * floating point; NaN / Inf rejected; cells outside the grid dropped one by one), all from R_b p + t_b alone:
+ *     values[p, c, b] = sum over s in {-1, 0, +1}^n_out with j0 + s inside the grid of
+ *                       image[j0 + s, c, b] * prod_d w_d(s_d)
+ *     values[p, c, b] = 0 for a rejected point
+ * values[:, c, b] is dpr_sample_smooth_ex_* of plane (c, b), BIT FOR BIT in fp32 and fp64 (no atomics; every plane is
+ * contracted in the same order).  The operator is the transpose of dpr_raster_smooth_channels_* in the point weights
+ * with one weight per (point, channel, pose):
+ *     sum_{v, c} ds_dimage[v, c, b] * image[v, c, b] = sum_{p, c} ds_dvalues[p, c, b] * values[p, c, b].
+ * The pullback takes ds_dvalues and writes
+ *   ds_dimage[.., c, b]  dpr_raster_smooth_ex_* of pose b with point_weight = ds_dvalues[:, c, b], background 0,
+ *                        out_weight 1: pose b's C planes are dpr_raster_smooth_channels_ex_* with point_weight =
+ *                        ds_dvalues[:, :, b]
+ *   ds_dpoints, ds_drotation, ds_dtranslation
+ *                        the sums over c of dpr_sample_smooth_pullback_ex_*'s gradients for plane (c, b) with
+ *                        ds_dvalues[:, c, b]: scaled_k = n_k / 2 * sum_c ds_dvalues[p, c, b] * sum_s image[j0 + s, c, b]
+ *                        * w'_k(s_k) * prod_{d != k} w_d(s_d), then as SMOOTH SAMPLING
+ * -- the exact derivative; no cell is held fixed.
+ * Layouts: image, ds_dimage     (n_1, .., n_N, C, B) as `out` of dpr_raster_smooth_channels_ex_*: plane (c, b) at
+ *                               (b * C + c) * G;
+ *          values, ds_dvalues   a point's C values contiguous, pose slowest: element (p, c, b) at (b * P + p) * C + c,
+ *                               so that ds_dvalues + b * P * C is a point_weight of dpr_raster_smooth_channels_ex_*;
+ *          everything else      as for dpr_sample_smooth_ex_* / dpr_sample_smooth_pullback_ex_*.
+ * (n_in, n_out): (2,2), (3,3) and (3,2); every other pair DPR_ERR_UNSUPPORTED_DIMS.  op: DPR_OP_RASTER (the forward)
+ * or DPR_OP_PULLBACK.  Outputs are overwritten, not accumulated.  Any pullback output may be NULL (not wanted, no
+ * work done for it); at least one must be given; `image` may be NULL when only ds_dimage is wanted.
+ * Algorithms (DPR_ALGO_CHUNKED, DPR_ALGO_ORDERED, unknown ones: DPR_ERR_UNSUPPORTED_ALGO).
+ *   Forward  DPR_ALGO_ATOMIC (= AUTO; DPR_ALGO_TILED: DPR_ERR_UNSUPPORTED_ALGO): one thread per point, the point in
+ *            registers across a slice of the poses; the cell, the weights and the offsets once per (point, pose), then
+ *            the planes in groups of four and a rest one by one; with C % 4 == 0, fp32 and `values` 16-byte aligned a
+ *            group leaves as one 16-byte store; no atomics, workspace 0.
+ *   Pullback DPR_ALGO_ATOMIC: one fused kernel per (point, pose slice), sliced as the smooth pullback slices the
+ *            poses: per channel ds_dvalues * prod w into ds_dimage with C global atomics per accepted cell, and from
+ *            the gathers of the C planes the n_out sums sum_c ds_dvalues * dcoord_c, which give the point gradient
+ *            (stored with one slice, added atomically with several) and the per-pose sums (wave -> block -> one
+ *            atomic per scalar per block); workspace 0.
+ *   Pullback DPR_ALGO_TILED: the same kernel without the image atomics, then ds_dimage pose by pose: the planes
+ *            zeroed, then the tiled smooth channel forward with B = 1, point_weight = ds_dvalues + b * P * C,
+ *            out_weight NULL -- one binning per pose for all C channels; the C planes of pose b are what
+ *            dpr_raster_smooth_channels_ex_*(DPR_ALGO_TILED) returns for those weights.  Workspace: that of
+ *            dpr_raster_smooth_ex_*(DPR_ALGO_TILED) for (grid, P), independent of B and C; its LIMITS and COST apply.
+ *            It is required only when ds_dimage is asked for and P, B > 0.
+ * AUTO (dpr_resolve_algo_sample_smooth_channels), from the shape and C alone: the forward DPR_ALGO_ATOMIC; the pullback
+ * DPR_ALGO_TILED exactly where dpr_resolve_algo_smooth_channels(DPR_OP_RASTER, .., P, 1, C) returns it, DPR_ALGO_ATOMIC
+ * otherwise (that threshold was measured for the smooth channel forward; profiles/sample_smooth_channels_probe.txt
+ * has this pullback's own times on either path).
+ * Flags: KEEP / REUSE are refused (DPR_ERR_UNSUPPORTED_ALGO), the others accepted and ignored.
+ * Workspace and stream: the contract of dpr_raster_ex_* holds -- the call only enqueues on `stream`, writes only
+ * inside [workspace, workspace + workspace_bytes), and the initial contents of the workspace do not matter.
+ * Summation order: the row of SUMMATION ORDER above.
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): a pair outside the three
+ * DPR_ERR_UNSUPPORTED_DIMS; C outside 1..16, a bad op, negative P / B, a bad grid, all pullback outputs NULL, a NULL
+ * input that the call would read, a misaligned data pointer DPR_ERR_INVALID_ARG; KEEP / REUSE, DPR_ALGO_CHUNKED /
+ * DPR_ALGO_ORDERED / an unknown algorithm, a DPR_ALGO_TILED forward and a DPR_ALGO_TILED pullback outside the LIMITS
+ * DPR_ERR_UNSUPPORTED_ALGO; a workspace smaller than dpr_workspace_bytes_sample_smooth_channels_ex_* (with ds_dimage
+ * wanted) or not 256-byte aligned DPR_ERR_WORKSPACE.  P = 0 or B = 0: DPR_OK, the outputs that still have elements
+ * zeroed.  dpr_workspace_bytes_sample_smooth_channels_ex_* returns (size_t)-1 for every refused combination,
+ * dpr_resolve_algo_sample_smooth_channels a negative status. */
+int dpr_resolve_algo_sample_smooth_channels(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B,
+                                            int64_t C);
+size_t dpr_workspace_bytes_sample_smooth_channels_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                         const int64_t *grid, int64_t P, int64_t B, int64_t C);
+size_t dpr_workspace_bytes_sample_smooth_channels_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                         const int64_t *grid, int64_t P, int64_t B, int64_t C);
+int dpr_sample_smooth_channels_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, int64_t C, float *values,
+                                      const float *image, const float *points, const float *rotation,
+                                      const float *translation, void *workspace, size_t workspace_bytes);
+int dpr_sample_smooth_channels_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t *grid, int64_t P, int64_t B, int64_t C, double *values,
+                                      const double *image, const double *points, const double *rotation,
+                                      const double *translation, void *workspace, size_t workspace_bytes);
+int dpr_sample_smooth_channels_pullback_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                               const int64_t *grid, int64_t P, int64_t B, int64_t C,
+                                               const float *ds_dvalues, const float *image, const float *points,
+                                               const float *rotation, const float *translation, float *ds_dimage,
+                                               float *ds_dpoints, float *ds_drotation, float *ds_dtranslation,
+                                               void *workspace, size_t workspace_bytes);
+int dpr_sample_smooth_channels_pullback_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                               const int64_t *grid, int64_t P, int64_t B, int64_t C,
+                                               const double *ds_dvalues, const double *image, const double *points,
+                                               const double *rotation, const double *translation, double *ds_dimage,
+                                               double *ds_dpoints, double *ds_drotation, double *ds_dtranslation,
+                                               void *workspace, size_t workspace_bytes);
 
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
