@@ -1,46 +1,16 @@
 // The smooth splat (include/dpr.h, "SMOOTH SPLAT"): quadratic B-spline weights on 3^N cells per point.
-// Index arithmetic shared by the host plan and the kernels of dpr_smooth.hip, and the launchers of dpr_smooth.hip,
-// dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip, dpr_smooth_bodies.hip and dpr_sample_smooth_bodies.hip that
-// dpr_api_smooth.hip and dpr_api_smooth_bodies.hip call.
+// The launchers of dpr_smooth.hip, dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip, dpr_smooth_bodies.hip and
+// dpr_sample_smooth_bodies.hip that dpr_api_smooth.hip and dpr_api_smooth_bodies.hip call.  The tiles of
+// DPR_ALGO_TILED (SmoothTileShape, SmoothTiles, smooth_tiles) and their index arithmetic, shared by the host plan and
+// every key and tile kernel: dpr_smooth_tile.h.
 #pragma once
 #include <type_traits>
 
 #include "../../include/dpr.h"
+#include "dpr_smooth_tile.h"
 #include "dpr_tiled.h"
 
 namespace dpr {
-
-// ---- tiles of DPR_ALGO_TILED ----------------------------------------------------------------------------------
-// A workgroup owns a tile and keeps it, plus one halo cell on both sides of every axis, as f64 cells in LDS:
-// 3-D 16 x 8 x 8 (18 x 10 x 10 cells, 14 400 bytes), 2-D 64 x 16 (66 x 18 cells, 9 504 bytes) -- ten workgroups and
-// more per CU's 160 KB.
-template <int NO> struct SmoothTileShape;
-template <> struct SmoothTileShape<2> {
-    static constexpr int e[2] = {64, 16};
-};
-template <> struct SmoothTileShape<3> {
-    static constexpr int e[3] = {16, 8, 8};
-};
-template <int NO> constexpr int smooth_lds_cells() {
-    int c = 1;
-    for (int d = 0; d < NO; ++d) c *= SmoothTileShape<NO>::e[d] + 2;
-    return c;
-}
-
-template <int NO> struct SmoothTiles {
-    int nt[NO];     // tiles per axis
-    int64_t tiles;  // their product
-};
-template <int NO> SmoothTiles<NO> smooth_tiles(const int64_t* grid) {
-    SmoothTiles<NO> t;
-    t.tiles = 1;
-    for (int d = 0; d < NO; ++d) {
-        const int e = SmoothTileShape<NO>::e[d];
-        t.nt[d] = (int)((grid[d] + e - 1) / e);
-        t.tiles *= t.nt[d];
-    }
-    return t;
-}
 
 constexpr uint32_t kSmoothNoKey = 0xffffffffu;  // a rejected point; sorts behind every tile
 
