@@ -21,7 +21,8 @@
 //   pullback k_tile_gather  ds_dout tile (+halo) staged in LDS, per-point gathers from LDS, the
 //                           gradient overwrites the record in place; per-item partial sums
 //            k_unpermute    gradient records back to the original point order (k_unpermute_runs: one
-//                           pose behind k_scatter_wc_runs, whole record runs through the sorted map)
+//                           pose behind k_scatter_wc_runs, whole record runs through the sorted map,
+//                           a slot per run: dpr_run_map.h)
 //            k_pose_reduce  per-item partials (f64) -> ds_drotation, ds_dtranslation, ...
 //
 // Why f64 accumulators for fp32 data: on gfx950 ds_add_f32 retires ~1 lane per 3 cycles
@@ -730,8 +731,9 @@ __global__ __launch_bounds__(kBinThreads) void k_scatter(
 // ones, profiles/r01_experiments.md).
 //   LDS: cursor[NT * nb] (dynamic) | lhist[NT] (dynamic) | recs[S] | dest[S] | lpos[S] (RUNS)
 // RUNS (single pose, 4-word records; Plan::run_map): the map for the pullback's un-permute is written in
-// SORTED order -- per sub-chunk, slot_of[base + i] = dest[i] and run_lp[base + i] = the index inside the
-// sub-chunk of the point at sorted position i, kRunEnd in slot_of from position n_valid on -- so that
+// SORTED order and per record run (dpr_run_map.h) -- per sub-chunk, run_lp[base + i] = the index inside the
+// sub-chunk of the point at sorted position i, with the start bit on the first position of a run, and in
+// slot_of, per segment of 64 positions, the slots of the first records of the segment's runs -- so that
 // k_unpermute_runs reads the gradient records run by run, as this kernel wrote the point records.
 // (The body of the two kernels that follow it: k_scatter_wc, and k_scatter_wc_runs for RUNS.)
 template <typename T, int NI, int NO, bool HAS_PW, int S, bool GROUP, bool W3, bool RUNS>
@@ -755,7 +757,7 @@ __device__ __forceinline__ void scatter_wc_body(
         return;
     }
     static_assert(!(W3 && HAS_PW), "compact records carry no point weight");
-    static_assert(!RUNS || (!GROUP && !W3 && S <= 65536), "the sorted map: one pose, 4-word records, uint16 owners");
+    static_assert(!RUNS || (!GROUP && !W3 && S <= kRunMaxSub), "the sorted map: one pose, 4-word records, 12-bit owners");
     constexpr int PPT = S / kWcThreads;  // points per thread per sub-chunk
     uint32_t wkey = 0;  // max / min |point_weight| of the binned points (wrange_*: k_tile_splat's fixed point)
     // Pose group (nb > 1): the S points of a sub-chunk stay in registers while the poses of the
@@ -919,7 +921,7 @@ __device__ __forceinline__ void scatter_wc_body(
                     if constexpr (!W3) r.v[3] = HAS_PW ? w[k] : idx_to_slot((uint32_t)base + lp, T(0));
                     recs[sidx] = r;
                     dest[sidx] = d;
-                    if constexpr (RUNS) lpos[sidx] = (uint16_t)lp;
+                    if constexpr (RUNS) lpos[sidx] = run_owner_word(lp, run_starts(sidx, lrank[k]));
                     else if (slot_b) __builtin_nontemporal_store(d, &slot_b[lp]);
                 } else if (lp < nloc) {
                     if (!RUNS && slot_b) __builtin_nontemporal_store(Pe, &slot_b[lp]);  // spare slot
@@ -934,16 +936,19 @@ __device__ __forceinline__ void scatter_wc_body(
             lds_barrier();
             // d. write-out in LDS (= tile) order; e. advance cursors, clear the histogram
             if constexpr (RUNS) {
-                // ... and the sorted map of the sub-chunk, both halves coalesced
+                // ... and the sorted map of the sub-chunk: an owner word per position (none from n_valid on), and
+                // per segment of 64 positions (= the lanes of this wave) the slots of its run starts, packed to
+                // the front of the segment's 64 table entries
                 uint16_t* const lp_b = run_lp + base;
                 for (uint32_t i = threadIdx.x; i < nloc; i += kWcThreads) {
                     const bool owned = i < n_valid;
                     const uint32_t d = dest[i];
-                    if (owned) {
-                        rec[d] = recs[i];
-                        __builtin_nontemporal_store(lpos[i], &lp_b[i]);
-                    }
-                    __builtin_nontemporal_store(owned ? d : kRunEnd, &slot_b[i]);
+                    const uint32_t ow = owned ? lpos[i] : kRunNone;
+                    if (owned) rec[d] = recs[i];
+                    __builtin_nontemporal_store((uint16_t)ow, &lp_b[i]);
+                    const bool st = owned && (ow & kRunStart);
+                    const uint64_t starts = __ballot(st);
+                    if (st) __builtin_nontemporal_store(d, &slot_b[run_table_index(i, starts, (uint32_t)lane)]);
                 }
             } else {
                 for (uint32_t i = threadIdx.x; i < n_valid; i += kWcThreads) rec[dest[i]] = recs[i];
@@ -3047,14 +3052,20 @@ __global__ __launch_bounds__(1024) void k_unpermute(int64_t P, int nb,
 }
 
 // ------------------------------------------------------------------ pullback un-permute, run order
-// The single-pose un-permute over the SORTED map k_scatter_wc_runs left (Plan::run_map): a block per
-// scatter sub-chunk of S points, lane i takes sorted position i -- its slot, the gradient record there,
-// and the index inside the sub-chunk of the point that owns it.  Neighbouring lanes sit in the same
-// record run and share its cache lines (a thread per ORIGINAL point asks for a line of its own: ~16
-// distinct lines per 16 lanes against ~8 in run order at C3).  The records are put in original order in
-// an LDS stage (zero-filled first: a rejected point owns no position and leaves with an empty gradient,
-// which is what the spare slot holds for k_unpermute), then ds_dpoints / ds_dpoint_weight of the
-// sub-chunk leave as dense stores.  Same values, same additions as k_unpermute: a pure permutation.
+// The single-pose un-permute over the SORTED map k_scatter_wc_runs left (Plan::run_map, dpr_run_map.h): a block
+// per scatter sub-chunk of S points, lane i takes sorted position i -- its owner word, its slot, the gradient
+// record there.  Neighbouring lanes sit in the same record run and share its cache lines (a thread per ORIGINAL
+// point asks for a line of its own: ~16 distinct lines per 16 lanes against ~8 in run order at C3).
+// The slot of a position is (first slot of its run) + (distance to the run's start).  A wave holds one SEGMENT
+// of 64 positions and decodes it alone: the ballot of the start bits gives every lane the index of its run
+// among the segment's runs and the lane the run starts at, and the run's first slot comes from the lane that
+// loaded that table entry (a shuffle).  Lane l asks for entry l of its segment TOGETHER with its owner word,
+// whether a run put a slot there or not (19 of 64 at C3; the rest is never looked at), so the gradient loads
+// wait for one round trip as they did with a slot per position, and no wave waits for another before them.
+// The records are put in original order in an LDS stage (zero-filled first: a rejected point owns no position
+// and leaves with an empty gradient, which is what the spare slot holds for k_unpermute), then ds_dpoints /
+// ds_dpoint_weight of the sub-chunk leave as dense stores.  Same values, same additions as k_unpermute: a pure
+// permutation.
 //   LDS: stage[S] records = 64 KB (two workgroups per CU)
 template <typename T, int NI, bool FIRST_POSE>
 __global__ __launch_bounds__(1024, 8) void k_unpermute_runs(int64_t P, const Rec4<T>* __restrict__ grad,
@@ -3065,6 +3076,7 @@ __global__ __launch_bounds__(1024, 8) void k_unpermute_runs(int64_t P, const Rec
                                                             int reduce_blocks, PoseReduceArgs<T> pr) {
     constexpr int S = sizeof(T) == 4 ? kWcPpt * kWcThreads : kWcPpt * kWcThreads / 2;  // the scatter's sub-chunk
     constexpr int PPT = S / 1024;
+    static_assert(kRunSegment == kWave && 1024 % kRunSegment == 0, "a wave holds whole segments");
     __shared__ Rec4<T> stage[S];
     // the first `reduce_blocks` blocks are the per-pose reduction
     if ((int)blockIdx.x < reduce_blocks) {
@@ -3089,31 +3101,45 @@ __global__ __launch_bounds__(1024, 8) void k_unpermute_runs(int64_t P, const Rec
     }
     const int64_t base = (int64_t)xcd_slice(ublock, ublocks) * S;
     const uint32_t nloc = (uint32_t)((P - base < S) ? P - base : S);  // points of this sub-chunk (>= 1)
-    uint32_t slot[PPT], lp[PPT];
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    // owner words and table entries, one round trip (position i: entry i; all indices stay inside the
+    // sub-chunk's nloc entries)
+    uint32_t own[PPT], tab[PPT];
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
         const uint32_t i = threadIdx.x + (uint32_t)k * 1024;
         const uint32_t ic = i < nloc ? i : nloc - 1;
-        slot[k] = __builtin_nontemporal_load(&run_slot[base + ic]);
-        lp[k] = __builtin_nontemporal_load(&run_lp[base + ic]);
-        if (i >= nloc) slot[k] = kRunEnd;
+        own[k] = __builtin_nontemporal_load(&run_lp[base + ic]);
+        if (i >= nloc) own[k] = kRunNone;
+        tab[k] = __builtin_nontemporal_load(&run_slot[base + ic]);
     }
     Rec4<T> zero;
 #pragma unroll
     for (int c = 0; c < 4; ++c) zero.v[c] = T(0);
+    // (a slot is a record of this pose: below P; anything else a foreign map holds is no record)
+    uint32_t slot[PPT];
+    bool has[PPT];
 #pragma unroll
-    for (int k = 0; k < PPT; ++k) stage[threadIdx.x + k * 1024] = zero;
-    // (a slot is a record of this pose: below P; kRunEnd and anything a foreign map holds is no record)
+    for (int k = 0; k < PPT; ++k) {
+        const uint64_t starts = __ballot((own[k] & kRunStart) != 0u);
+        uint32_t j, dist;
+        has[k] = run_segment_decode(starts, lane, j, dist) && run_owner_valid(own[k]);
+        slot[k] = (uint32_t)__shfl((int)tab[k], (int)j, kWave) + dist;
+        has[k] = has[k] && slot[k] < (uint64_t)P;
+    }
     Rec4<T> g[PPT];
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
         g[k] = zero;
-        if (slot[k] < (uint64_t)P) g[k] = grad[slot[k]];
+        if (has[k]) g[k] = grad[slot[k]];
     }
+    // (the zero fill goes to the LDS queue behind the shuffles the gradient loads wait for, not in front of them)
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) stage[threadIdx.x + k * 1024] = zero;
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < PPT; ++k)
-        if (slot[k] < (uint64_t)P) stage[lp[k] & (uint32_t)(S - 1)] = g[k];
+        if (has[k]) stage[run_owner_index<S>(own[k])] = g[k];
     __syncthreads();
     // original order: point base + q is stage[q]; component j of it is word 4 q + j of the stage
     const T* const words = &stage[0].v[0];

@@ -7,6 +7,7 @@
 #include "../../include/dpr.h"
 #include "dpr_device.h"
 #include "dpr_jvp.h"
+#include "dpr_run_map.h"
 #include "dpr_tiled.h"
 
 namespace dpr {
@@ -136,14 +137,19 @@ constexpr int kMaxRunsGather = 64;   // ... and in k_tile_gather (their tables l
 //   slot_of[p]   = record slot of ORIGINAL point p, the spare slot for a rejected one; `indices` holds the
 //                  point index of every record for the plain k_scatter with point weights, else nothing
 //   run_map      (Plan::run_map: one pose at a time through the write-combining scatter) the map is kept in
-//                  SORTED order instead, per scatter sub-chunk of `sub` points starting at point g * sub:
-//                    slot_of region, uint32 [g * sub + i] = record slot of sorted position i of the
-//                                                           sub-chunk, kRunEnd from the first position no
-//                                                           record owns (rejected points own none)
-//                    indices region, uint16 [g * sub + i] = index inside the sub-chunk (< sub) of the point
-//                                                           that owns sorted position i
-//                  2 + 4 bytes per point: the uint16 half fills at most half of `indices`.
-constexpr uint32_t kRunEnd = 0xffffffffu;  // (no record slot: slots are < P < 2^32)
+//                  SORTED order and per record run instead (dpr_run_map.h has the format and both directions
+//                  of it), per scatter sub-chunk of `sub` points starting at point g * sub:
+//                  A run = the records of one tile inside one segment of 64 sorted positions.
+//                    indices region, uint16 [g * sub + i] = owner word of sorted position i: the index inside
+//                                                           the sub-chunk (< sub) of the point that owns it,
+//                                                           bit 15 on the first position of a run; kRunNone
+//                                                           from the first position no record owns (rejected
+//                                                           points own none)
+//                    slot_of region, uint32 [g * sub + 64 s + j] = record slot of the first record of run j of
+//                                                           segment s; nothing from the segment's number of
+//                                                           runs on
+//                  2 + 4 * runs / sub bytes per point are written (3.2 at C3): the uint16 half fills at most
+//                  half of `indices`, the run table a part of `slot_of` that depends on the cloud.
 struct Plan {
     int bg;          // poses binned together (pose group, a power of two; 1 = per-pose pipeline)
     int nblk;

@@ -266,7 +266,7 @@ uint32_t plan_layout_id(const Plan& pl) {
     mix(pl.pose_stride);
     mix(pl.off_iperm);
     mix((uint64_t)pl.lb);
-    mix(pl.run_map ? 1 : 0);
+    mix(pl.run_map ? kRunMapVersion : 0);  // (the form of the sorted map: a binning kept in another form is refused)
     const uint32_t id = (uint32_t)(h ^ (h >> 32));
     return id ? id : 1u;
 }
