@@ -50,7 +50,7 @@ static int raster_bodies_impl(void* stream, int algo, unsigned flags, int n_in, 
     if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
     if (P > 0 && (!rot || !trans)) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL with P > 0");
     if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
-    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
+    if (int rc = check_body_alignment(body)) return rc;
     hipStream_t st = (hipStream_t)stream;
     stage_mark(st);
     fill_background(st, out, G, B, bg);
@@ -93,7 +93,7 @@ static int pullback_bodies_impl(void* stream, int algo, unsigned flags, int n_in
     }
     if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
         return rc;
-    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
+    if (int rc = check_body_alignment(body)) return rc;
     hipStream_t st = (hipStream_t)stream;
     stage_mark(st);
     if (B == 0) {  // no image: the sums over the poses are empty

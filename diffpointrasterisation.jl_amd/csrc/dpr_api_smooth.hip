@@ -1,33 +1,22 @@
 // The smooth entry points of libdpr -- splat, sampling, forward mode, per-pose clouds, weight channels and sampling of
-// channel images: host checks, AUTO rules and C ABI (core: dpr_api.hip; kernels and their launches: dpr_smooth.hip,
-// dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip; the smooth splat of rigid bodies: dpr_api_smooth_bodies.hip).
+// channel images: what each family is, its AUTO rule, its extent and size bounds, and the C ABI.  The checks, pointer
+// checks, stream prologues and entry-point skeletons they share: dpr_host_smooth.h (core: dpr_api.hip; kernels and
+// their launches: dpr_smooth.hip, dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip; the smooth splat of rigid
+// bodies: dpr_api_smooth_bodies.hip).
 #include <hip/hip_runtime.h>
 
-#include "dpr_host.h"
-#include "dpr_smooth.h"
+#include "dpr_host_smooth.h"
 
 namespace dpr {
+
+static int no_extent() { return DPR_OK; }
 
 // ---------------------------------------------------------------- smooth splat
 // dpr_raster_smooth_ex_* / dpr_raster_pullback_smooth_ex_* (include/dpr.h, "SMOOTH SPLAT"; kernels: dpr_smooth.hip).
 // (2,2), (3,3), (3,2) only.  DPR_ALGO_ATOMIC: forward and pullback; DPR_ALGO_TILED: forward.
-// (before check_common: the grid of a pair without kernels is not looked at)
-static int check_smooth_dims(int n_in, int n_out) {
-    if (!smooth_dims_supported(n_in, n_out))
-        return fail(DPR_ERR_UNSUPPORTED_DIMS,
-                    "unsupported (n_in, n_out) = (%d, %d); the smooth splat supports (2,2), (3,3), (3,2)", n_in, n_out);
-    return DPR_OK;
-}
-static int check_smooth(int op, unsigned flags) {
-    if (op == DPR_OP_RESIDUAL_PULLBACK)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth splat has no residual pullback");
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
-        return fail(DPR_ERR_INVALID_ARG, "smooth splat: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "the smooth splat keeps / reuses no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    return DPR_OK;
-}
+constexpr SmoothFamily kSmoothSplat{"smooth splat", kTiledForward, /*residual_refusal*/ true, /*group_plan*/ false,
+                                    kGroupIgnored, /*has_body*/ false, /*needs_point_weight*/ false,
+                                    /*pullback_slices_poses*/ true};
 
 // AUTO (dpr_resolve_algo_smooth), from the shape alone (profiles/smooth_probe.txt, fp32, uniform clouds in either
 // order, 1 and 16 poses).  The pullback is DPR_ALGO_ATOMIC.  The forward is DPR_ALGO_TILED from a point count on,
@@ -40,194 +29,87 @@ static int check_smooth(int op, unsigned flags) {
 //    2.21 / 1.82), 1e6 0.229 against 0.412 (3.14 / 5.98).  Between 3e5 and 1e6 nothing was measured.
 constexpr int64_t kSmoothTiledMinPoints3D = 100000;
 constexpr int64_t kSmoothTiledMinPoints2D = 500000;
-static int resolve_algo_smooth(int algo, int op, int n_out, const int64_t* grid, int64_t P) {
-    if (algo != DPR_ALGO_AUTO) return algo;
+static int resolve_algo_smooth(int op, int n_out, const int64_t* grid, int64_t P) {
     const int64_t min_points = n_out == 3 ? kSmoothTiledMinPoints3D : kSmoothTiledMinPoints2D;
     if (op == DPR_OP_RASTER && P >= min_points && smooth_tile_count(n_out, grid, P) != 0) return DPR_ALGO_TILED;
     return DPR_ALGO_ATOMIC;
 }
 
-// bytes of workspace, or (size_t)-1 (message recorded) when the algorithm cannot run the call
-static size_t smooth_workspace_bytes(int op, int algo, int n_out, const int64_t* grid, int64_t P) {
-    if (algo == DPR_ALGO_ATOMIC) return 0;  // (the pullback's per-pose partials leave their block as atomics)
-    if (algo != DPR_ALGO_TILED) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth splat runs on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d",
-             algo);
-        return (size_t)-1;
-    }
-    if (op != DPR_OP_RASTER) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth pullback runs on DPR_ALGO_ATOMIC only");
-        return (size_t)-1;
-    }
-    const size_t n = smooth_tiled_workspace_bytes(n_out, grid, P);
-    if (n == (size_t)-1)
-        fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    return n;
+// (the entry points alone hold P to the block count of a launch: this family's query and resolver answer for any P)
+static SmoothCall check_smooth_splat(bool entry_point, int op, int algo, unsigned flags, int n_in, int n_out,
+                                     const int64_t* grid, int64_t P, int64_t B) {
+    return smooth_checks(
+        kSmoothSplat, op, algo, flags, n_in, n_out, grid, P, B, no_extent,
+        [&](int64_t) { return entry_point ? check_point_blocks(P) : DPR_OK; },
+        [&] { return resolve_algo_smooth(op, n_out, grid, P); });
 }
 
 template <typename T>
 static int raster_smooth_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
                               int64_t P, int64_t B, T* out, const T* points, const T* rot, const T* trans,
                               const T* bg, const T* ow, const T* pw, void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_smooth(DPR_OP_RASTER, flags)) return rc;
-    if (int rc = check_point_blocks(P)) return rc;
-    algo = resolve_algo_smooth(algo, DPR_OP_RASTER, n_out, grid, P);
-    const size_t need = smooth_workspace_bytes(DPR_OP_RASTER, algo, n_out, grid, P);
-    if (need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
-    if (B == 0) return DPR_OK;
-    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "smooth splat (algorithm %d) needs %zu workspace bytes, got %zu", algo, need,
-                    ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    fill_background(st, out, G, B, bg);
-    stage_mark(st);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_fwd_tiled<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, ow, pw, ws, ws_bytes)
-                           : smooth_fwd_atomic<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, ow, pw);
-        stage_mark(st);
-        return rc;
-    });
+    const SmoothCall c = check_smooth_splat(true, DPR_OP_RASTER, algo, flags, n_in, n_out, grid, P, B);
+    return smooth_splat_forward<T>(
+        kSmoothSplat, c, stream, n_in, n_out, P, B, B, out, points, nullptr, rot, trans, bg, ow, pw, ws, ws_bytes,
+        [&](hipStream_t st, auto ni, auto no) {
+            constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+            return c.algo == DPR_ALGO_TILED
+                       ? smooth_fwd_tiled<T, NI, NO>(st, grid, c.G, P, B, out, points, rot, trans, ow, pw, ws, ws_bytes)
+                       : smooth_fwd_atomic<T, NI, NO>(st, grid, c.G, P, B, out, points, rot, trans, ow, pw);
+        });
 }
 
 template <typename T>
 static int pullback_smooth_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
                                 int64_t P, int64_t B, const T* g, const T* points, const T* rot, const T* trans,
                                 const T* ow, const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw,
-                                void* ws, size_t ws_bytes) {
-    (void)ws_bytes;
-    int64_t G = 0;
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = check_smooth(DPR_OP_PULLBACK, flags)) return rc;
-    if (int rc = check_point_blocks(P)) return rc;
+                                void* ws, size_t) {
+    const SmoothCall c = check_smooth_splat(true, DPR_OP_PULLBACK, algo, flags, n_in, n_out, grid, P, B);
     if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
-    algo = resolve_algo_smooth(algo, DPR_OP_PULLBACK, n_out, grid, P);
-    if (smooth_workspace_bytes(DPR_OP_PULLBACK, algo, n_out, grid, P) == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
-    if (B == 0) return DPR_OK;  // (every output is empty)
-    if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (!d_rot || !d_trans || !d_bg || !d_ow) return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
-    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
-        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * n_out * n_in)));
-    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * n_out)));
-    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
-    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)B));
-    grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
-    stage_mark(st);
-    if (P == 0) return DPR_OK;  // (the per-pose sums are 0, ds_dbackground is done; pose_slices divides by the blocks)
-    int64_t slices = 1;
-    const int poses_per_slice = pose_slices(P, B, &slices);  // (the linear atomic pullback's: SUMMATION ORDER, note 1)
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        const int rc = smooth_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
-            st, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice,
-            slices);
-        stage_mark(st);
-        return rc;
-    });
-}
-
-template <typename T>
-static size_t workspace_smooth_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                    int64_t P, int64_t B) {
-    int64_t G = 0;
-    if (check_smooth_dims(n_in, n_out)) return (size_t)-1;
-    if (check_common(n_in, n_out, grid, P, B, &G)) return (size_t)-1;
-    if (check_smooth(op, flags)) return (size_t)-1;
-    algo = resolve_algo_smooth(algo, op, n_out, grid, P);
-    return smooth_workspace_bytes(op, algo, n_out, grid, P);
+    return smooth_splat_pullback<T>(
+        kSmoothSplat, c, stream, flags, n_in, n_out, P, B, B, B, g, points, nullptr, rot, trans, ow, pw, d_pts, d_rot,
+        d_trans, d_bg, d_ow, d_pw, ws, [&](hipStream_t st, auto ni, auto no, int poses_per_slice, int64_t slices) {
+            return smooth_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice,
+                slices);
+        });
 }
 
 // ---------------------------------------------------------------- smooth sampling
 // dpr_sample_smooth_ex_* / dpr_sample_smooth_pullback_ex_* (include/dpr.h, "SMOOTH SAMPLING"; kernels:
 // dpr_smooth.hip).  Forward: DPR_ALGO_ATOMIC.  Pullback: DPR_ALGO_ATOMIC, the fused kernel with image atomics;
 // DPR_ALGO_TILED, the same kernel without them, then ds_dimage pose by pose from the tiled smooth forward.
-static int check_sample_smooth_op(int op, unsigned flags) {
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
-        return fail(DPR_ERR_INVALID_ARG, "smooth sampling: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "smooth sampling keeps / reuses no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    return DPR_OK;
-}
+constexpr SmoothFamily kSmoothSampling{"smooth sampling", kTiledPullback, /*residual_refusal*/ false,
+                                       /*group_plan*/ false, kGroupIgnored, /*has_body*/ false,
+                                       /*needs_point_weight*/ false, /*pullback_slices_poses*/ false};
 
 // AUTO: the forward is ATOMIC; the pullback is TILED where the smooth forward of one pose of the shape would be
 // (the measured rows: profiles/sample_smooth_probe.txt)
-static int resolve_algo_sample_smooth(int algo, int op, int n_out, const int64_t* grid, int64_t P) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    if (op == DPR_OP_PULLBACK) return resolve_algo_smooth(DPR_ALGO_AUTO, DPR_OP_RASTER, n_out, grid, P);
+static int resolve_algo_sample_smooth(int op, int n_out, const int64_t* grid, int64_t P) {
+    if (op == DPR_OP_PULLBACK) return resolve_algo_smooth(DPR_OP_RASTER, n_out, grid, P);
     return DPR_ALGO_ATOMIC;
 }
 
-// bytes of workspace, or (size_t)-1 (message recorded) when the algorithm cannot run the call
-static size_t sample_smooth_workspace_bytes(int op, int algo, int n_out, const int64_t* grid, int64_t P) {
-    if (algo == DPR_ALGO_ATOMIC) return 0;
-    if (algo != DPR_ALGO_TILED) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO,
-             "smooth sampling runs on DPR_ALGO_ATOMIC and, the pullback, DPR_ALGO_TILED, not algorithm %d", algo);
-        return (size_t)-1;
-    }
-    if (op != DPR_OP_PULLBACK) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth sampling forward runs on DPR_ALGO_ATOMIC only");
-        return (size_t)-1;
-    }
-    const size_t n = smooth_tiled_workspace_bytes(n_out, grid, P);
-    if (n == (size_t)-1)
-        fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    return n;
-}
-
-// the host checks both entry points share; *G_out and the resolved *algo come back
-static int check_sample_smooth(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                               int64_t B, int64_t* G_out, size_t* need) {
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, G_out)) return rc;
-    if (int rc = check_sample_smooth_op(op, flags)) return rc;
-    *algo = resolve_algo_sample_smooth(*algo, op, n_out, grid, P);
-    *need = sample_smooth_workspace_bytes(op, *algo, n_out, grid, P);
-    if (*need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
-    return check_sample_sizes(P, B, *G_out);
+// (the entry points and the query hold the sizes to check_sample_sizes: this family's resolver answers for any)
+static SmoothCall check_sample_smooth(bool resolver, int op, int algo, unsigned flags, int n_in, int n_out,
+                                      const int64_t* grid, int64_t P, int64_t B) {
+    return smooth_checks(
+        kSmoothSampling, op, algo, flags, n_in, n_out, grid, P, B, no_extent,
+        [&](int64_t G) { return resolver ? DPR_OK : check_sample_sizes(P, B, G); },
+        [&] { return resolve_algo_sample_smooth(op, n_out, grid, P); });
 }
 
 template <typename T>
 static int sample_smooth_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
                               int64_t P, int64_t B, T* values, const T* image, const T* points, const T* rot,
-                              const T* trans, void* ws, size_t ws_bytes) {
-    (void)ws_bytes;
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_sample_smooth(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return rc;
-    if (P == 0 || B == 0) return DPR_OK;
-    if (!values) return fail(DPR_ERR_INVALID_ARG, "values is NULL");
-    if (!image) return fail(DPR_ERR_INVALID_ARG, "image is NULL");
-    if (!points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (int rc = check_alignment<T>(ws, {values, image, points, rot, trans})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    int64_t slices = 1;
-    const int pps = pose_slices(P, B, &slices);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        const int rc = sample_smooth_fwd<T, decltype(ni)::value, decltype(no)::value>(
-            st, grid, G, P, B, values, image, points, rot, trans, pps, slices);
-        stage_mark(st);
-        return rc;
-    });
+                              const T* trans, void* ws, size_t) {
+    const SmoothCall c = check_sample_smooth(false, DPR_OP_RASTER, algo, flags, n_in, n_out, grid, P, B);
+    return smooth_sample_forward<T>(
+        kSmoothSampling, c, stream, n_in, n_out, P, B, values, image, points, nullptr, rot, trans, ws,
+        [&](hipStream_t st, auto ni, auto no, int poses_per_slice, int64_t slices) {
+            return sample_smooth_fwd<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, values, image, points, rot, trans, poses_per_slice, slices);
+        });
 }
 
 template <typename T>
@@ -235,57 +117,26 @@ static int sample_smooth_pullback_impl(void* stream, int algo, unsigned flags, i
                                        const int64_t* grid, int64_t P, int64_t B, const T* dv, const T* image,
                                        const T* points, const T* rot, const T* trans, T* d_img, T* d_pts, T* d_rot,
                                        T* d_trans, void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_sample_smooth(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return rc;
-    if (!d_img && !d_pts && !d_rot && !d_trans)
-        return fail(DPR_ERR_INVALID_ARG, "smooth sampling pullback: every output is NULL");
-    const bool tiled = algo == DPR_ALGO_TILED;
-    if (tiled && d_img && P > 0 && B > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "DPR_ALGO_TILED smooth sampling pullback needs %zu workspace bytes, got %zu",
-                    need, ws ? ws_bytes : (size_t)0);
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && B > 0) {
-        if (!dv) return fail(DPR_ERR_INVALID_ARG, "ds_dvalues is NULL");
-        if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-        if ((d_pts || d_rot || d_trans) && !image)
-            return fail(DPR_ERR_INVALID_ARG, "image is NULL (needed for ds_dpoints / ds_drotation / ds_dtranslation)");
-    }
-    if (int rc = check_alignment<T>(ws, {dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    if (d_rot) DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * n_out * n_in)));
-    if (d_trans) DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * n_out)));
-    if (d_img) DPR_HIP(zero_async(st, d_img, sizeof(T) * (size_t)(B * G)));
-    if (d_pts && B == 0) DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
-    if (P == 0 || B == 0) return DPR_OK;
-    int64_t slices = 1;
-    const int pps = pose_slices(P, B, &slices);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        if (int rc = sample_smooth_bwd<T, NI, NO>(st, grid, G, P, B, dv, image, points, rot, trans,
-                                                  tiled ? nullptr : d_img, d_pts, d_rot, d_trans, pps, slices))
-            return rc;
-        stage_mark(st);
-        if (tiled && d_img) {
-            // plane b (zeroed above): the single-pose tiled smooth forward of weights ds_dvalues[:, b] (a contiguous
-            // column), out_weight 1 -- what dpr_raster_smooth_ex_*(DPR_ALGO_TILED) returns for them
+    const SmoothCall c = check_sample_smooth(false, DPR_OP_PULLBACK, algo, flags, n_in, n_out, grid, P, B);
+    return smooth_sample_pullback<T>(
+        kSmoothSampling, c, stream, n_in, n_out, P, B, B, B, dv, image, points, nullptr, rot, trans, d_img, d_pts,
+        d_rot, d_trans, ws, ws_bytes,
+        [&](hipStream_t st, auto ni, auto no, T* d_img_atomic, int poses_per_slice, int64_t slices) {
+            return sample_smooth_bwd<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, dv, image, points, rot, trans, d_img_atomic, d_pts, d_rot, d_trans,
+                poses_per_slice, slices);
+        },
+        [&](hipStream_t st, auto ni, auto no) -> int {
+            constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+            // plane b: the single-pose tiled smooth forward of weights ds_dvalues[:, b] (a contiguous column),
+            // out_weight 1 -- what dpr_raster_smooth_ex_*(DPR_ALGO_TILED) returns for them
             for (int64_t b = 0; b < B; ++b)
-                if (int rc = smooth_fwd_tiled<T, NI, NO>(st, grid, G, P, 1, d_img + b * G, points, rot + b * (NO * NI),
-                                                         trans + b * NO, nullptr, dv + b * P, ws, ws_bytes))
+                if (int rc = smooth_fwd_tiled<T, NI, NO>(st, grid, c.G, P, 1, d_img + b * c.G, points,
+                                                         rot + b * (NO * NI), trans + b * NO, nullptr, dv + b * P, ws,
+                                                         ws_bytes))
                     return rc;
-        }
-        return DPR_OK;
-    });
-}
-
-template <typename T>
-static size_t workspace_sample_smooth_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                           int64_t P, int64_t B) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (check_sample_smooth(op, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return (size_t)-1;
-    return need;
+            return DPR_OK;
+        });
 }
 
 // ---------------------------------------------------------------- smooth splat, forward mode
@@ -304,24 +155,25 @@ static size_t workspace_sample_smooth_impl(int op, int algo, unsigned flags, int
 //    and 4e5 is the measured row.  Nothing was measured between.
 constexpr int64_t kSmoothJvpTiledMinWork3D = 100000;
 constexpr int64_t kSmoothJvpTiledMinWork2D = 400000;
-static int resolve_algo_smooth_jvp(int algo, int n_out, const int64_t* grid, int64_t P, int64_t K) {
-    if (algo != DPR_ALGO_AUTO) return algo;
+static int resolve_algo_smooth_jvp(int n_out, const int64_t* grid, int64_t P, int64_t K) {
     const int64_t min_work = n_out == 3 ? kSmoothJvpTiledMinWork3D : kSmoothJvpTiledMinWork2D;
     if (P * K >= min_work && smooth_tile_count(n_out, grid, P) != 0) return DPR_ALGO_TILED;
     return DPR_ALGO_ATOMIC;
 }
 
-// the checks every smooth JVP entry point and query shares, in the smooth entry points' order; *need: workspace
-static int check_smooth_jvp(int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                            int64_t B, int64_t K, int64_t* G, size_t* need) {
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
-    if (int rc = check_jvp(K, flags)) return rc;
-    if (int rc = check_sample_sizes(P, B, *G)) return rc;
-    if (B > 0 && *G * K > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "output too large");
-    *algo = resolve_algo_smooth_jvp(*algo, n_out, grid, P, K);
-    *need = smooth_workspace_bytes(DPR_OP_RASTER, *algo, n_out, grid, P);
-    return *need == (size_t)-1 ? DPR_ERR_UNSUPPORTED_ALGO : DPR_OK;
+constexpr SmoothFamily kSmoothJvp{"smooth JVP", kTiledOnlyOp, /*residual_refusal*/ false, /*group_plan*/ false,
+                                  kGroupIgnored, /*has_body*/ false, /*needs_point_weight*/ false,
+                                  /*pullback_slices_poses*/ false};
+
+static SmoothCall check_smooth_jvp(int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
+                                   int64_t B, int64_t K) {
+    return smooth_checks(
+        kSmoothJvp, DPR_OP_RASTER, algo, flags, n_in, n_out, grid, P, B, [&] { return check_jvp(K, 0u); },
+        [&](int64_t G) {
+            if (int rc = check_sample_sizes(P, B, G)) return rc;
+            return check_plane_offsets(G, K, B);
+        },
+        [&] { return resolve_algo_smooth_jvp(n_out, grid, P, K); });
 }
 
 template <typename T>
@@ -329,51 +181,27 @@ static int raster_smooth_jvp_impl(void* stream, int algo, unsigned flags, int n_
                                   int64_t P, int64_t B, int64_t K, T* out_dot, const T* points, const T* rot,
                                   const T* trans, const T* ow, const T* pw, JvpTangents<T> tan, const T* bg_dot,
                                   void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_jvp(&algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
-    if (B == 0) return DPR_OK;
-    if (!out_dot) return fail(DPR_ERR_INVALID_ARG, "out_dot is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "smooth JVP (algorithm %d) needs %zu workspace bytes, got %zu", algo, need,
-                    ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out_dot, points, rot, trans, ow, pw, tan.points, tan.rot, tan.trans, tan.ow,
-                                         tan.pw, bg_dot}))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    // the background tangent (or 0) into every plane; then the deposits, where any other tangent is given
+    const SmoothCall c = check_smooth_jvp(algo, flags, n_in, n_out, grid, P, B, K);
     const int k = (int)K;
-    jvp_fill(st, out_dot, G, k, B, bg_dot);
-    stage_mark(st);
-    DPR_HIP(hipGetLastError());
-    if (P == 0 || !(tan.points || tan.rot || tan.trans || tan.ow || tan.pw)) return DPR_OK;
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_jvp_tiled<T, NI, NO>(st, grid, G, P, B, k, out_dot, points, rot, trans, ow, pw, tan,
-                                                         ws, ws_bytes)
-                           : smooth_jvp_atomic<T, NI, NO>(st, grid, G, P, B, k, out_dot, points, rot, trans, ow, pw,
-                                                          tan);
-        stage_mark(st);
-        return rc;
-    });
-}
-
-static size_t workspace_smooth_jvp_impl(int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                                        int64_t B, int64_t K) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (check_smooth_jvp(&algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return (size_t)-1;
-    return need;
+    return smooth_jvp_forward<T>(
+        kSmoothJvp, c, stream, n_in, n_out, P, B, K, out_dot, points, nullptr, rot, trans, ow, pw, tan, bg_dot, ws,
+        ws_bytes, [&](hipStream_t st, auto ni, auto no) {
+            constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+            return c.algo == DPR_ALGO_TILED
+                       ? smooth_jvp_tiled<T, NI, NO>(st, grid, c.G, P, B, k, out_dot, points, rot, trans, ow, pw, tan,
+                                                     ws, ws_bytes)
+                       : smooth_jvp_atomic<T, NI, NO>(st, grid, c.G, P, B, k, out_dot, points, rot, trans, ow, pw,
+                                                      tan);
+        });
 }
 
 // ---------------------------------------------------------------- smooth splat, per-pose clouds
 // dpr_raster_smooth_clouds_ex_* / dpr_raster_pullback_smooth_clouds_ex_* (include/dpr.h, "SMOOTH SPLAT, PER-POSE
 // CLOUDS"; kernels: dpr_smooth.hip).  DPR_ALGO_ATOMIC: forward and pullback, one thread per (point, pose).
 // DPR_ALGO_TILED: forward, the poses binned in groups (smooth_clouds_group; DPR_FLAG_MAX_POSE_GROUP honoured).
+constexpr SmoothFamily kSmoothClouds{"smooth splat of per-pose clouds", kTiledForward, /*residual_refusal*/ true,
+                                     /*group_plan*/ true, kGroupIgnored, /*has_body*/ false,
+                                     /*needs_point_weight*/ false, /*pullback_slices_poses*/ false};
 
 // AUTO (dpr_resolve_algo_smooth_clouds), from the shape alone (profiles/smooth_clouds_probe.txt, fp32, uniform clouds
 // in generation order, times in ms TILED / ATOMIC).  The pullback is DPR_ALGO_ATOMIC.  The forward is DPR_ALGO_TILED
@@ -391,8 +219,7 @@ static size_t workspace_smooth_jvp_impl(int algo, unsigned flags, int n_in, int 
 constexpr int64_t kSmoothCloudsTiledMinWork3D = 100000;
 constexpr int64_t kSmoothCloudsTiledMinWork2D = 400000;
 constexpr int64_t kSmoothCloudsTiledMinPointsPerTile = 4;
-static int resolve_algo_smooth_clouds(int algo, int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    if (algo != DPR_ALGO_AUTO) return algo;
+static int resolve_algo_smooth_clouds(int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
     if (op != DPR_OP_RASTER) return DPR_ALGO_ATOMIC;
     const int64_t bg = smooth_clouds_group(n_out, grid, P, B, 0);
     if (bg == 0) return DPR_ALGO_ATOMIC;
@@ -401,112 +228,49 @@ static int resolve_algo_smooth_clouds(int algo, int op, int n_out, const int64_t
     return bg * P >= min_work && P / kSmoothCloudsTiledMinPointsPerTile >= tiles ? DPR_ALGO_TILED : DPR_ALGO_ATOMIC;
 }
 
-// bytes of workspace, or (size_t)-1 (message recorded) when the algorithm cannot run the call
-static size_t smooth_clouds_workspace_bytes(int op, int algo, unsigned flags, int n_out, const int64_t* grid,
-                                            int64_t P, int64_t B) {
-    if (algo == DPR_ALGO_ATOMIC) return 0;
-    if (algo != DPR_ALGO_TILED) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO,
-             "the smooth splat of per-pose clouds runs on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d", algo);
-        return (size_t)-1;
-    }
-    if (op != DPR_OP_RASTER) {
-        fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth pullback runs on DPR_ALGO_ATOMIC only");
-        return (size_t)-1;
-    }
-    const size_t n = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, max_pose_group(flags));
-    if (n == (size_t)-1)
-        fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    return n;
-}
-
-// the checks every entry point and query of the family shares, in the order of the two parent families; *G and the
-// resolved *algo come back, *need: workspace
-static int check_smooth_clouds(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                               int64_t B, int64_t* G, size_t* need) {
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
-    if (int rc = check_smooth(op, flags)) return rc;
-    // 64-bit offsets: cloud b starts at b * P * n_in, plane b at b * G
-    if (int rc = check_point_blocks(P)) return rc;
-    if (B > 0 && (P > ((int64_t)1 << 60) / B / n_in || *G > ((int64_t)1 << 62) / B))
-        return fail(DPR_ERR_INVALID_ARG, "B * P * n_in or the image (G * B) too large");
-    *algo = resolve_algo_smooth_clouds(*algo, op, n_out, grid, P, B);
-    *need = smooth_clouds_workspace_bytes(op, *algo, flags, n_out, grid, P, B);
-    return *need == (size_t)-1 ? DPR_ERR_UNSUPPORTED_ALGO : DPR_OK;
+static SmoothCall check_smooth_clouds(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                      int64_t P, int64_t B) {
+    return smooth_checks(
+        kSmoothClouds, op, algo, flags, n_in, n_out, grid, P, B, no_extent,
+        [&](int64_t G) {
+            // 64-bit offsets: cloud b starts at b * P * n_in, plane b at b * G
+            if (int rc = check_point_blocks(P)) return rc;
+            if (B > 0 && (P > ((int64_t)1 << 60) / B / n_in || G > ((int64_t)1 << 62) / B))
+                return fail(DPR_ERR_INVALID_ARG, "B * P * n_in or the image (G * B) too large");
+            return (int)DPR_OK;
+        },
+        [&] { return resolve_algo_smooth_clouds(op, n_out, grid, P, B); });
 }
 
 template <typename T>
 static int raster_smooth_clouds_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
                                      int64_t P, int64_t B, T* out, const T* points, const T* rot, const T* trans,
                                      const T* bg, const T* ow, const T* pw, void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_clouds(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return rc;
-    if (B == 0) return DPR_OK;
-    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "smooth splat of per-pose clouds (algorithm %d) needs %zu workspace bytes, got %zu",
-                    algo, need, ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    fill_background(st, out, G, B, bg);
-    stage_mark(st);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_clouds_fwd_tiled<T, NI, NO>(st, grid, G, P, B, max_pose_group(flags), out,
-                                                                points, rot, trans, ow, pw, ws, ws_bytes)
-                           : smooth_clouds_fwd_atomic<T, NI, NO>(st, grid, G, P, B, out, points, rot, trans, ow, pw);
-        stage_mark(st);
-        return rc;
-    });
+    const SmoothCall c = check_smooth_clouds(DPR_OP_RASTER, algo, flags, n_in, n_out, grid, P, B);
+    return smooth_splat_forward<T>(
+        kSmoothClouds, c, stream, n_in, n_out, P, B, B, out, points, nullptr, rot, trans, bg, ow, pw, ws, ws_bytes,
+        [&](hipStream_t st, auto ni, auto no) {
+            constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+            return c.algo == DPR_ALGO_TILED
+                       ? smooth_clouds_fwd_tiled<T, NI, NO>(st, grid, c.G, P, B, max_pose_group(flags), out, points,
+                                                            rot, trans, ow, pw, ws, ws_bytes)
+                       : smooth_clouds_fwd_atomic<T, NI, NO>(st, grid, c.G, P, B, out, points, rot, trans, ow, pw);
+        });
 }
 
 template <typename T>
 static int pullback_smooth_clouds_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
                                        const int64_t* grid, int64_t P, int64_t B, const T* g, const T* points,
                                        const T* rot, const T* trans, const T* ow, const T* pw, T* d_pts, T* d_rot,
-                                       T* d_trans, T* d_bg, T* d_ow, T* d_pw, void* ws, size_t ws_bytes) {
-    (void)ws_bytes;
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_clouds(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return rc;
+                                       T* d_trans, T* d_bg, T* d_ow, T* d_pw, void* ws, size_t) {
+    const SmoothCall c = check_smooth_clouds(DPR_OP_PULLBACK, algo, flags, n_in, n_out, grid, P, B);
     if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
-    if (B == 0) return DPR_OK;  // (every output is empty)
-    if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (!d_rot || !d_trans || !d_bg || !d_ow) return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
-    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
-        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * n_out * n_in)));
-    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * n_out)));
-    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
-    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)B));
-    grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
-    stage_mark(st);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        const int rc = smooth_clouds_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
-            st, grid, G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw);
-        stage_mark(st);
-        return rc;
-    });
-}
-
-static size_t workspace_smooth_clouds_impl(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                           int64_t P, int64_t B) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (check_smooth_clouds(op, &algo, flags, n_in, n_out, grid, P, B, &G, &need)) return (size_t)-1;
-    return need;
+    return smooth_splat_pullback<T>(
+        kSmoothClouds, c, stream, flags, n_in, n_out, P, B, B, B, g, points, nullptr, rot, trans, ow, pw, d_pts, d_rot,
+        d_trans, d_bg, d_ow, d_pw, ws, [&](hipStream_t st, auto ni, auto no, int, int64_t) {
+            return smooth_clouds_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw);
+        });
 }
 
 // ---------------------------------------------------------------- smooth splat, C weights per point
@@ -526,63 +290,47 @@ static size_t workspace_smooth_clouds_impl(int op, int algo, unsigned flags, int
 //    and 3e5, and 3e5 is the measured row.  Nothing was measured between.
 constexpr int64_t kSmoothChannelsTiledMinWork3D = 100000;
 constexpr int64_t kSmoothChannelsTiledMinWork2D = 300000;
-static int resolve_algo_smooth_channels(int algo, int op, int n_out, const int64_t* grid, int64_t P, int64_t C) {
-    if (algo != DPR_ALGO_AUTO) return algo;
+static int resolve_algo_smooth_channels(int op, int n_out, const int64_t* grid, int64_t P, int64_t C) {
     if (op != DPR_OP_RASTER) return DPR_ALGO_ATOMIC;
     const int64_t min_work = n_out == 3 ? kSmoothChannelsTiledMinWork3D : kSmoothChannelsTiledMinWork2D;
     if (P * C >= min_work && smooth_tile_count(n_out, grid, P) != 0) return DPR_ALGO_TILED;
     return DPR_ALGO_ATOMIC;
 }
 
-// the checks every entry point and query of the family shares, in the smooth entry points' order; *G and the
-// resolved *algo come back, *need: workspace
-static int check_smooth_channels(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                 int64_t P, int64_t B, int64_t C, int64_t* G, size_t* need) {
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
-    if (int rc = check_smooth(op, flags)) return rc;
-    if (C < 1 || C > kMaxChannels)
-        return fail(DPR_ERR_INVALID_ARG, "channels C = %lld out of range [1, %d]", (long long)C, kMaxChannels);
-    // 64-bit offsets: plane (c, b) starts at (b * C + c) * G, the weights of point p at p * C
-    if (int rc = check_point_blocks(P)) return rc;
-    if (B > 0 && *G * C > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "output too large");
-    *algo = resolve_algo_smooth_channels(*algo, op, n_out, grid, P, C);
-    *need = smooth_workspace_bytes(op, *algo, n_out, grid, P);
-    return *need == (size_t)-1 ? DPR_ERR_UNSUPPORTED_ALGO : DPR_OK;
+constexpr SmoothFamily kSmoothChannels{"smooth splat with channels", kTiledForward, /*residual_refusal*/ true,
+                                       /*group_plan*/ false, kGroupIgnored, /*has_body*/ false,
+                                       /*needs_point_weight*/ true, /*pullback_slices_poses*/ true};
+
+static SmoothCall check_smooth_channels(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                        int64_t P, int64_t B, int64_t C) {
+    return smooth_checks(
+        kSmoothChannels, op, algo, flags, n_in, n_out, grid, P, B, [&] { return check_channel_count(C); },
+        [&](int64_t G) {
+            // 64-bit offsets: plane (c, b) starts at (b * C + c) * G, the weights of point p at p * C
+            if (int rc = check_point_blocks(P)) return rc;
+            return check_plane_offsets(G, C, B);
+        },
+        [&] { return resolve_algo_smooth_channels(op, n_out, grid, P, C); });
 }
 
+// fill_background / grid_sum serve the B * C planes as they are: ds_dbackground[b, c] = sum of plane b * C + c
 template <typename T>
 static int raster_smooth_channels_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
                                        const int64_t* grid, int64_t P, int64_t B, int64_t C, T* out, const T* points,
                                        const T* rot, const T* trans, const T* bg, const T* ow, const T* pw, void* ws,
                                        size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_channels(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need)) return rc;
-    if (B == 0) return DPR_OK;
-    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && !pw) return fail(DPR_ERR_INVALID_ARG, "point_weight is NULL with P > 0 (the channel form needs it)");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "smooth splat with channels (algorithm %d) needs %zu workspace bytes, got %zu",
-                    algo, need, ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    fill_background(st, out, G, B * C, bg);
-    stage_mark(st);
-    const int c = (int)C;
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_channels_fwd_tiled<T, NI, NO>(st, grid, G, P, B, c, out, points, rot, trans, ow, pw,
-                                                                  ws, ws_bytes)
-                           : smooth_channels_fwd_atomic<T, NI, NO>(st, grid, G, P, B, c, out, points, rot, trans, ow,
-                                                                   pw);
-        stage_mark(st);
-        return rc;
-    });
+    const SmoothCall c = check_smooth_channels(DPR_OP_RASTER, algo, flags, n_in, n_out, grid, P, B, C);
+    const int ch = (int)C;
+    return smooth_splat_forward<T>(
+        kSmoothChannels, c, stream, n_in, n_out, P, B, B * C, out, points, nullptr, rot, trans, bg, ow, pw, ws,
+        ws_bytes, [&](hipStream_t st, auto ni, auto no) {
+            constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+            return c.algo == DPR_ALGO_TILED
+                       ? smooth_channels_fwd_tiled<T, NI, NO>(st, grid, c.G, P, B, ch, out, points, rot, trans, ow, pw,
+                                                              ws, ws_bytes)
+                       : smooth_channels_fwd_atomic<T, NI, NO>(st, grid, c.G, P, B, ch, out, points, rot, trans, ow,
+                                                               pw);
+        });
 }
 
 template <typename T>
@@ -590,52 +338,17 @@ static int pullback_smooth_channels_impl(void* stream, int algo, unsigned flags,
                                          const int64_t* grid, int64_t P, int64_t B, int64_t C, const T* g,
                                          const T* points, const T* rot, const T* trans, const T* ow, const T* pw,
                                          T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow, T* d_pw, void* ws,
-                                         size_t ws_bytes) {
-    (void)ws_bytes;
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_channels(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need))
-        return rc;
+                                         size_t) {
+    const SmoothCall c = check_smooth_channels(DPR_OP_PULLBACK, algo, flags, n_in, n_out, grid, P, B, C);
     if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
-    if (B == 0) return DPR_OK;  // (every output is empty)
-    if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (!d_rot || !d_trans || !d_bg || !d_ow) return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
-    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
-        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && !pw) return fail(DPR_ERR_INVALID_ARG, "point_weight is NULL with P > 0 (the channel form needs it)");
-    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    const int64_t planes = B * C;
-    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * n_out * n_in)));
-    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * n_out)));
-    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
-    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)planes));
-    // ds_dbackground[b, c] = sum of plane b * C + c
-    grid_sum(st, g, G, planes, d_bg, Residual<T>{nullptr, T(0), nullptr});
-    stage_mark(st);
-    if (P == 0) return DPR_OK;  // (the per-pose sums are 0, ds_dbackground is done)
-    int64_t slices = 1;
-    const int poses_per_slice = pose_slices(P, B, &slices);  // (the linear atomic pullback's: SUMMATION ORDER, note 1)
-    const int c = (int)C;
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        const int rc = smooth_channels_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
-            st, grid, G, P, B, c, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw, poses_per_slice,
-            slices);
-        stage_mark(st);
-        return rc;
-    });
-}
-
-static size_t workspace_smooth_channels_impl(int op, int algo, unsigned flags, int n_in, int n_out,
-                                             const int64_t* grid, int64_t P, int64_t B, int64_t C) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (check_smooth_channels(op, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need)) return (size_t)-1;
-    return need;
+    return smooth_splat_pullback<T>(
+        kSmoothChannels, c, stream, flags, n_in, n_out, P, B, B * C, B, g, points, nullptr, rot, trans, ow, pw, d_pts,
+        d_rot, d_trans, d_bg, d_ow, d_pw, ws,
+        [&](hipStream_t st, auto ni, auto no, int poses_per_slice, int64_t slices) {
+            return smooth_channels_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, (int)C, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw,
+                poses_per_slice, slices);
+        });
 }
 
 // ---------------------------------------------------------------- smooth sampling of C-channel images
@@ -645,58 +358,43 @@ static size_t workspace_smooth_channels_impl(int op, int algo, unsigned flags, i
 // pose from the tiled smooth channel forward -- one binning per pose for all C channels.
 // AUTO: the forward is ATOMIC; the pullback is TILED where the smooth channel forward of one pose of the shape would
 // be (resolve_algo_smooth_channels; the measured rows: profiles/sample_smooth_channels_probe.txt).
-static int resolve_algo_sample_smooth_channels(int algo, int op, int n_out, const int64_t* grid, int64_t P,
+static int resolve_algo_sample_smooth_channels(int op, int n_out, const int64_t* grid, int64_t P,
                                                int64_t C) {
-    if (algo != DPR_ALGO_AUTO) return algo;
-    if (op == DPR_OP_PULLBACK) return resolve_algo_smooth_channels(DPR_ALGO_AUTO, DPR_OP_RASTER, n_out, grid, P, C);
+    if (op == DPR_OP_PULLBACK) return resolve_algo_smooth_channels(DPR_OP_RASTER, n_out, grid, P, C);
     return DPR_ALGO_ATOMIC;
 }
 
-// the host checks both entry points and the queries share: smooth sampling's, then C and the 64-bit offsets of the
-// channel layouts; *G and the resolved *algo come back, *need: workspace (sample_smooth_workspace_bytes: the tiled
-// smooth forward's for one pose, whatever B and C)
-static int check_sample_smooth_channels(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                        int64_t P, int64_t B, int64_t C, int64_t* G, size_t* need) {
-    if (int rc = check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
-    if (int rc = check_sample_smooth_op(op, flags)) return rc;
-    if (C < 1 || C > kMaxChannels)
-        return fail(DPR_ERR_INVALID_ARG, "channels C = %lld out of range [1, %d]", (long long)C, kMaxChannels);
-    *algo = resolve_algo_sample_smooth_channels(*algo, op, n_out, grid, P, C);
-    *need = sample_smooth_workspace_bytes(op, *algo, n_out, grid, P);
-    if (*need == (size_t)-1) return DPR_ERR_UNSUPPORTED_ALGO;
-    if (int rc = check_sample_sizes(P, B, *G)) return rc;
-    // 64-bit offsets: plane (c, b) starts at (b * C + c) * G, the values of (point p, pose b) at (b * P + p) * C
-    if (B > 0 && (P > ((int64_t)1 << 62) / (B * C) || *G > ((int64_t)1 << 62) / (B * C)))
-        return fail(DPR_ERR_INVALID_ARG, "P * C * B or the image (G * C * B) too large");
-    return DPR_OK;
+constexpr SmoothFamily kSmoothChannelSampling{"smooth channel sampling", kTiledPullback, /*residual_refusal*/ false,
+                                              /*group_plan*/ false, kGroupIgnored, /*has_body*/ false,
+                                              /*needs_point_weight*/ false, /*pullback_slices_poses*/ false};
+
+// (the workspace is the tiled smooth forward's for one pose, whatever B and C)
+static SmoothCall check_sample_smooth_channels(int op, int algo, unsigned flags, int n_in, int n_out,
+                                               const int64_t* grid, int64_t P, int64_t B, int64_t C) {
+    return smooth_checks(
+        kSmoothChannelSampling, op, algo, flags, n_in, n_out, grid, P, B, [&] { return check_channel_count(C); },
+        [&](int64_t G) {
+            if (int rc = check_sample_sizes(P, B, G)) return rc;
+            // 64-bit offsets: plane (c, b) starts at (b * C + c) * G, the values of (point p, pose b) at
+            // (b * P + p) * C
+            if (B > 0 && (P > ((int64_t)1 << 62) / (B * C) || G > ((int64_t)1 << 62) / (B * C)))
+                return fail(DPR_ERR_INVALID_ARG, "P * C * B or the image (G * C * B) too large");
+            return (int)DPR_OK;
+        },
+        [&] { return resolve_algo_sample_smooth_channels(op, n_out, grid, P, C); });
 }
 
 template <typename T>
 static int sample_smooth_channels_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
                                        const int64_t* grid, int64_t P, int64_t B, int64_t C, T* values, const T* image,
-                                       const T* points, const T* rot, const T* trans, void* ws, size_t ws_bytes) {
-    (void)ws_bytes;
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_sample_smooth_channels(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need))
-        return rc;
-    if (P == 0 || B == 0) return DPR_OK;
-    if (!values) return fail(DPR_ERR_INVALID_ARG, "values is NULL");
-    if (!image) return fail(DPR_ERR_INVALID_ARG, "image is NULL");
-    if (!points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (int rc = check_alignment<T>(ws, {values, image, points, rot, trans})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    int64_t slices = 1;
-    const int pps = pose_slices(P, B, &slices);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        const int rc = sample_smooth_channels_fwd<T, decltype(ni)::value, decltype(no)::value>(
-            st, grid, G, P, B, (int)C, values, image, points, rot, trans, pps, slices);
-        stage_mark(st);
-        return rc;
-    });
+                                       const T* points, const T* rot, const T* trans, void* ws, size_t) {
+    const SmoothCall c = check_sample_smooth_channels(DPR_OP_RASTER, algo, flags, n_in, n_out, grid, P, B, C);
+    return smooth_sample_forward<T>(
+        kSmoothChannelSampling, c, stream, n_in, n_out, P, B, values, image, points, nullptr, rot, trans, ws,
+        [&](hipStream_t st, auto ni, auto no, int poses_per_slice, int64_t slices) {
+            return sample_smooth_channels_fwd<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, (int)C, values, image, points, rot, trans, poses_per_slice, slices);
+        });
 }
 
 template <typename T>
@@ -704,62 +402,28 @@ static int sample_smooth_channels_pullback_impl(void* stream, int algo, unsigned
                                                 const int64_t* grid, int64_t P, int64_t B, int64_t C, const T* dv,
                                                 const T* image, const T* points, const T* rot, const T* trans,
                                                 T* d_img, T* d_pts, T* d_rot, T* d_trans, void* ws, size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_sample_smooth_channels(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need))
-        return rc;
-    if (!d_img && !d_pts && !d_rot && !d_trans)
-        return fail(DPR_ERR_INVALID_ARG, "smooth channel sampling pullback: every output is NULL");
-    const bool tiled = algo == DPR_ALGO_TILED;
-    if (tiled && d_img && P > 0 && B > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE,
-                    "DPR_ALGO_TILED smooth channel sampling pullback needs %zu workspace bytes, got %zu", need,
-                    ws ? ws_bytes : (size_t)0);
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && B > 0) {
-        if (!dv) return fail(DPR_ERR_INVALID_ARG, "ds_dvalues is NULL");
-        if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-        if ((d_pts || d_rot || d_trans) && !image)
-            return fail(DPR_ERR_INVALID_ARG, "image is NULL (needed for ds_dpoints / ds_drotation / ds_dtranslation)");
-    }
-    if (int rc = check_alignment<T>(ws, {dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans})) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    if (d_rot) DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * n_out * n_in)));
-    if (d_trans) DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * n_out)));
-    if (d_img) DPR_HIP(zero_async(st, d_img, sizeof(T) * (size_t)(B * C * G)));
-    if (d_pts && B == 0) DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
-    if (P == 0 || B == 0) return DPR_OK;
-    int64_t slices = 1;
-    const int pps = pose_slices(P, B, &slices);
-    const int c = (int)C;
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        if (int rc = sample_smooth_channels_bwd<T, NI, NO>(st, grid, G, P, B, c, dv, image, points, rot, trans,
-                                                           tiled ? nullptr : d_img, d_pts, d_rot, d_trans, pps,
-                                                           slices))
-            return rc;
-        stage_mark(st);
-        if (tiled && d_img) {
-            // the C planes of pose b (zeroed above): the single-pose tiled smooth channel forward of the weights
+    const SmoothCall c = check_sample_smooth_channels(DPR_OP_PULLBACK, algo, flags, n_in, n_out, grid, P, B, C);
+    const int ch = (int)C;
+    return smooth_sample_pullback<T>(
+        kSmoothChannelSampling, c, stream, n_in, n_out, P, B, B * C, B, dv, image, points, nullptr, rot, trans, d_img,
+        d_pts, d_rot, d_trans, ws, ws_bytes,
+        [&](hipStream_t st, auto ni, auto no, T* d_img_atomic, int poses_per_slice, int64_t slices) {
+            return sample_smooth_channels_bwd<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, ch, dv, image, points, rot, trans, d_img_atomic, d_pts, d_rot, d_trans,
+                poses_per_slice, slices);
+        },
+        [&](hipStream_t st, auto ni, auto no) -> int {
+            constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+            // the C planes of pose b: the single-pose tiled smooth channel forward of the weights
             // ds_dvalues[:, :, b] (P x C, contiguous), out_weight 1 -- what
             // dpr_raster_smooth_channels_ex_*(DPR_ALGO_TILED) returns for them
             for (int64_t b = 0; b < B; ++b)
-                if (int rc = smooth_channels_fwd_tiled<T, NI, NO>(st, grid, G, P, 1, c, d_img + b * C * G, points,
+                if (int rc = smooth_channels_fwd_tiled<T, NI, NO>(st, grid, c.G, P, 1, ch, d_img + b * C * c.G, points,
                                                                   rot + b * (NO * NI), trans + b * NO, nullptr,
                                                                   dv + b * P * C, ws, ws_bytes))
                     return rc;
-        }
-        return DPR_OK;
-    });
-}
-
-static size_t workspace_sample_smooth_channels_impl(int op, int algo, unsigned flags, int n_in, int n_out,
-                                                    const int64_t* grid, int64_t P, int64_t B, int64_t C) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (check_sample_smooth_channels(op, &algo, flags, n_in, n_out, grid, P, B, C, &G, &need)) return (size_t)-1;
-    return need;
+            return DPR_OK;
+        });
 }
 
 }  // namespace dpr
@@ -767,17 +431,13 @@ static size_t workspace_sample_smooth_channels_impl(int op, int algo, unsigned f
 extern "C" {
 
 int dpr_resolve_algo_smooth(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    int64_t G = 0;
-    if (int rc = dpr::check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = dpr::check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = dpr::check_smooth(op, 0u)) return rc;
-    return dpr::resolve_algo_smooth(DPR_ALGO_AUTO, op, n_out, grid, P);
+    return dpr::resolver_value(dpr::check_smooth_splat(false, op, DPR_ALGO_AUTO, 0u, n_in, n_out, grid, P, B));
 }
 
 #define DPR_DEFINE_SMOOTH(SUF, T)                                                                              \
     size_t dpr_workspace_bytes_smooth_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,          \
                                                const int64_t* grid, int64_t P, int64_t B) {                    \
-        return dpr::workspace_smooth_impl<T>(op, algo, flags, n_in, n_out, grid, P, B);                        \
+        return dpr::query_value(dpr::check_smooth_splat(false, op, algo, flags, n_in, n_out, grid, P, B));     \
     }                                                                                                          \
     int dpr_raster_smooth_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,                \
                                    const int64_t* grid, int64_t P, int64_t B, T* out, const T* points,         \
@@ -803,17 +463,13 @@ DPR_DEFINE_SMOOTH(f64, double)
 #undef DPR_DEFINE_SMOOTH
 
 int dpr_resolve_algo_sample_smooth(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    int64_t G = 0;
-    if (int rc = dpr::check_smooth_dims(n_in, n_out)) return rc;
-    if (int rc = dpr::check_common(n_in, n_out, grid, P, B, &G)) return rc;
-    if (int rc = dpr::check_sample_smooth_op(op, 0u)) return rc;
-    return dpr::resolve_algo_sample_smooth(DPR_ALGO_AUTO, op, n_out, grid, P);
+    return dpr::resolver_value(dpr::check_sample_smooth(true, op, DPR_ALGO_AUTO, 0u, n_in, n_out, grid, P, B));
 }
 
 #define DPR_DEFINE_SAMPLE_SMOOTH(SUF, T)                                                                       \
     size_t dpr_workspace_bytes_sample_smooth_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,   \
                                                       const int64_t* grid, int64_t P, int64_t B) {             \
-        return dpr::workspace_sample_smooth_impl<T>(op, algo, flags, n_in, n_out, grid, P, B);                 \
+        return dpr::query_value(dpr::check_sample_smooth(false, op, algo, flags, n_in, n_out, grid, P, B));    \
     }                                                                                                          \
     int dpr_sample_smooth_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,                \
                                    const int64_t* grid, int64_t P, int64_t B, T* values, const T* image,       \
@@ -838,17 +494,13 @@ DPR_DEFINE_SAMPLE_SMOOTH(f64, double)
 #undef DPR_DEFINE_SAMPLE_SMOOTH
 
 int dpr_resolve_algo_smooth_jvp(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t K) {
-    int64_t G = 0;
-    size_t need = 0;
-    int algo = DPR_ALGO_AUTO;
-    if (int rc = dpr::check_smooth_jvp(&algo, 0u, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
-    return algo;
+    return dpr::resolver_value(dpr::check_smooth_jvp(DPR_ALGO_AUTO, 0u, n_in, n_out, grid, P, B, K));
 }
 
 #define DPR_DEFINE_SMOOTH_JVP(SUF, T)                                                                          \
     size_t dpr_workspace_bytes_smooth_jvp_ex_##SUF(int algo, unsigned flags, int n_in, int n_out,              \
                                                    const int64_t* grid, int64_t P, int64_t B, int64_t K) {     \
-        return dpr::workspace_smooth_jvp_impl(algo, flags, n_in, n_out, grid, P, B, K);                        \
+        return dpr::query_value(dpr::check_smooth_jvp(algo, flags, n_in, n_out, grid, P, B, K));               \
     }                                                                                                          \
     int dpr_raster_smooth_jvp_ex_##SUF(                                                                        \
         void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, \
@@ -867,17 +519,13 @@ DPR_DEFINE_SMOOTH_JVP(f64, double)
 #undef DPR_DEFINE_SMOOTH_JVP
 
 int dpr_resolve_algo_smooth_clouds(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    int64_t G = 0;
-    size_t need = 0;
-    int algo = DPR_ALGO_AUTO;
-    if (int rc = dpr::check_smooth_clouds(op, &algo, 0u, n_in, n_out, grid, P, B, &G, &need)) return rc;
-    return algo;
+    return dpr::resolver_value(dpr::check_smooth_clouds(op, DPR_ALGO_AUTO, 0u, n_in, n_out, grid, P, B));
 }
 
 #define DPR_DEFINE_SMOOTH_CLOUDS(SUF, T)                                                                       \
     size_t dpr_workspace_bytes_smooth_clouds_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,   \
                                                       const int64_t* grid, int64_t P, int64_t B) {             \
-        return dpr::workspace_smooth_clouds_impl(op, algo, flags, n_in, n_out, grid, P, B);                    \
+        return dpr::query_value(dpr::check_smooth_clouds(op, algo, flags, n_in, n_out, grid, P, B));           \
     }                                                                                                          \
     int dpr_raster_smooth_clouds_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,         \
                                           const int64_t* grid, int64_t P, int64_t B, T* out, const T* points,  \
@@ -905,17 +553,13 @@ DPR_DEFINE_SMOOTH_CLOUDS(f64, double)
 
 int dpr_resolve_algo_smooth_channels(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
                                      int64_t C) {
-    int64_t G = 0;
-    size_t need = 0;
-    int algo = DPR_ALGO_AUTO;
-    if (int rc = dpr::check_smooth_channels(op, &algo, 0u, n_in, n_out, grid, P, B, C, &G, &need)) return rc;
-    return algo;
+    return dpr::resolver_value(dpr::check_smooth_channels(op, DPR_ALGO_AUTO, 0u, n_in, n_out, grid, P, B, C));
 }
 
 #define DPR_DEFINE_SMOOTH_CHANNELS(SUF, T)                                                                     \
     size_t dpr_workspace_bytes_smooth_channels_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out, \
                                                         const int64_t* grid, int64_t P, int64_t B, int64_t C) { \
-        return dpr::workspace_smooth_channels_impl(op, algo, flags, n_in, n_out, grid, P, B, C);               \
+        return dpr::query_value(dpr::check_smooth_channels(op, algo, flags, n_in, n_out, grid, P, B, C));      \
     }                                                                                                          \
     int dpr_raster_smooth_channels_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,       \
                                             const int64_t* grid, int64_t P, int64_t B, int64_t C, T* out,      \
@@ -943,18 +587,16 @@ DPR_DEFINE_SMOOTH_CHANNELS(f64, double)
 
 int dpr_resolve_algo_sample_smooth_channels(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
                                             int64_t C) {
-    int64_t G = 0;
-    size_t need = 0;
-    int algo = DPR_ALGO_AUTO;
-    if (int rc = dpr::check_sample_smooth_channels(op, &algo, 0u, n_in, n_out, grid, P, B, C, &G, &need)) return rc;
-    return algo;
+    return dpr::resolver_value(
+        dpr::check_sample_smooth_channels(op, DPR_ALGO_AUTO, 0u, n_in, n_out, grid, P, B, C));
 }
 
 #define DPR_DEFINE_SAMPLE_SMOOTH_CHANNELS(SUF, T)                                                              \
     size_t dpr_workspace_bytes_sample_smooth_channels_ex_##SUF(int op, int algo, unsigned flags, int n_in,     \
                                                                int n_out, const int64_t* grid, int64_t P,      \
                                                                int64_t B, int64_t C) {                         \
-        return dpr::workspace_sample_smooth_channels_impl(op, algo, flags, n_in, n_out, grid, P, B, C);        \
+        return dpr::query_value(                                                                               \
+            dpr::check_sample_smooth_channels(op, algo, flags, n_in, n_out, grid, P, B, C));                   \
     }                                                                                                          \
     int dpr_sample_smooth_channels_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,       \
                                             const int64_t* grid, int64_t P, int64_t B, int64_t C, T* values,   \

@@ -1,15 +1,22 @@
-// The smooth rigid-body entry points of libdpr -- splat, pullback, forward mode and sampling: host checks, AUTO rules
-// and C ABI (include/dpr.h, "SMOOTH SPLAT, RIGID BODIES", "SMOOTH SPLAT, RIGID BODIES, FORWARD MODE" and "SMOOTH
-// SAMPLING, RIGID BODIES"; core: dpr_api.hip; kernels and their launches: dpr_smooth_bodies.hip,
-// dpr_sample_smooth_bodies.hip).
+// The smooth rigid-body entry points of libdpr -- splat, pullback, forward mode and sampling: what each family is, its
+// AUTO rule, its extent and size bounds, and the C ABI (include/dpr.h, "SMOOTH SPLAT, RIGID BODIES", "SMOOTH SPLAT,
+// RIGID BODIES, FORWARD MODE" and "SMOOTH SAMPLING, RIGID BODIES").  The checks, pointer checks, stream prologues and
+// entry-point skeletons shared with the other smooth families: dpr_host_smooth.h (core: dpr_api.hip; kernels and their
+// launches: dpr_smooth_bodies.hip, dpr_sample_smooth_bodies.hip).  Point p is seen in image b through pose
+// b * K + body[p]: B images, B * K poses.
 #include <hip/hip_runtime.h>
 
-#include "dpr_host.h"
-#include "dpr_smooth.h"
+#include "dpr_host_smooth.h"
 
 namespace dpr {
 
-// ---------------------------------------------------------------- host checks
+// ---------------------------------------------------------------- smooth splat of rigid bodies
+// DPR_ALGO_ATOMIC: forward and pullback; DPR_ALGO_TILED: forward, the images binned in groups
+// (DPR_FLAG_MAX_POSE_GROUP; the pullback forms none and refuses the flag).
+constexpr SmoothFamily kSmoothBodies{"smooth rigid bodies", kTiledForward, /*residual_refusal*/ true,
+                                     /*group_plan*/ true, kGroupRefusedOffTiledOp, /*has_body*/ true,
+                                     /*needs_point_weight*/ false, /*pullback_slices_poses*/ true};
+
 // AUTO (dpr_resolve_algo_smooth_bodies), from the shape alone.  The pullback is DPR_ALGO_ATOMIC.  The forward is
 // DPR_ALGO_TILED where the default GROUP of images holds bg * P >= the constant below and the cloud holds at least
 // kSmoothBodiesTiledMinPointsPerTile points per tile of the grid, DPR_ALGO_ATOMIC otherwise: the shape of
@@ -26,8 +33,7 @@ namespace dpr {
 constexpr int64_t kSmoothBodiesTiledMinWork3D = 100000;
 constexpr int64_t kSmoothBodiesTiledMinWork2D = 160000;
 constexpr int64_t kSmoothBodiesTiledMinPointsPerTile = 4;
-static int resolve_algo_smooth_bodies(int algo, int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    if (algo != DPR_ALGO_AUTO) return algo;
+static int resolve_algo_smooth_bodies(int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
     if (op != DPR_OP_RASTER) return DPR_ALGO_ATOMIC;
     const int64_t bg = smooth_clouds_group(n_out, grid, P, B, 0);
     if (bg == 0) return DPR_ALGO_ATOMIC;
@@ -36,43 +42,12 @@ static int resolve_algo_smooth_bodies(int algo, int op, int n_out, const int64_t
     return bg * P >= min_work && P / kSmoothBodiesTiledMinPointsPerTile >= tiles ? DPR_ALGO_TILED : DPR_ALGO_ATOMIC;
 }
 
-// Every refusal of the family, shared by the entry points, the workspace query and dpr_resolve_algo_smooth_bodies;
-// *G, the resolved *algo and the workspace bytes *need come back.
-static int check_smooth_bodies(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                               int64_t B, int64_t K, int64_t* G, size_t* need) {
-    // (a pair outside the three is refused before the grid is looked at)
-    if (!smooth_dims_supported(n_in, n_out))
-        return fail(DPR_ERR_UNSUPPORTED_DIMS,
-                    "smooth rigid bodies: (n_in, n_out) = (%d, %d); supports (2,2), (3,3), (3,2)", n_in, n_out);
-    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
-    if (op == DPR_OP_RESIDUAL_PULLBACK)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "smooth rigid bodies have no residual pullback");
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
-        return fail(DPR_ERR_INVALID_ARG, "smooth bodies: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK", op);
-    if (K < 1) return fail(DPR_ERR_INVALID_ARG, "K = %lld: a call needs at least one body", (long long)K);
-    // the kernels compare a body index with K as 32-bit values and count poses b * K + k in 64 bits; the zeroing of
-    // the B * K pose gradients and their offsets stay far inside both with this bound
-    if (K > 0x7fffffffLL || (B > 0 && K > 0x7fffffffLL / B))
-        return fail(DPR_ERR_INVALID_ARG, "B * K = %lld * %lld poses exceed 2^31 - 1", (long long)B, (long long)K);
-    if (int rc = check_point_blocks(P)) return rc;
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "smooth rigid bodies keep / reuse no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    if (op == DPR_OP_PULLBACK && (flags & 0xff00u))
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "the smooth rigid-body pullback forms no groups of images (DPR_FLAG_MAX_POSE_GROUP)");
-    if (*algo != DPR_ALGO_AUTO && *algo != DPR_ALGO_ATOMIC && *algo != DPR_ALGO_TILED)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "smooth rigid bodies run on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d", *algo);
-    if (*algo == DPR_ALGO_TILED && op != DPR_OP_RASTER)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth rigid-body pullback runs on DPR_ALGO_ATOMIC only");
-    *algo = resolve_algo_smooth_bodies(*algo, op, n_out, grid, P, B);
-    *need = 0;
-    if (*algo == DPR_ALGO_TILED) {
-        *need = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, max_pose_group(flags));
-        if (*need == (size_t)-1) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    }
-    return DPR_OK;
+static SmoothCall check_smooth_bodies(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                      int64_t P, int64_t B, int64_t K) {
+    return smooth_checks(
+        kSmoothBodies, op, algo, flags, n_in, n_out, grid, P, B, [&] { return check_body_count(B, K); },
+        [&](int64_t) { return check_point_blocks(P); },
+        [&] { return resolve_algo_smooth_bodies(op, n_out, grid, P, B); });
 }
 
 template <typename T>
@@ -80,34 +55,17 @@ static int raster_smooth_bodies_impl(void* stream, int algo, unsigned flags, int
                                      int64_t P, int64_t B, int64_t K, T* out, const T* points, const int32_t* body,
                                      const T* rot, const T* trans, const T* bg, const T* ow, const T* pw, void* ws,
                                      size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_bodies(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
-    if (B == 0) return DPR_OK;
-    if (!out) return fail(DPR_ERR_INVALID_ARG, "out is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
-    if (P > 0 && (!rot || !trans)) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "smooth rigid bodies (algorithm %d) need %zu workspace bytes, got %zu", algo,
-                    need, ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out, points, rot, trans, bg, ow, pw})) return rc;
-    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    fill_background(st, out, G, B, bg);
-    stage_mark(st);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_bodies_fwd_tiled<T, NI, NO>(st, grid, G, P, B, (int)K,
-                                                                max_pose_group(flags), out, points, body, rot,
-                                                                trans, ow, pw, ws, ws_bytes)
-                           : smooth_bodies_fwd_atomic<T, NI, NO>(st, grid, G, P, B, (int)K, out, points, body, rot,
-                                                                 trans, ow, pw);
-        stage_mark(st);
-        return rc;
-    });
+    const SmoothCall c = check_smooth_bodies(DPR_OP_RASTER, algo, flags, n_in, n_out, grid, P, B, K);
+    return smooth_splat_forward<T>(
+        kSmoothBodies, c, stream, n_in, n_out, P, B, B, out, points, body, rot, trans, bg, ow, pw, ws, ws_bytes,
+        [&](hipStream_t st, auto ni, auto no) {
+            constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+            return c.algo == DPR_ALGO_TILED
+                       ? smooth_bodies_fwd_tiled<T, NI, NO>(st, grid, c.G, P, B, (int)K, max_pose_group(flags), out,
+                                                            points, body, rot, trans, ow, pw, ws, ws_bytes)
+                       : smooth_bodies_fwd_atomic<T, NI, NO>(st, grid, c.G, P, B, (int)K, out, points, body, rot,
+                                                             trans, ow, pw);
+        });
 }
 
 template <typename T>
@@ -116,51 +74,24 @@ static int pullback_smooth_bodies_impl(void* stream, int algo, unsigned flags, i
                                        const T* points, const int32_t* body, const T* rot, const T* trans,
                                        const T* ow, const T* pw, T* d_pts, T* d_rot, T* d_trans, T* d_bg, T* d_ow,
                                        T* d_pw, void* ws) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_bodies(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
+    const SmoothCall c = check_smooth_bodies(DPR_OP_PULLBACK, algo, flags, n_in, n_out, grid, P, B, K);
     if (flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD) d_pw = nullptr;
-    if (P > 0 && (!d_pts || (!d_pw && !(flags & DPR_FLAG_NO_POINT_WEIGHT_GRAD))))
-        return fail(DPR_ERR_INVALID_ARG, "ds_dpoints/ds_dpoint_weight is NULL with P > 0");
-    if (B > 0) {
-        if (!g) return fail(DPR_ERR_INVALID_ARG, "ds_dout is NULL");
-        if (!d_rot || !d_trans || !d_bg || !d_ow)
-            return fail(DPR_ERR_INVALID_ARG, "a per-pose output pointer is NULL");
-        if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-        if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
-        if (P > 0 && (!rot || !trans)) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL with P > 0");
-    }
-    if (int rc = check_alignment<T>(ws, {g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_bg, d_ow, d_pw}))
-        return rc;
-    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    if (B == 0) {  // no image: the sums over the images are empty
-        if (P > 0) {
-            DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
-            if (d_pw) DPR_HIP(zero_async(st, d_pw, sizeof(T) * (size_t)P));
-        }
-        return DPR_OK;
-    }
-    DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * K * n_out * n_in)));
-    DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * K * n_out)));
-    DPR_HIP(zero_async(st, d_ow, sizeof(T) * (size_t)B));
-    DPR_HIP(zero_async(st, d_bg, sizeof(T) * (size_t)B));
-    grid_sum(st, g, G, B, d_bg, Residual<T>{nullptr, T(0), nullptr});
-    stage_mark(st);
-    if (P == 0) return DPR_OK;  // (the pose sums are 0, ds_dbackground is done)
-    int64_t slices = 1;
-    const int poses_per_slice = pose_slices(P, B, &slices);  // (the smooth pullback's: SUMMATION ORDER, note 1)
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        const int rc = smooth_bodies_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
-            st, grid, G, P, B, (int)K, g, points, body, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw,
-            poses_per_slice, slices);
-        stage_mark(st);
-        return rc;
-    });
+    return smooth_splat_pullback<T>(
+        kSmoothBodies, c, stream, flags, n_in, n_out, P, B, B, B * K, g, points, body, rot, trans, ow, pw, d_pts,
+        d_rot, d_trans, d_bg, d_ow, d_pw, ws,
+        [&](hipStream_t st, auto ni, auto no, int poses_per_slice, int64_t slices) {
+            return smooth_bodies_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, (int)K, g, points, body, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw,
+                poses_per_slice, slices);
+        });
 }
 
-// ---------------------------------------------------------------- forward mode: host checks and entry point
+// ---------------------------------------------------------------- forward mode
+// DPR_ALGO_ATOMIC and DPR_ALGO_TILED; DPR_FLAG_MAX_POSE_GROUP sizes the groups of a TILED call.
+constexpr SmoothFamily kSmoothBodiesJvp{"smooth rigid-body JVP", kTiledOnlyOp, /*residual_refusal*/ false,
+                                        /*group_plan*/ true, kGroupIgnored, /*has_body*/ true,
+                                        /*needs_point_weight*/ false, /*pullback_slices_poses*/ false};
+
 // AUTO (dpr_resolve_algo_smooth_bodies_jvp), from the shape and V alone: the forward's rule -- DPR_ALGO_TILED where the
 // default GROUP holds enough work and the cloud at least 4 points per tile -- with the group's work counted as
 // bg * P * V^2.  The rule started as the forward's with bg * P * V (what dpr_resolve_algo_smooth_jvp does with P * K);
@@ -181,8 +112,7 @@ static int pullback_smooth_bodies_impl(void* stream, int algo, unsigned flags, i
 constexpr int64_t kSmoothBodiesJvpTiledMinWork3D = 96000;
 constexpr int64_t kSmoothBodiesJvpTiledMinWork2D = 160000;
 constexpr int64_t kSmoothBodiesJvpTiledMinPointsPerTile = 4;
-static int resolve_algo_smooth_bodies_jvp(int algo, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t V) {
-    if (algo != DPR_ALGO_AUTO) return algo;
+static int resolve_algo_smooth_bodies_jvp(int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t V) {
     const int64_t bg = smooth_clouds_group(n_out, grid, P, B, 0);
     if (bg == 0) return DPR_ALGO_ATOMIC;
     const int64_t min_work = n_out == 3 ? kSmoothBodiesJvpTiledMinWork3D : kSmoothBodiesJvpTiledMinWork2D;
@@ -192,31 +122,19 @@ static int resolve_algo_smooth_bodies_jvp(int algo, int n_out, const int64_t* gr
                                                                                           : DPR_ALGO_ATOMIC;
 }
 
-// Every refusal of the forward-mode entry points, shared by them, the workspace query and
-// dpr_resolve_algo_smooth_bodies_jvp; *G, the resolved *algo and the workspace bytes *need come back.
-static int check_smooth_bodies_jvp(int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P,
-                                   int64_t B, int64_t K, int64_t V, int64_t* G, size_t* need) {
-    if (!smooth_dims_supported(n_in, n_out))
-        return fail(DPR_ERR_UNSUPPORTED_DIMS,
-                    "smooth rigid bodies, forward mode: (n_in, n_out) = (%d, %d); supports (2,2), (3,3), (3,2)", n_in,
-                    n_out);
-    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
-    if (K < 1) return fail(DPR_ERR_INVALID_ARG, "K = %lld: a call needs at least one body", (long long)K);
-    if (K > 0x7fffffffLL || (B > 0 && K > 0x7fffffffLL / B))
-        return fail(DPR_ERR_INVALID_ARG, "B * K = %lld * %lld poses exceed 2^31 - 1", (long long)B, (long long)K);
-    if (int rc = check_jvp(V, flags)) return rc;  // (V in 1 .. kMaxTangents; KEEP / REUSE refused)
-    if (int rc = check_sample_sizes(P, B, *G)) return rc;
-    if (B > 0 && *G * V > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "output too large");
-    if (*algo != DPR_ALGO_AUTO && *algo != DPR_ALGO_ATOMIC && *algo != DPR_ALGO_TILED)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "the smooth rigid-body JVP runs on DPR_ALGO_ATOMIC and DPR_ALGO_TILED, not algorithm %d", *algo);
-    *algo = resolve_algo_smooth_bodies_jvp(*algo, n_out, grid, P, B, V);
-    *need = 0;
-    if (*algo == DPR_ALGO_TILED) {
-        *need = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, max_pose_group(flags));
-        if (*need == (size_t)-1) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    }
-    return DPR_OK;
+static SmoothCall check_smooth_bodies_jvp(int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                          int64_t P, int64_t B, int64_t K, int64_t V) {
+    return smooth_checks(
+        kSmoothBodiesJvp, DPR_OP_RASTER, algo, flags, n_in, n_out, grid, P, B,
+        [&] {
+            if (int rc = check_body_count(B, K)) return rc;
+            return check_jvp(V, 0u);  // (V in 1 .. kMaxTangents)
+        },
+        [&](int64_t G) {
+            if (int rc = check_sample_sizes(P, B, G)) return rc;
+            return check_plane_offsets(G, V, B);
+        },
+        [&] { return resolve_algo_smooth_bodies_jvp(n_out, grid, P, B, V); });
 }
 
 template <typename T>
@@ -225,39 +143,18 @@ static int raster_smooth_bodies_jvp_impl(void* stream, int algo, unsigned flags,
                                          const T* points, const int32_t* body, const T* rot, const T* trans,
                                          const T* ow, const T* pw, JvpTangents<T> tan, const T* bg_dot, void* ws,
                                          size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_smooth_bodies_jvp(&algo, flags, n_in, n_out, grid, P, B, K, V, &G, &need)) return rc;
-    if (B == 0) return DPR_OK;
-    if (!out_dot) return fail(DPR_ERR_INVALID_ARG, "out_dot is NULL");
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
-    if (P > 0 && (!rot || !trans)) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL with P > 0");
-    if (P > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE, "smooth rigid bodies JVP (algorithm %d) needs %zu workspace bytes, got %zu",
-                    algo, need, ws ? ws_bytes : (size_t)0);
-    if (int rc = check_alignment<T>(ws, {out_dot, points, rot, trans, ow, pw, tan.points, tan.rot, tan.trans, tan.ow,
-                                         tan.pw, bg_dot}))
-        return rc;
-    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    // the background tangent (or 0) into every plane; then the deposits, where any other tangent is given
-    jvp_fill(st, out_dot, G, (int)V, B, bg_dot);
-    stage_mark(st);
-    DPR_HIP(hipGetLastError());
-    if (P == 0 || !(tan.points || tan.rot || tan.trans || tan.ow || tan.pw)) return DPR_OK;
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        const int rc = algo == DPR_ALGO_TILED
-                           ? smooth_bodies_jvp_tiled<T, NI, NO>(st, grid, G, P, B, (int)K, (int)V,
-                                                                max_pose_group(flags), out_dot, points, body,
-                                                                rot, trans, ow, pw, tan, ws, ws_bytes)
-                           : smooth_bodies_jvp_atomic<T, NI, NO>(st, grid, G, P, B, (int)K, (int)V, out_dot, points,
-                                                                 body, rot, trans, ow, pw, tan);
-        stage_mark(st);
-        return rc;
-    });
+    const SmoothCall c = check_smooth_bodies_jvp(algo, flags, n_in, n_out, grid, P, B, K, V);
+    return smooth_jvp_forward<T>(
+        kSmoothBodiesJvp, c, stream, n_in, n_out, P, B, V, out_dot, points, body, rot, trans, ow, pw, tan, bg_dot, ws,
+        ws_bytes, [&](hipStream_t st, auto ni, auto no) {
+            constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
+            return c.algo == DPR_ALGO_TILED
+                       ? smooth_bodies_jvp_tiled<T, NI, NO>(st, grid, c.G, P, B, (int)K, (int)V,
+                                                            max_pose_group(flags), out_dot, points, body, rot, trans,
+                                                            ow, pw, tan, ws, ws_bytes)
+                       : smooth_bodies_jvp_atomic<T, NI, NO>(st, grid, c.G, P, B, (int)K, (int)V, out_dot, points,
+                                                             body, rot, trans, ow, pw, tan);
+        });
 }
 
 // ---------------------------------------------------------------- smooth sampling at the points of rigid bodies
@@ -267,75 +164,35 @@ static int raster_smooth_bodies_jvp_impl(void* stream, int algo, unsigned flags,
 // images through the binning of the tiled smooth rigid-body forward.
 // AUTO: the forward is ATOMIC; the pullback is TILED exactly where the smooth rigid-body forward of the shape would
 // be (resolve_algo_smooth_bodies above; dpr_resolve_algo_sample_smooth's precedent).
-static int resolve_algo_sample_smooth_bodies(int algo, int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
-    if (algo != DPR_ALGO_AUTO) return algo;
+static int resolve_algo_sample_smooth_bodies(int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
     if (op != DPR_OP_PULLBACK) return DPR_ALGO_ATOMIC;
-    return resolve_algo_smooth_bodies(DPR_ALGO_AUTO, DPR_OP_RASTER, n_out, grid, P, B);
+    return resolve_algo_smooth_bodies(DPR_OP_RASTER, n_out, grid, P, B);
 }
 
-// Every refusal of the family, shared by the entry points, the workspace query and
-// dpr_resolve_algo_sample_smooth_bodies; *G, the resolved *algo and the workspace bytes *need come back.
-static int check_sample_smooth_bodies(int op, int* algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
-                                      int64_t P, int64_t B, int64_t K, int64_t* G, size_t* need) {
-    if (!smooth_dims_supported(n_in, n_out))
-        return fail(DPR_ERR_UNSUPPORTED_DIMS,
-                    "smooth rigid-body sampling: (n_in, n_out) = (%d, %d); supports (2,2), (3,3), (3,2)", n_in, n_out);
-    if (int rc = check_common(n_in, n_out, grid, P, B, G)) return rc;
-    if (op != DPR_OP_RASTER && op != DPR_OP_PULLBACK)
-        return fail(DPR_ERR_INVALID_ARG, "smooth rigid-body sampling: op %d is not DPR_OP_RASTER / DPR_OP_PULLBACK",
-                    op);
-    if (K < 1) return fail(DPR_ERR_INVALID_ARG, "K = %lld: a call needs at least one body", (long long)K);
-    if (K > 0x7fffffffLL || (B > 0 && K > 0x7fffffffLL / B))  // (check_smooth_bodies' bound, for its reasons)
-        return fail(DPR_ERR_INVALID_ARG, "B * K = %lld * %lld poses exceed 2^31 - 1", (long long)B, (long long)K);
-    if (int rc = check_point_blocks(P)) return rc;
-    if (flags & 3u)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "smooth rigid-body sampling keeps / reuses no binning (DPR_FLAG_KEEP_BINNING / REUSE_BINNING)");
-    if (*algo != DPR_ALGO_AUTO && *algo != DPR_ALGO_ATOMIC && *algo != DPR_ALGO_TILED)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "smooth rigid-body sampling runs on DPR_ALGO_ATOMIC and, the pullback, DPR_ALGO_TILED, not "
-                    "algorithm %d", *algo);
-    if (*algo == DPR_ALGO_TILED && op != DPR_OP_PULLBACK)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO, "the smooth rigid-body sampling forward runs on DPR_ALGO_ATOMIC only");
-    *algo = resolve_algo_sample_smooth_bodies(*algo, op, n_out, grid, P, B);
-    if ((flags & 0xff00u) && *algo != DPR_ALGO_TILED)
-        return fail(DPR_ERR_UNSUPPORTED_ALGO,
-                    "smooth rigid-body sampling forms groups of images on the DPR_ALGO_TILED pullback only "
-                    "(DPR_FLAG_MAX_POSE_GROUP)");
-    *need = 0;
-    if (*algo == DPR_ALGO_TILED) {
-        *need = smooth_clouds_tiled_workspace_bytes(n_out, grid, P, B, max_pose_group(flags));
-        if (*need == (size_t)-1) return fail(DPR_ERR_UNSUPPORTED_ALGO, kSmoothTiledRefused);
-    }
-    return check_sample_sizes(P, B, *G);
+// (DPR_FLAG_MAX_POSE_GROUP sizes the groups of a TILED pullback; every other call refuses it)
+constexpr SmoothFamily kSmoothBodySampling{"smooth rigid-body sampling", kTiledPullback, /*residual_refusal*/ false,
+                                           /*group_plan*/ true, kGroupRefusedOffTiled, /*has_body*/ true,
+                                           /*needs_point_weight*/ false, /*pullback_slices_poses*/ false};
+
+static SmoothCall check_sample_smooth_bodies(int op, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t* grid, int64_t P, int64_t B, int64_t K) {
+    return smooth_checks(
+        kSmoothBodySampling, op, algo, flags, n_in, n_out, grid, P, B, [&] { return check_body_count(B, K); },
+        [&](int64_t G) { return check_sample_sizes(P, B, G); },
+        [&] { return resolve_algo_sample_smooth_bodies(op, n_out, grid, P, B); });
 }
 
 template <typename T>
 static int sample_smooth_bodies_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
                                      int64_t P, int64_t B, int64_t K, T* values, const T* image, const T* points,
                                      const int32_t* body, const T* rot, const T* trans, void* ws) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_sample_smooth_bodies(DPR_OP_RASTER, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need))
-        return rc;
-    if (P == 0 || B == 0) return DPR_OK;
-    if (!values) return fail(DPR_ERR_INVALID_ARG, "values is NULL");
-    if (!image) return fail(DPR_ERR_INVALID_ARG, "image is NULL");
-    if (!points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (!body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
-    if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-    if (int rc = check_alignment<T>(ws, {values, image, points, rot, trans})) return rc;
-    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    int64_t slices = 1;
-    const int pps = pose_slices(P, B, &slices);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        const int rc = sample_smooth_bodies_fwd<T, decltype(ni)::value, decltype(no)::value>(
-            st, grid, G, P, B, (int)K, values, image, points, body, rot, trans, pps, slices);
-        stage_mark(st);
-        return rc;
-    });
+    const SmoothCall c = check_sample_smooth_bodies(DPR_OP_RASTER, algo, flags, n_in, n_out, grid, P, B, K);
+    return smooth_sample_forward<T>(
+        kSmoothBodySampling, c, stream, n_in, n_out, P, B, values, image, points, body, rot, trans, ws,
+        [&](hipStream_t st, auto ni, auto no, int poses_per_slice, int64_t slices) {
+            return sample_smooth_bodies_fwd<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, (int)K, values, image, points, body, rot, trans, poses_per_slice, slices);
+        });
 }
 
 template <typename T>
@@ -344,48 +201,19 @@ static int sample_smooth_bodies_pullback_impl(void* stream, int algo, unsigned f
                                               const T* image, const T* points, const int32_t* body, const T* rot,
                                               const T* trans, T* d_img, T* d_pts, T* d_rot, T* d_trans, void* ws,
                                               size_t ws_bytes) {
-    int64_t G = 0;
-    size_t need = 0;
-    if (int rc = check_sample_smooth_bodies(DPR_OP_PULLBACK, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need))
-        return rc;
-    if (!d_img && !d_pts && !d_rot && !d_trans)
-        return fail(DPR_ERR_INVALID_ARG, "smooth rigid-body sampling pullback: every output is NULL");
-    const bool tiled = algo == DPR_ALGO_TILED;
-    if (tiled && d_img && P > 0 && B > 0 && need > 0 && (!ws || ws_bytes < need))
-        return fail(DPR_ERR_WORKSPACE,
-                    "DPR_ALGO_TILED smooth rigid-body sampling pullback needs %zu workspace bytes, got %zu", need,
-                    ws ? ws_bytes : (size_t)0);
-    if (P > 0 && !points) return fail(DPR_ERR_INVALID_ARG, "points is NULL with P > 0");
-    if (P > 0 && !body) return fail(DPR_ERR_INVALID_ARG, "body is NULL with P > 0");
-    if (P > 0 && B > 0) {
-        if (!dv) return fail(DPR_ERR_INVALID_ARG, "ds_dvalues is NULL");
-        if (!rot || !trans) return fail(DPR_ERR_INVALID_ARG, "rotation/translation is NULL");
-        if ((d_pts || d_rot || d_trans) && !image)
-            return fail(DPR_ERR_INVALID_ARG, "image is NULL (needed for ds_dpoints / ds_drotation / ds_dtranslation)");
-    }
-    if (int rc = check_alignment<T>(ws, {dv, image, points, rot, trans, d_img, d_pts, d_rot, d_trans})) return rc;
-    if ((uintptr_t)body & 3) return fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)");
-    hipStream_t st = (hipStream_t)stream;
-    stage_mark(st);
-    if (d_rot) DPR_HIP(zero_async(st, d_rot, sizeof(T) * (size_t)(B * K * n_out * n_in)));
-    if (d_trans) DPR_HIP(zero_async(st, d_trans, sizeof(T) * (size_t)(B * K * n_out)));
-    if (d_img) DPR_HIP(zero_async(st, d_img, sizeof(T) * (size_t)(B * G)));
-    if (d_pts && B == 0) DPR_HIP(zero_async(st, d_pts, sizeof(T) * (size_t)(P * n_in)));
-    if (P == 0 || B == 0) return DPR_OK;
-    int64_t slices = 1;
-    const int pps = pose_slices(P, B, &slices);
-    return with_smooth_dims(n_in, n_out, [&](auto ni, auto no) -> int {
-        constexpr int NI = decltype(ni)::value, NO = decltype(no)::value;
-        if (int rc = sample_smooth_bodies_bwd<T, NI, NO>(st, grid, G, P, B, (int)K, dv, image, points, body, rot,
-                                                         trans, tiled ? nullptr : d_img, d_pts, d_rot, d_trans, pps,
-                                                         slices))
-            return rc;
-        stage_mark(st);
-        if (tiled && d_img)  // (the planes are zeroed above)
-            return sample_smooth_bodies_image_tiled<T, NI, NO>(st, grid, G, P, B, (int)K, max_pose_group(flags),
-                                                               d_img, dv, points, body, rot, trans, ws, ws_bytes);
-        return DPR_OK;
-    });
+    const SmoothCall c = check_sample_smooth_bodies(DPR_OP_PULLBACK, algo, flags, n_in, n_out, grid, P, B, K);
+    return smooth_sample_pullback<T>(
+        kSmoothBodySampling, c, stream, n_in, n_out, P, B, B, B * K, dv, image, points, body, rot, trans, d_img, d_pts,
+        d_rot, d_trans, ws, ws_bytes,
+        [&](hipStream_t st, auto ni, auto no, T* d_img_atomic, int poses_per_slice, int64_t slices) {
+            return sample_smooth_bodies_bwd<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, (int)K, dv, image, points, body, rot, trans, d_img_atomic, d_pts, d_rot, d_trans,
+                poses_per_slice, slices);
+        },
+        [&](hipStream_t st, auto ni, auto no) {
+            return sample_smooth_bodies_image_tiled<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, (int)K, max_pose_group(flags), d_img, dv, points, body, rot, trans, ws, ws_bytes);
+        });
 }
 
 }  // namespace dpr
@@ -394,22 +222,14 @@ extern "C" {
 
 int dpr_resolve_algo_sample_smooth_bodies(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
                                           int64_t K) {
-    int64_t G = 0;
-    size_t need = 0;
-    int algo = DPR_ALGO_AUTO;
-    if (int rc = dpr::check_sample_smooth_bodies(op, &algo, 0u, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
-    return algo;
+    return dpr::resolver_value(dpr::check_sample_smooth_bodies(op, DPR_ALGO_AUTO, 0u, n_in, n_out, grid, P, B, K));
 }
 
 #define DPR_DEFINE_SAMPLE_SMOOTH_BODIES(SUF, T)                                                                     \
     size_t dpr_workspace_bytes_sample_smooth_bodies_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out, \
                                                              const int64_t* grid, int64_t P, int64_t B,             \
                                                              int64_t K) {                                           \
-        int64_t G = 0;                                                                                              \
-        size_t need = 0;                                                                                            \
-        return dpr::check_sample_smooth_bodies(op, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need)             \
-                   ? (size_t)-1                                                                                     \
-                   : need;                                                                                          \
+        return dpr::query_value(dpr::check_sample_smooth_bodies(op, algo, flags, n_in, n_out, grid, P, B, K));      \
     }                                                                                                               \
     int dpr_sample_smooth_bodies_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,              \
                                           const int64_t* grid, int64_t P, int64_t B, int64_t K, T* values,          \
@@ -436,20 +256,13 @@ DPR_DEFINE_SAMPLE_SMOOTH_BODIES(f64, double)
 
 int dpr_resolve_algo_smooth_bodies(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
                                    int64_t K) {
-    int64_t G = 0;
-    size_t need = 0;
-    int algo = DPR_ALGO_AUTO;
-    if (int rc = dpr::check_smooth_bodies(op, &algo, 0u, n_in, n_out, grid, P, B, K, &G, &need)) return rc;
-    return algo;
+    return dpr::resolver_value(dpr::check_smooth_bodies(op, DPR_ALGO_AUTO, 0u, n_in, n_out, grid, P, B, K));
 }
 
 #define DPR_DEFINE_SMOOTH_BODIES(SUF, T)                                                                          \
     size_t dpr_workspace_bytes_smooth_bodies_ex_##SUF(int op, int algo, unsigned flags, int n_in, int n_out,      \
                                                       const int64_t* grid, int64_t P, int64_t B, int64_t K) {     \
-        int64_t G = 0;                                                                                            \
-        size_t need = 0;                                                                                          \
-        return dpr::check_smooth_bodies(op, &algo, flags, n_in, n_out, grid, P, B, K, &G, &need) ? (size_t)-1     \
-                                                                                                  : need;         \
+        return dpr::query_value(dpr::check_smooth_bodies(op, algo, flags, n_in, n_out, grid, P, B, K));           \
     }                                                                                                             \
     int dpr_raster_smooth_bodies_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,            \
                                           const int64_t* grid, int64_t P, int64_t B, int64_t K, T* out,           \
@@ -478,21 +291,14 @@ DPR_DEFINE_SMOOTH_BODIES(f64, double)
 
 int dpr_resolve_algo_smooth_bodies_jvp(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t K,
                                        int64_t V) {
-    int64_t G = 0;
-    size_t need = 0;
-    int algo = DPR_ALGO_AUTO;
-    if (int rc = dpr::check_smooth_bodies_jvp(&algo, 0u, n_in, n_out, grid, P, B, K, V, &G, &need)) return rc;
-    return algo;
+    return dpr::resolver_value(dpr::check_smooth_bodies_jvp(DPR_ALGO_AUTO, 0u, n_in, n_out, grid, P, B, K, V));
 }
 
 #define DPR_DEFINE_SMOOTH_BODIES_JVP(SUF, T)                                                                      \
     size_t dpr_workspace_bytes_smooth_bodies_jvp_ex_##SUF(int algo, unsigned flags, int n_in, int n_out,          \
                                                           const int64_t* grid, int64_t P, int64_t B, int64_t K,   \
                                                           int64_t V) {                                            \
-        int64_t G = 0;                                                                                            \
-        size_t need = 0;                                                                                          \
-        return dpr::check_smooth_bodies_jvp(&algo, flags, n_in, n_out, grid, P, B, K, V, &G, &need) ? (size_t)-1  \
-                                                                                                     : need;      \
+        return dpr::query_value(dpr::check_smooth_bodies_jvp(algo, flags, n_in, n_out, grid, P, B, K, V));        \
     }                                                                                                             \
     int dpr_raster_smooth_bodies_jvp_ex_##SUF(                                                                    \
         void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,   \

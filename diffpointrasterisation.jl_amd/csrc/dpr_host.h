@@ -50,11 +50,16 @@ int check_alignment(const void* ws, std::initializer_list<const void*> data) {
         return fail(DPR_ERR_INVALID_ARG, "a data pointer is not aligned to its element type");
     return DPR_OK;
 }
+// (the body index of a point, the rigid-body families' int32_t array; NULL where the family has none)
+inline int check_body_alignment(const void* body) {
+    return ((uintptr_t)body & 3) ? fail(DPR_ERR_INVALID_ARG, "body is not aligned to its element type (int32_t)")
+                                 : DPR_OK;
+}
 
 int check_common(int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t* G_out);
 // (a launch of one thread per point counts its blocks of kBlock points in 31 bits)
 inline int check_point_blocks(int64_t P) {
-    return (P + kBlock - 1) / kBlock > 0x7fffffffLL ? fail(DPR_ERR_INVALID_ARG, "P too large") : DPR_OK;
+    return P / kBlock + (P % kBlock != 0) > 0x7fffffffLL ? fail(DPR_ERR_INVALID_ARG, "P too large") : DPR_OK;
 }
 int resolve_algo(int algo, int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, int64_t G,
                  unsigned* flags);
