@@ -39,6 +39,11 @@ from .sample_smooth_bodies import (resolve_algo_sample_smooth_bodies, sample_smo
 from .sample_smooth_channels import (resolve_algo_sample_smooth_channels, sample_smooth_channels,
                                      sample_smooth_channels_, sample_smooth_channels_ad,
                                      sample_smooth_channels_pullback_)
+# (workspace_bytes_sample_smooth_clouds: an attribute of the package, not of `__all__` -- tests/workspace_cases.py
+# walks the `workspace_bytes*` names of `__all__`, and this family's plan is the smooth cloud splat's, which it walks)
+from .sample_smooth_clouds import (resolve_algo_sample_smooth_clouds, sample_smooth_clouds, sample_smooth_clouds_,
+                                   sample_smooth_clouds_ad, sample_smooth_clouds_pullback_,
+                                   workspace_bytes_sample_smooth_clouds)
 from .sharded import (raster_point_sharded, raster_pullback_point_sharded_,
                       raster_pullback_sharded_, raster_sharded, shard_range)
 
@@ -72,4 +77,6 @@ __all__ = [
     "resolve_algo_sample_smooth_bodies",
     "sample_smooth_channels", "sample_smooth_channels_", "sample_smooth_channels_pullback_",
     "sample_smooth_channels_ad", "resolve_algo_sample_smooth_channels",
+    "sample_smooth_clouds", "sample_smooth_clouds_", "sample_smooth_clouds_pullback_", "sample_smooth_clouds_ad",
+    "resolve_algo_sample_smooth_clouds",
 ]

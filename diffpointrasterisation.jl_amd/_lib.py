@@ -96,6 +96,10 @@ EXPORTS = [
     "dpr_workspace_bytes_sample_smooth_channels_ex_f64", "dpr_sample_smooth_channels_ex_f32",
     "dpr_sample_smooth_channels_ex_f64", "dpr_sample_smooth_channels_pullback_ex_f32",
     "dpr_sample_smooth_channels_pullback_ex_f64",
+    "dpr_resolve_algo_sample_smooth_clouds", "dpr_workspace_bytes_sample_smooth_clouds_ex_f32",
+    "dpr_workspace_bytes_sample_smooth_clouds_ex_f64", "dpr_sample_smooth_clouds_ex_f32",
+    "dpr_sample_smooth_clouds_ex_f64", "dpr_sample_smooth_clouds_pullback_ex_f32",
+    "dpr_sample_smooth_clouds_pullback_ex_f64",
 ]
 
 _lib = None
@@ -361,6 +365,19 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, f"dpr_sample_smooth_channels_pullback_ex_{suf}")
         f.restype = i
         f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64, i64] + [vp] * 9 + [vp, sz]
+    L.dpr_resolve_algo_sample_smooth_clouds.restype = i
+    L.dpr_resolve_algo_sample_smooth_clouds.argtypes = [i, i, i, vp, i64, i64]
+    for suf in ("f32", "f64"):
+        f = getattr(L, f"dpr_workspace_bytes_sample_smooth_clouds_ex_{suf}")
+        f.restype = sz
+        f.argtypes = [i, i, ctypes.c_uint, i, i, vp, i64, i64]
+        # the argument lists of dpr_sample_smooth_ex_* / dpr_sample_smooth_pullback_ex_*
+        f = getattr(L, f"dpr_sample_smooth_clouds_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64] + [vp] * 5 + [vp, sz]
+        f = getattr(L, f"dpr_sample_smooth_clouds_pullback_ex_{suf}")
+        f.restype = i
+        f.argtypes = [vp, i, ctypes.c_uint, i, i, vp, i64, i64] + [vp] * 9 + [vp, sz]
     L.dpr_comm_unique_id.restype = i
     L.dpr_comm_unique_id.argtypes = [vp, sz]
     L.dpr_comm_init.restype = i

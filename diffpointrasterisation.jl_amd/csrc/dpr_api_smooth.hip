@@ -1,8 +1,8 @@
-// The smooth entry points of libdpr -- splat, sampling, forward mode, per-pose clouds, weight channels and sampling of
-// channel images: what each family is, its AUTO rule, its extent and size bounds, and the C ABI.  The checks, pointer
-// checks, stream prologues and entry-point skeletons they share: dpr_host_smooth.h (core: dpr_api.hip; kernels and
-// their launches: dpr_smooth.hip, dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip; the smooth splat of rigid
-// bodies: dpr_api_smooth_bodies.hip).
+// The smooth entry points of libdpr -- splat, sampling, forward mode, per-pose clouds and sampling at them, weight
+// channels and sampling of channel images: what each family is, its AUTO rule, its extent and size bounds, and the C
+// ABI.  The checks, pointer checks, stream prologues and entry-point skeletons they share: dpr_host_smooth.h (core:
+// dpr_api.hip; kernels and their launches: dpr_smooth.hip, dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip,
+// dpr_sample_smooth_clouds.hip; the smooth splat of rigid bodies: dpr_api_smooth_bodies.hip).
 #include <hip/hip_runtime.h>
 
 #include "dpr_host_smooth.h"
@@ -228,17 +228,19 @@ static int resolve_algo_smooth_clouds(int op, int n_out, const int64_t* grid, in
     return bg * P >= min_work && P / kSmoothCloudsTiledMinPointsPerTile >= tiles ? DPR_ALGO_TILED : DPR_ALGO_ATOMIC;
 }
 
+// 64-bit offsets: cloud b starts at b * P * n_in, plane b at b * G
+static int check_cloud_sizes(int n_in, int64_t P, int64_t B, int64_t G) {
+    if (int rc = check_point_blocks(P)) return rc;
+    if (B > 0 && (P > ((int64_t)1 << 60) / B / n_in || G > ((int64_t)1 << 62) / B))
+        return fail(DPR_ERR_INVALID_ARG, "B * P * n_in or the image (G * B) too large");
+    return DPR_OK;
+}
+
 static SmoothCall check_smooth_clouds(int op, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
                                       int64_t P, int64_t B) {
     return smooth_checks(
         kSmoothClouds, op, algo, flags, n_in, n_out, grid, P, B, no_extent,
-        [&](int64_t G) {
-            // 64-bit offsets: cloud b starts at b * P * n_in, plane b at b * G
-            if (int rc = check_point_blocks(P)) return rc;
-            if (B > 0 && (P > ((int64_t)1 << 60) / B / n_in || G > ((int64_t)1 << 62) / B))
-                return fail(DPR_ERR_INVALID_ARG, "B * P * n_in or the image (G * B) too large");
-            return (int)DPR_OK;
-        },
+        [&](int64_t G) { return check_cloud_sizes(n_in, P, B, G); },
         [&] { return resolve_algo_smooth_clouds(op, n_out, grid, P, B); });
 }
 
@@ -270,6 +272,70 @@ static int pullback_smooth_clouds_impl(void* stream, int algo, unsigned flags, i
         d_trans, d_bg, d_ow, d_pw, ws, [&](hipStream_t st, auto ni, auto no, int, int64_t) {
             return smooth_clouds_bwd_atomic<T, decltype(ni)::value, decltype(no)::value>(
                 st, grid, c.G, P, B, g, points, rot, trans, ow, pw, d_pts, d_rot, d_trans, d_ow, d_pw);
+        });
+}
+
+// ---------------------------------------------------------------- smooth sampling at per-pose clouds
+// dpr_sample_smooth_clouds_ex_* / dpr_sample_smooth_clouds_pullback_ex_* (include/dpr.h, "SMOOTH SAMPLING, PER-POSE
+// CLOUDS"; kernels: dpr_sample_smooth_clouds.hip).  Forward: DPR_ALGO_ATOMIC, one thread per (point, pose).  Pullback:
+// DPR_ALGO_ATOMIC, the fused kernel with image atomics; DPR_ALGO_TILED, the same kernel without them, then ds_dimage
+// from the tiled forward of the smooth cloud splat, the poses binned in its groups (DPR_FLAG_MAX_POSE_GROUP honoured).
+constexpr SmoothFamily kSmoothCloudSampling{"smooth sampling at per-pose clouds", kTiledPullback,
+                                            /*residual_refusal*/ false, /*group_plan*/ true, kGroupIgnored,
+                                            /*has_body*/ false, /*needs_point_weight*/ false,
+                                            /*pullback_slices_poses*/ false, /*per_pose_clouds*/ true};
+
+// AUTO: the forward is ATOMIC; the pullback is TILED where the forward of the smooth cloud splat of the shape would
+// be.  That rule was measured for the splat; this op's own times: profiles/sample_smooth_clouds_probe.txt.
+static int resolve_algo_sample_smooth_clouds(int op, int n_out, const int64_t* grid, int64_t P, int64_t B) {
+    if (op == DPR_OP_PULLBACK) return resolve_algo_smooth_clouds(DPR_OP_RASTER, n_out, grid, P, B);
+    return DPR_ALGO_ATOMIC;
+}
+
+static SmoothCall check_sample_smooth_clouds(int op, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t* grid, int64_t P, int64_t B) {
+    return smooth_checks(
+        kSmoothCloudSampling, op, algo, flags, n_in, n_out, grid, P, B, no_extent,
+        [&](int64_t G) {
+            if (int rc = check_cloud_sizes(n_in, P, B, G)) return rc;
+            // values[b, p] at b * P + p (smooth sampling's bound; the clouds' B * P * n_in is the tighter one today)
+            if (B > 0 && P > ((int64_t)1 << 62) / B) return fail(DPR_ERR_INVALID_ARG, "P * B too large");
+            return (int)DPR_OK;
+        },
+        [&] { return resolve_algo_sample_smooth_clouds(op, n_out, grid, P, B); });
+}
+
+template <typename T>
+static int sample_smooth_clouds_impl(void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid,
+                                     int64_t P, int64_t B, T* values, const T* image, const T* points, const T* rot,
+                                     const T* trans, void* ws, size_t) {
+    const SmoothCall c = check_sample_smooth_clouds(DPR_OP_RASTER, algo, flags, n_in, n_out, grid, P, B);
+    return smooth_sample_forward<T>(
+        kSmoothCloudSampling, c, stream, n_in, n_out, P, B, values, image, points, nullptr, rot, trans, ws,
+        [&](hipStream_t st, auto ni, auto no, int, int64_t) {
+            return sample_smooth_clouds_fwd<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, values, image, points, rot, trans);
+        });
+}
+
+template <typename T>
+static int sample_smooth_clouds_pullback_impl(void* stream, int algo, unsigned flags, int n_in, int n_out,
+                                              const int64_t* grid, int64_t P, int64_t B, const T* dv, const T* image,
+                                              const T* points, const T* rot, const T* trans, T* d_img, T* d_pts,
+                                              T* d_rot, T* d_trans, void* ws, size_t ws_bytes) {
+    const SmoothCall c = check_sample_smooth_clouds(DPR_OP_PULLBACK, algo, flags, n_in, n_out, grid, P, B);
+    return smooth_sample_pullback<T>(
+        kSmoothCloudSampling, c, stream, n_in, n_out, P, B, B, B, dv, image, points, nullptr, rot, trans, d_img, d_pts,
+        d_rot, d_trans, ws, ws_bytes,
+        [&](hipStream_t st, auto ni, auto no, T* d_img_atomic, int, int64_t) {
+            return sample_smooth_clouds_bwd<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, dv, image, points, rot, trans, d_img_atomic, d_pts, d_rot, d_trans);
+        },
+        [&](hipStream_t st, auto ni, auto no) -> int {
+            // ds_dvalues (B, P) is a point_weight of the smooth cloud splat: the planes are what
+            // dpr_raster_smooth_clouds_ex_*(DPR_ALGO_TILED) adds for those weights with out_weight 1
+            return smooth_clouds_fwd_tiled<T, decltype(ni)::value, decltype(no)::value>(
+                st, grid, c.G, P, B, max_pose_group(flags), d_img, points, rot, trans, nullptr, dv, ws, ws_bytes);
         });
 }
 
@@ -550,6 +616,37 @@ int dpr_resolve_algo_smooth_clouds(int op, int n_in, int n_out, const int64_t* g
 DPR_DEFINE_SMOOTH_CLOUDS(f32, float)
 DPR_DEFINE_SMOOTH_CLOUDS(f64, double)
 #undef DPR_DEFINE_SMOOTH_CLOUDS
+
+int dpr_resolve_algo_sample_smooth_clouds(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B) {
+    return dpr::resolver_value(dpr::check_sample_smooth_clouds(op, DPR_ALGO_AUTO, 0u, n_in, n_out, grid, P, B));
+}
+
+#define DPR_DEFINE_SAMPLE_SMOOTH_CLOUDS(SUF, T)                                                                \
+    size_t dpr_workspace_bytes_sample_smooth_clouds_ex_##SUF(int op, int algo, unsigned flags, int n_in,       \
+                                                             int n_out, const int64_t* grid, int64_t P,        \
+                                                             int64_t B) {                                      \
+        return dpr::query_value(dpr::check_sample_smooth_clouds(op, algo, flags, n_in, n_out, grid, P, B));    \
+    }                                                                                                          \
+    int dpr_sample_smooth_clouds_ex_##SUF(void* stream, int algo, unsigned flags, int n_in, int n_out,         \
+                                          const int64_t* grid, int64_t P, int64_t B, T* values,                \
+                                          const T* image, const T* points, const T* rotation,                  \
+                                          const T* translation, void* workspace, size_t workspace_bytes) {     \
+        return dpr::sample_smooth_clouds_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B, values, image,  \
+                                                 points, rotation, translation, workspace, workspace_bytes);   \
+    }                                                                                                          \
+    int dpr_sample_smooth_clouds_pullback_ex_##SUF(                                                            \
+        void* stream, int algo, unsigned flags, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B, \
+        const T* ds_dvalues, const T* image, const T* points, const T* rotation, const T* translation,         \
+        T* ds_dimage, T* ds_dpoints, T* ds_drotation, T* ds_dtranslation, void* workspace,                     \
+        size_t workspace_bytes) {                                                                              \
+        return dpr::sample_smooth_clouds_pullback_impl<T>(stream, algo, flags, n_in, n_out, grid, P, B,        \
+                                                          ds_dvalues, image, points, rotation, translation,    \
+                                                          ds_dimage, ds_dpoints, ds_drotation,                 \
+                                                          ds_dtranslation, workspace, workspace_bytes);        \
+    }
+DPR_DEFINE_SAMPLE_SMOOTH_CLOUDS(f32, float)
+DPR_DEFINE_SAMPLE_SMOOTH_CLOUDS(f64, double)
+#undef DPR_DEFINE_SAMPLE_SMOOTH_CLOUDS
 
 int dpr_resolve_algo_smooth_channels(int op, int n_in, int n_out, const int64_t* grid, int64_t P, int64_t B,
                                      int64_t C) {

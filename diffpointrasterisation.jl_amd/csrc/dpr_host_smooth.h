@@ -35,6 +35,7 @@ struct SmoothFamily {
     bool has_body;              // rigid bodies: a `body` pointer, and pose pointers that P == 0 leaves unread
     bool needs_point_weight;    // point_weight may not be NULL (C weights per point)
     bool pullback_slices_poses; // the splat pullback takes pose_slices and has nothing to launch for P == 0
+    bool per_pose_clouds = false;  // sampling: ds_dpoints holds B clouds, each entry stored by its own (point, pose)
 };
 
 // what the funnel hands back: the status, voxels per pose, the resolved algorithm, the workspace bytes
@@ -353,7 +354,9 @@ int smooth_sample_pullback(const SmoothFamily& fam, const SmoothCall& c, void* s
                                             d_trans, ws, ws_bytes))
         return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = sample_pullback_prologue(st, n_in, n_out, c.G, P, B, planes, poses, d_img, d_pts, d_rot, d_trans))
+    // (per-pose clouds: ds_dpoints is empty with B == 0, so nothing of it is zeroed)
+    if (int rc = sample_pullback_prologue(st, n_in, n_out, c.G, fam.per_pose_clouds ? 0 : P, B, planes, poses, d_img,
+                                          d_pts, d_rot, d_trans))
         return rc;
     if (P == 0 || B == 0) return DPR_OK;
     const bool tiled = c.algo == DPR_ALGO_TILED;

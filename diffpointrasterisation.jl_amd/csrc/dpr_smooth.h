@@ -1,6 +1,6 @@
 // The smooth splat (include/dpr.h, "SMOOTH SPLAT"): quadratic B-spline weights on 3^N cells per point.
-// The launchers of dpr_smooth.hip, dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip, dpr_smooth_bodies.hip and
-// dpr_sample_smooth_bodies.hip that dpr_api_smooth.hip and dpr_api_smooth_bodies.hip call.  The tiles of
+// The launchers of dpr_smooth.hip, dpr_smooth_channels.hip, dpr_sample_smooth_channels.hip,
+// dpr_sample_smooth_clouds.hip, dpr_smooth_bodies.hip and dpr_sample_smooth_bodies.hip that dpr_api_smooth.hip and dpr_api_smooth_bodies.hip call.  The tiles of
 // DPR_ALGO_TILED (SmoothTileShape, SmoothTiles, smooth_tiles) and their index arithmetic, shared by the host plan and
 // every key and tile kernel: dpr_smooth_tile.h.
 #pragma once
@@ -190,6 +190,19 @@ template <typename T, int NI, int NO>
 int sample_smooth_channels_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, int C,
                                const T* dv, const T* image, const T* points, const T* rot, const T* trans, T* d_img,
                                T* d_pts, T* d_rot, T* d_trans, int poses_per_slice, int64_t slices);
+
+// Smooth sampling at per-pose clouds (include/dpr.h, "SMOOTH SAMPLING, PER-POSE CLOUDS"; kernels:
+// dpr_sample_smooth_clouds.hip): cloud b at points + b * P * NI and d_pts likewise, values / dv (B, P) with the point
+// index fastest -- dv is a `pw` of smooth_clouds_fwd_tiled.  One thread per (point, pose), no pose slices: d_pts is
+// stored, never zeroed or accumulated.  d_img, d_rot and d_trans are zeroed by the caller (dpr_api_smooth.hip); any of
+// the four outputs may be NULL (none: nothing is launched); `image` is read only for d_pts / d_rot / d_trans.
+template <typename T, int NI, int NO>
+int sample_smooth_clouds_fwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, T* values,
+                             const T* image, const T* points, const T* rot, const T* trans);
+template <typename T, int NI, int NO>
+int sample_smooth_clouds_bwd(hipStream_t st, const int64_t* grid, int64_t G, int64_t P, int64_t B, const T* dv,
+                             const T* image, const T* points, const T* rot, const T* trans, T* d_img, T* d_pts,
+                             T* d_rot, T* d_trans);
 
 // Smooth sampling at the points of rigid bodies (include/dpr.h, "SMOOTH SAMPLING, RIGID BODIES"; kernels:
 // dpr_sample_smooth_bodies.hip): smooth sampling through pose b * K + body[p].  The same contract with the caller

@@ -1,7 +1,7 @@
 // Device helpers of the smooth splat (include/dpr.h, "SMOOTH SPLAT") that the kernels of dpr_smooth.hip,
-// dpr_smooth_channels.hip, dpr_smooth_bodies.hip and dpr_sample_smooth_channels.hip share: the cell of a point, the
-// B-spline weights of an axis and their derivatives, the per-axis offsets of the 3^N cells, the pullback's sums of one
-// (point, pose), and the rows of one tangent's deposits in forward mode.
+// dpr_smooth_channels.hip, dpr_smooth_bodies.hip, dpr_sample_smooth_channels.hip and dpr_sample_smooth_clouds.hip
+// share: the cell of a point, the B-spline weights of an axis and their derivatives, the per-axis offsets of the 3^N
+// cells, the pullback's sums of one (point, pose), and the rows of one tangent's deposits in forward mode.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1727,6 +1727,98 @@ int dpr_sample_smooth_channels_pullback_ex_f64(void *stream, int algo, unsigned 
                                                double *ds_dpoints, double *ds_drotation, double *ds_dtranslation,
                                                void *workspace, size_t workspace_bytes);
 
+/* ---- SMOOTH SAMPLING, PER-POSE CLOUDS: quadratic B-spline interpolation of image b at cloud b, C1 ---------------------
+ * SMOOTH SAMPLING with a different cloud for every pose: the transpose of dpr_raster_smooth_clouds_* with respect to
+ * the point weights.  With coord_d, j0_d, u_d, w_d and w'_d of SMOOTH SPLAT and its acceptance rule (-1 <= coord_d <
+ * n_d + 1 on every axis, tested in floating point; NaN / Inf rejected; cells outside the grid dropped one by one), all
+ * from R_b points[b, p] + t_b:
+ *     values[b, p] = sum over s in {-1, 0, +1}^n_out with j0 + s inside the grid of
+ *                    image[j0 + s, b] * prod_d w_d(s_d)
+ *     values[b, p] = 0 for a rejected point
+ * Row b is dpr_sample_smooth_ex_* of (image[.., b], points[b], R_b, t_b) with B = 1, BIT FOR BIT in fp32 and fp64 (no
+ * atomics, no sum across threads, the same order of operations).  What a loop of B single-pose smooth sampling calls
+ * computes, in one call.  The adjoint identity, per pose:
+ *     sum_v (raster_smooth_clouds(pw) - background)[v, b] * image[v, b] = out_weight[b] * sum_p pw[b, p] * values[b, p].
+ * The pullback takes ds_dvalues (B, P) and writes
+ *   ds_dimage[.., b]    dpr_raster_smooth_clouds_ex_* with point_weight = ds_dvalues, background 0, out_weight 1
+ *   and, with scaled_k = ds_dvalues[b, p] * n_k / 2 * sum_s image[j0 + s, b] * w'_k(s_k) * prod_{d != k} w_d(s_d),
+ *   ds_dtranslation[b] = sum_p scaled,   ds_drotation[b] = sum_p scaled * points[b, p]^T,
+ *   ds_dpoints[b, p] = R_b^T * scaled  -- one pose per point, no sum over poses; 0 for a rejected point
+ * -- the exact derivative; no cell is held fixed.  ds_dpoints[b] has the bits of the single-pose
+ * dpr_sample_smooth_pullback_ex_*(DPR_ALGO_ATOMIC) for pose b.
+ * Layouts: points, ds_dpoints   n_in x P x B as for PER-POSE CLOUDS: cloud b at b * P * n_in;
+ *          values, ds_dvalues   (B, P) contiguous, point index fastest: row b at b * P -- the layout of point_weight of
+ *                               dpr_raster_smooth_clouds_ex_*.  (Not the P x B of SMOOTH SAMPLING read as a transpose:
+ *                               the memory is the same, the pose is the slow index in both.)
+ *          image, ds_dimage     (n_1, .., n_N, B) as `out` of dpr_raster_ex_*;
+ *          ds_drotation         n_out x n_in column-major per pose;  ds_dtranslation  n_out per pose.
+ * Clouds of different sizes: pad them to a common P.  The values of the padded points are to be ignored and their
+ * ds_dvalues set to 0: such a point gets ds_dpoints = 0, adds nothing to the pose gradients and deposits nothing.
+ * (n_in, n_out): (2,2), (3,3) and (3,2); every other pair DPR_ERR_UNSUPPORTED_DIMS.  op: DPR_OP_RASTER (the forward)
+ * or DPR_OP_PULLBACK.  Outputs are overwritten, not accumulated.  Any pullback output may be NULL (not wanted, no
+ * work done for it); at least one must be given; `image` may be NULL when only ds_dimage is wanted.
+ * Algorithms (DPR_ALGO_CHUNKED, DPR_ALGO_ORDERED, unknown ones: DPR_ERR_UNSUPPORTED_ALGO).
+ *   Forward  DPR_ALGO_ATOMIC (= AUTO; DPR_ALGO_TILED: DPR_ERR_UNSUPPORTED_ALGO): one thread per (point, pose), a block
+ *            inside one pose, the poses strided over at most 65 535 rows of blocks; the 3^N gathers issued one
+ *            3^(N-1) plane at a time, a dropped cell replaced by 0 with a select; every value stored coalesced; no
+ *            atomics, workspace 0.
+ *   Pullback DPR_ALGO_ATOMIC: one fused kernel, one thread per (point, pose): from one set of gathers the point
+ *            gradient (one plain store) and the per-pose sums (wave -> block -> one atomic per scalar per block), and
+ *            ds_dvalues * prod w into ds_dimage with 3^N global atomics; workspace 0.
+ *   Pullback DPR_ALGO_TILED: the same kernel without the image atomics, then ds_dimage: the planes zeroed, then the
+ *            tiled forward of SMOOTH SPLAT, PER-POSE CLOUDS with point_weight = ds_dvalues and out_weight NULL, the
+ *            poses binned in its GROUPS -- the planes are what dpr_raster_smooth_clouds_ex_*(DPR_ALGO_TILED) adds for
+ *            those weights.  GROUP SIZE, LIMITS and COST: those of SMOOTH SPLAT, PER-POSE CLOUDS.  Workspace:
+ *            dpr_workspace_bytes_smooth_clouds_ex_*(DPR_OP_RASTER, DPR_ALGO_TILED, flags, ..) for the same shape and
+ *            flags; it is required only when ds_dimage is asked for and P, B > 0.
+ * AUTO (dpr_resolve_algo_sample_smooth_clouds), from the shape alone: the forward DPR_ALGO_ATOMIC; the pullback
+ * DPR_ALGO_TILED exactly where dpr_resolve_algo_smooth_clouds(DPR_OP_RASTER, ..) returns it, DPR_ALGO_ATOMIC otherwise
+ * (that rule was measured for the splat; profiles/sample_smooth_clouds_probe.txt has this pullback's own times on
+ * either path and names the rows where the rule picks the slower one).
+ * Flags: DPR_FLAG_MAX_POSE_GROUP(n) is HONOURED by the DPR_ALGO_TILED pullback (pass the same flags to the workspace
+ * query) and ignored elsewhere; KEEP / REUSE are refused (DPR_ERR_UNSUPPORTED_ALGO); the others accepted and ignored.
+ * Workspace and stream: the contract of dpr_raster_ex_* holds -- the call only enqueues on `stream`, writes only
+ * inside [workspace, workspace + workspace_bytes), and the initial contents of the workspace do not matter.
+ * Summation order.  values and ds_dpoints: no sum across threads -- plane by plane in smooth_point_backward's order, as
+ * SMOOTH SAMPLING; reproducible bit for bit.  Per-pose sums: lanes of a wave, waves of a block, then one atomic per
+ * block: unordered across blocks.  ds_dimage: DPR_ALGO_ATOMIC global atomics, unordered; DPR_ALGO_TILED the order of
+ * the tiled forward of SMOOTH SPLAT, PER-POSE CLOUDS (f64 cells in LDS, then at most 3^N tile partials per cell), which
+ * depends on the group size.
+ * Errors (status, dpr_last_error text, nothing launched, outputs untouched): a pair outside the three
+ * DPR_ERR_UNSUPPORTED_DIMS (the grid is not looked at first); a bad op, negative P / B, a bad grid, B * P * n_in beyond
+ * 2^60 or G * B beyond 2^62, all pullback outputs NULL, a NULL input that the call would read, a misaligned data
+ * pointer DPR_ERR_INVALID_ARG; KEEP / REUSE, DPR_ALGO_CHUNKED / DPR_ALGO_ORDERED / an unknown algorithm, a
+ * DPR_ALGO_TILED forward and a DPR_ALGO_TILED pullback outside the LIMITS DPR_ERR_UNSUPPORTED_ALGO; a workspace
+ * smaller than dpr_workspace_bytes_sample_smooth_clouds_ex_* (with ds_dimage wanted) or not 256-byte aligned
+ * DPR_ERR_WORKSPACE.  P = 0 or B = 0: DPR_OK, the outputs that still have elements zeroed.
+ * dpr_workspace_bytes_sample_smooth_clouds_ex_* returns (size_t)-1 for every refused combination,
+ * dpr_resolve_algo_sample_smooth_clouds a negative status. */
+int dpr_resolve_algo_sample_smooth_clouds(int op, int n_in, int n_out, const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_sample_smooth_clouds_ex_f32(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                       const int64_t *grid, int64_t P, int64_t B);
+size_t dpr_workspace_bytes_sample_smooth_clouds_ex_f64(int op, int algo, unsigned flags, int n_in, int n_out,
+                                                       const int64_t *grid, int64_t P, int64_t B);
+int dpr_sample_smooth_clouds_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                                    int64_t P, int64_t B, float *values, const float *image, const float *points,
+                                    const float *rotation, const float *translation, void *workspace,
+                                    size_t workspace_bytes);
+int dpr_sample_smooth_clouds_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out, const int64_t *grid,
+                                    int64_t P, int64_t B, double *values, const double *image, const double *points,
+                                    const double *rotation, const double *translation, void *workspace,
+                                    size_t workspace_bytes);
+int dpr_sample_smooth_clouds_pullback_ex_f32(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t *grid, int64_t P, int64_t B, const float *ds_dvalues,
+                                             const float *image, const float *points, const float *rotation,
+                                             const float *translation, float *ds_dimage, float *ds_dpoints,
+                                             float *ds_drotation, float *ds_dtranslation, void *workspace,
+                                             size_t workspace_bytes);
+int dpr_sample_smooth_clouds_pullback_ex_f64(void *stream, int algo, unsigned flags, int n_in, int n_out,
+                                             const int64_t *grid, int64_t P, int64_t B, const double *ds_dvalues,
+                                             const double *image, const double *points, const double *rotation,
+                                             const double *translation, double *ds_dimage, double *ds_dpoints,
+                                             double *ds_drotation, double *ds_dtranslation, void *workspace,
+                                             size_t workspace_bytes);
+
 /* Pose-independent spatial pre-sort of the model-frame points along a Hilbert curve (any run
  * of consecutive sorted points is a compact blob; 3-D: 30-bit keys, 1024^3 cells over [-1, 1)^3) --
  * not in the reference; every algorithm here is faster on coherent input and the sort only depends
