@@ -296,18 +296,24 @@ static BinHeader make_header(const int64_t* grid, int64_t P, const T* points, co
     return h;
 }
 // device side: does the workspace header match `want` and the pose in memory?
+// Every word is loaded, then compared: the differences are OR-ed together, so no branch sits
+// between two loads (a chain of && is a chain of dependent round trips in front of everything
+// the caller does next; what is left are the waits the compiler puts between its groups of scalar
+// loads, profiles/reuse_chain.md).  The header always lies inside the workspace, whatever it holds.
 __device__ __forceinline__ bool header_matches(const BinHeader* hdr, const BinHeader& want,
                                                const uint32_t* rot, int rot_words,
                                                const uint32_t* trans, int trans_words) {
-    bool ok = hdr->magic == kBinMagic && hdr->state == kBinValid && hdr->elem == want.elem &&
-              hdr->n_in == want.n_in && hdr->n_out == want.n_out && hdr->has_pw == want.has_pw &&
-              hdr->P == want.P && hdr->grid[0] == want.grid[0] && hdr->grid[1] == want.grid[1] &&
-              hdr->grid[2] == want.grid[2] && hdr->points == want.points && hdr->pw == want.pw &&
-              hdr->layout == want.layout;
+    uint32_t diff = (hdr->magic ^ kBinMagic) | (hdr->state ^ kBinValid) | (hdr->elem ^ want.elem) |
+                    (hdr->n_in ^ want.n_in) | (hdr->n_out ^ want.n_out) | (hdr->has_pw ^ want.has_pw) |
+                    (uint32_t)(hdr->grid[0] ^ want.grid[0]) | (uint32_t)(hdr->grid[1] ^ want.grid[1]) |
+                    (uint32_t)(hdr->grid[2] ^ want.grid[2]) | (hdr->layout ^ want.layout);
+    const uint64_t wide = (uint64_t)(hdr->P ^ want.P) | (hdr->points ^ want.points) | (hdr->pw ^ want.pw);
     const uint32_t* pose = (const uint32_t*)hdr->pose;
-    for (int i = 0; i < rot_words; ++i) ok = ok && pose[i] == rot[i];
-    for (int i = 0; i < trans_words; ++i) ok = ok && pose[rot_words + i] == trans[i];
-    return ok;
+#pragma unroll
+    for (int i = 0; i < rot_words; ++i) diff |= pose[i] ^ rot[i];
+#pragma unroll
+    for (int i = 0; i < trans_words; ++i) diff |= pose[rot_words + i] ^ trans[i];
+    return diff == 0u && wide == 0u;
 }
 
 // Wait HERE for every outstanding global load / store of the wave (s_waitcnt vmcnt(0) through the
@@ -2357,6 +2363,49 @@ __global__ __launch_bounds__(256) void k_halo_gather(GridDesc<NO> gd, TileGeom<N
                                 (int)split_list[w / kSplitChunks], true, w % kSplitChunks);
 }
 
+// Epilogue of k_tile_gather: the per-tile partial sums of the per-pose scalars (f64), reduced later by
+// k_pose_reduce.  The NVAL - 2 sums a thread holds in T are parked in LDS as f64 (`park[k][thread]`, which
+// aliases the ds_dout tile: the first barrier is behind the record loop) and wave q adds up scalars q, q + NW,
+// ...: a lane takes its column of the GT / 64 rows, then ONE butterfly per scalar -- instead of NVAL butterflies
+// in every wave (15 of six bpermute round trips each in 3-D, for a tile whose threads hold 16 records or fewer).
+// The two sums of the staged image (ds_dbackground, loss) keep their order -- wave butterfly, then the waves in
+// index order -- so that ds_dbackground stays bit-identical.  Both barriers order LDS only: no wave waits for the
+// acknowledgement of the gradient records it has just stored.
+template <typename T, int GT, int NVAL>
+__device__ __forceinline__ void gather_block_sums(const T (&vals)[NVAL - 2], double bg_sum, double sq_sum,
+                                                  double* park, double (*red2)[2], bool with_loss,
+                                                  double* __restrict__ partials, int max_items) {
+    constexpr int NW = GT / kWave;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const double s_bg = wave_sum<double>(bg_sum), s_sq = wave_sum<double>(sq_sum);
+    lds_barrier();  // every thread has left the record loop: the tile may be overwritten
+#pragma unroll
+    for (int k = 0; k < NVAL - 2; ++k) park[k * GT + threadIdx.x] = (double)vals[k];
+    if (lane == 0) {
+        red2[wave][0] = s_bg;
+        red2[wave][1] = s_sq;
+    }
+    lds_barrier();
+    for (int k = wave; k < NVAL - 2; k += NW) {
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) s += park[k * GT + i * kWave + lane];
+        s = wave_sum<double>(s);
+        if (lane == 0) partials[(size_t)k * max_items + blockIdx.x] = s;
+    }
+    if (threadIdx.x < (with_loss ? 2 : 1)) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) s += red2[w][threadIdx.x];
+        partials[(size_t)(NVAL - 2 + threadIdx.x) * max_items + blockIdx.x] = s;
+    }
+}
+// do the parked sums fit inside the ds_dout tile (NVH elements of T)?  3-D: yes; a 2-D tile is smaller than the
+// parking area, and those instantiations keep the butterfly epilogue instead of growing their LDS
+template <typename T, int GT, int NVAL, int NVH> __host__ __device__ constexpr bool gather_park_fits() {
+    return (NVAL - 2) * GT * (int)sizeof(double) <= NVH * (int)sizeof(T);
+}
+
 // ------------------------------------------------------------------ pullback K4
 // UNPERM: the per-point gradient {d point, d point_weight} overwrites the point's record in
 // place (coalesced 16/32-byte stores in binned order); k_unpermute then brings it back to the
@@ -2374,8 +2423,15 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
     constexpr int NVH = tile_voxels_halo<NO>();
     constexpr int NVAL = NO * NI + NO + 3;  // dR | dt | d out_weight | d background | loss
     constexpr int NW = GT / kWave;
-    __shared__ T tile_g[NVH];
-    __shared__ double red[NW][NVAL];
+    constexpr bool PARK = gather_park_fits<T, GT, NVAL, NVH>();
+    __shared__ __align__(8) T tile_g[NVH];  // (PARK: the epilogue parks its sums in it)
+    __shared__ double red[NW][PARK ? 2 : NVAL];
+    // item, item count and the first image's pose are requested together (see k_tile_splat), and with
+    // them the words of the header check below: loads first, verdict after, nothing stored before it.
+    // (All of them lie inside the workspace whatever it holds: the grid has max_items blocks.)
+    const uint32_t n_it = *n_items;
+    WorkItem item = items[blockIdx.x];
+    Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b0);
     if (want.magic) {
         // DPR_FLAG_REUSE_BINNING: trust the lists in the workspace only if a KEEP_BINNING forward
         // with the same problem, buffers and pose wrote them and nobody has consumed them since
@@ -2385,10 +2441,6 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
         if (blockIdx.x == 0 && threadIdx.x == 0) hdr->verdict = ok ? 1u : 0u;
         if (!ok) return;  // k_unpermute / k_pose_reduce turn the verdict into NaN outputs
     }
-    // item, item count and the first image's pose are requested together (see k_tile_splat)
-    const uint32_t n_it = *n_items;
-    WorkItem item = items[blockIdx.x];
-    Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b0);
     if (blockIdx.x >= n_it) return;  // the grid is sized for the worst case
     // record ranges never leave the record buffer, whatever the lists say
     if (item.end > (uint32_t)P) item.end = (uint32_t)P;
@@ -2594,21 +2646,26 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
             if (ds_dpw) ds_dpw[p] += dpw_part;
         }
     }
-    // per-tile partial sums of the per-pose scalars (f64), reduced later by k_pose_reduce
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    if constexpr (PARK) {
+        gather_block_sums<T, GT, NVAL>(vals, bg_sum, sq_sum, (double*)tile_g, red, rs.target != nullptr, partials,
+                                       max_items);
+    } else {
+        // per-tile partial sums of the per-pose scalars (f64), reduced later by k_pose_reduce
+        const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
 #pragma unroll
-    for (int k = 0; k < NVAL; ++k) {
-        const double v = (k < NVAL - 2) ? (double)vals[k < NVAL - 2 ? k : 0]
-                                        : (k == NVAL - 2 ? bg_sum : sq_sum);
-        const double s = wave_sum<double>(v);
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < (rs.target ? NVAL : NVAL - 1)) {
-        double s = 0.0;
+        for (int k = 0; k < NVAL; ++k) {
+            const double v = (k < NVAL - 2) ? (double)vals[k < NVAL - 2 ? k : 0]
+                                            : (k == NVAL - 2 ? bg_sum : sq_sum);
+            const double s = wave_sum<double>(v);
+            if (lane == 0) red[wave][k] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < (rs.target ? NVAL : NVAL - 1)) {
+            double s = 0.0;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) s += red[w][threadIdx.x];
-        partials[(size_t)threadIdx.x * max_items + blockIdx.x] = s;
+            for (int w = 0; w < NW; ++w) s += red[w][threadIdx.x];
+            partials[(size_t)threadIdx.x * max_items + blockIdx.x] = s;
+        }
     }
 }
 
@@ -2632,6 +2689,12 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
     constexpr int NW = GT / kWave;
     __shared__ T tile_g[NVH];
     __shared__ double red[NW][NVAL];
+    // item, item count and the first image's pose are requested together (see k_tile_splat), and with
+    // them the words of the header check below: loads first, verdict after, nothing stored before it.
+    // (All of them lie inside the workspace whatever it holds: the grid has max_items blocks.)
+    const uint32_t n_it = *n_items;
+    WorkItem item = items[blockIdx.x];
+    Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b0);
     if (want.magic) {
         // DPR_FLAG_REUSE_BINNING: trust the lists in the workspace only if a KEEP_BINNING forward
         // with the same problem, buffers and pose wrote them and nobody has consumed them since
@@ -2641,10 +2704,6 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
         if (blockIdx.x == 0 && threadIdx.x == 0) hdr->verdict = ok ? 1u : 0u;
         if (!ok) return;  // k_unpermute / k_pose_reduce turn the verdict into NaN outputs
     }
-    // item, item count and the first image's pose are requested together (see k_tile_splat)
-    const uint32_t n_it = *n_items;
-    WorkItem item = items[blockIdx.x];
-    Pose<T, NI, NO> ps = load_pose<T, NI, NO>(rot, trans, ow, b0);
     if (blockIdx.x >= n_it) return;  // the grid is sized for the worst case
     // record ranges never leave the record buffer, whatever the lists say (RUNS: load_runs)
     if (!RUNS && item.end > (uint32_t)P) item.end = (uint32_t)P;
@@ -2889,7 +2948,8 @@ __global__ __launch_bounds__(gather_threads<T>(), gather_waves_per_simd<T>()) vo
             }
         }
     }
-    // per-tile partial sums of the per-pose scalars (f64), reduced later by k_pose_reduce
+    // per-tile partial sums of the per-pose scalars (f64), reduced later by k_pose_reduce.  (Not parked as in
+    // k_tile_gather: with the run cursor's registers the fp32 3-D instantiation would need scratch for it.)
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
 #pragma unroll
     for (int k = 0; k < NVAL; ++k) {
@@ -2990,6 +3050,19 @@ __global__ __launch_bounds__(1024) void k_unpermute(int64_t P, int nb,
     }
     const unsigned ublock = blockIdx.x - (unsigned)reduce_blocks;
     const unsigned ublocks = gridDim.x - (unsigned)reduce_blocks;
+    // One block covers kUPB * 1024 consecutive points = one sub-chunk of the scatter: points of
+    // a sub-chunk that fell into the same tile sit next to each other in that tile's record
+    // run, so the 64-byte sectors this block fetches are shared among its own threads.
+    // The slots are requested BEFORE the verdict is looked at, which arrives while they fly:
+    // slot_of has P entries for every workspace of this plan, and no record is read through
+    // them before the verdict is known.
+    const int64_t base = (int64_t)xcd_slice(ublock, ublocks) * (kUPB * 1024) + threadIdx.x;
+    uint32_t slot[kUPB];
+#pragma unroll
+    for (int k = 0; k < kUPB; ++k) {
+        const int64_t p = base + k * 1024;
+        slot[k] = __builtin_nontemporal_load(&slot_of[p < P ? p : P - 1]);
+    }
     bool stale = hdr && hdr->verdict != 1u;
     if (hdr && pose_stride)  // a batch: every pose's header must have matched
         for (int j = 1; j < nb; ++j)
@@ -3007,16 +3080,6 @@ __global__ __launch_bounds__(1024) void k_unpermute(int64_t P, int nb,
             if (ds_dpw) ds_dpw[p] = nan;
         }
         return;
-    }
-    // One block covers kUPB * 1024 consecutive points = one sub-chunk of the scatter: points of
-    // a sub-chunk that fell into the same tile sit next to each other in that tile's record
-    // run, so the 64-byte sectors this block fetches are shared among its own threads.
-    const int64_t base = (int64_t)xcd_slice(ublock, ublocks) * (kUPB * 1024) + threadIdx.x;
-    uint32_t slot[kUPB];
-#pragma unroll
-    for (int k = 0; k < kUPB; ++k) {
-        const int64_t p = base + k * 1024;
-        slot[k] = __builtin_nontemporal_load(&slot_of[p < P ? p : P - 1]);
     }
     Rec4<T> g[kUPB];
 #pragma unroll
@@ -3085,6 +3148,22 @@ __global__ __launch_bounds__(1024, 8) void k_unpermute_runs(int64_t P, const Rec
     }
     const unsigned ublock = blockIdx.x - (unsigned)reduce_blocks;
     const unsigned ublocks = gridDim.x - (unsigned)reduce_blocks;
+    const int64_t base = (int64_t)xcd_slice(ublock, ublocks) * S;
+    const uint32_t nloc = (uint32_t)((P - base < S) ? P - base : S);  // points of this sub-chunk (>= 1)
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    // owner words and table entries, one round trip (position i: entry i; all indices stay inside the
+    // sub-chunk's nloc entries).  They are requested BEFORE the verdict is looked at, which arrives while
+    // they fly: the two map regions have these entries for every workspace of this plan, and nothing is
+    // read THROUGH them before the verdict is known.
+    uint32_t own[PPT], tab[PPT];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const uint32_t i = threadIdx.x + (uint32_t)k * 1024;
+        const uint32_t ic = i < nloc ? i : nloc - 1;
+        own[k] = __builtin_nontemporal_load(&run_lp[base + ic]);
+        if (i >= nloc) own[k] = kRunNone;
+        tab[k] = __builtin_nontemporal_load(&run_slot[base + ic]);
+    }
     if (hdr && hdr->verdict != 1u) {
         // REUSE_BINNING without a matching KEEP_BINNING forward: no gradient was computed
         const T nan = T(__builtin_nanf(""));
@@ -3098,20 +3177,6 @@ __global__ __launch_bounds__(1024, 8) void k_unpermute_runs(int64_t P, const Rec
             if (ds_dpw) ds_dpw[p] = nan;
         }
         return;
-    }
-    const int64_t base = (int64_t)xcd_slice(ublock, ublocks) * S;
-    const uint32_t nloc = (uint32_t)((P - base < S) ? P - base : S);  // points of this sub-chunk (>= 1)
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-    // owner words and table entries, one round trip (position i: entry i; all indices stay inside the
-    // sub-chunk's nloc entries)
-    uint32_t own[PPT], tab[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const uint32_t i = threadIdx.x + (uint32_t)k * 1024;
-        const uint32_t ic = i < nloc ? i : nloc - 1;
-        own[k] = __builtin_nontemporal_load(&run_lp[base + ic]);
-        if (i >= nloc) own[k] = kRunNone;
-        tab[k] = __builtin_nontemporal_load(&run_slot[base + ic]);
     }
     Rec4<T> zero;
 #pragma unroll
